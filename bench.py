@@ -1,7 +1,7 @@
 """
 bench.py — training graphs/sec of the MI355X-native GGNN hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -42,6 +42,8 @@ config.fuse_flags = the GI_FUSE launch-count reductions in use (include/graphinv
 config.host = what the timed loop cost the HOST per step: enqueue_ms_per_step (Python + torch + the library's launches)
 and wait_for_device_ms_per_step (blocked on the prefetched counts, i.e. the device is the bound when this is > 0); the
 counts of the next TWO batches are prefetched, so the host may run two steps ahead of the device.
+--dump-outputs DIR writes what the last timed step computed (dump_outputs) so that two builds can be compared output for
+output: the inputs and initial weights are seeded, identical from run to run for the same arguments.
 """
 import argparse
 import ctypes as C
@@ -452,6 +454,29 @@ def cpu_baseline(cfg, threads: int = 0, n_timed: int = 3):
                        + f", {threads} threads of {os.cpu_count()} host CPUs{probe}", **extra)
 
 
+DUMP_LIMIT_BYTES = 60_000_000     # the array data; the .npy headers stay well inside 64 MB
+
+
+def dump_outputs(out_dir: str, loss_val: float, model) -> None:
+    """What the last timed step left its caller, as float32 .npy files in `out_dir`: `loss` (the step's return value),
+    `param.<name>` (every parameter after the optimizer update) and `grad.<name>` (its all-reduced gradient).  If the
+    whole would exceed DUMP_LIMIT_BYTES, each tensor is written as the same fraction of its elements: a sorted sample
+    of flat indices drawn from a fixed seed, so that two runs write the same elements."""
+    arrays = {"loss": torch.tensor(loss_val, dtype=torch.float32)}
+    for name, p in model.named_parameters():
+        arrays["param." + name] = p.detach()
+        if p.grad is not None:
+            arrays["grad." + name] = p.grad.detach()
+    keep = min(1.0, DUMP_LIMIT_BYTES / sum(4 * a.numel() for a in arrays.values()))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.float().cpu().numpy()
+        if keep < 1.0:
+            n = int(a.size * keep)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     global SHAPE, MODEL, BATCH
     ap = argparse.ArgumentParser()
@@ -488,7 +513,12 @@ def main():
                     help="nccl = RCCL over xGMI (the product path).  gloo + ranks sharing one GPU is "
                          "a control-flow smoke test of the multi-rank path on a 1-GPU box; its "
                          "numbers are not a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (loss, updated parameters, gradients) as "
+                         "DIR/<name>.npy, float32, at most 64 MB (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     SHAPE, MODEL, BATCH = args.shape, args.model, args.batch
     if args.one_stream:
         mpnn.WGRAD_SIDE_STREAM = False
@@ -540,6 +570,8 @@ def main():
         spread = float(both[0] + both[1])                      # max - min over ranks
         if not spread <= 1e-9 * max(abs(float(chk)), 1.0):
             raise SystemExit(f"ranks diverged: parameter checksum spread {spread}")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss_val, model)        # before any later leg steps the model again
 
     result = {
         "metric": "training graphs/sec (GGNN, GDB-13 max_n_nodes=13)" if headline else

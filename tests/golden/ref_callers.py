@@ -4,8 +4,10 @@ here (rdkit, h5py, tensorboard, matplotlib-using ``util``, ``Analyzer``, ``DataP
 ``ScoringFunction``, ``MolecularGraph``, ``parameters.constants``; none of them is touched by the methods under test:
 ``get_dataloader``, ``define_model_and_optimizer``, ``create_model``, ``train_epoch``, ``validation_epoch``, ``loss``,
 ``build_graphs`` and what it calls).  ``which`` decides which ``gnn`` / ``BlockDatasetLoader`` the unmodified callers
-bind: "reference" (``/root/reference/graphinvent`` first on ``sys.path``: golden generation on CPU) or "dropin"
-(``graphinvent_amd/`` first: the MI355X modules under the reference's names)."""
+bind: "reference" (``/root/reference/graphinvent`` first on ``sys.path``: golden generation on CPU), "dropin"
+(``graphinvent_amd/`` first: the MI355X modules under the reference's names) or "cpu" (``cpu_model_modules``: a CPU
+model and the drop-in loader, both from this repository; what tests/golden/golden_callers_cpu.npz was made with).
+``cpu_model_modules`` alone needs no reference checkout."""
 import os
 import sys
 import types
@@ -63,9 +65,29 @@ class _H5File:
         return self._d[name]
 
 
+def cpu_model_modules():
+    """Register ``gnn.mpnn`` / ``BlockDatasetLoader`` as the callers import them, for a run on CPU that needs nothing
+    outside this repository: the drop-in loader, and a ``GGNN`` built by the drop-in's constructor (seed for seed the
+    reference's: tests/test_boundary_cpu.py) whose forward is the fp32 oracle (the drop-in has no CPU forward)."""
+    from graphinvent_amd import BlockDatasetLoader
+    from graphinvent_amd.gnn import mpnn
+    from oracle import ggnn_oracle as O
+
+    class GGNN(mpnn.GGNN):
+        def forward(self, nodes, edges):
+            cfg = {k: getattr(self.constants, k) for k in O.GDB13_DEFAULTS}
+            return O.ggnn_forward(dict(self.named_parameters()), cfg, nodes.float(), edges.float())
+
+    for name in list(sys.modules):
+        if name in ("BlockDatasetLoader", "gnn") or name.startswith("gnn."):
+            del sys.modules[name]
+    _stub("gnn").mpnn = _stub("gnn.mpnn", GGNN=GGNN)
+    sys.modules["BlockDatasetLoader"] = BlockDatasetLoader
+
+
 def load(which: str, constants):
     """-> (Workflow module, GraphGenerator module), freshly imported with `constants` as ``parameters.constants``."""
-    assert which in ("reference", "dropin") and have_reference()
+    assert which in ("reference", "dropin", "cpu") and have_reference()
     for name in list(sys.modules):
         if name in ("Workflow", "GraphGenerator", "BlockDatasetLoader", "gnn") or name.startswith("gnn."):
             del sys.modules[name]
@@ -87,6 +109,8 @@ def load(which: str, constants):
             import torch.utils.tensorboard  # noqa: F401
         except Exception:
             torch.utils.tensorboard = _stub("torch.utils.tensorboard", SummaryWriter=object)
+    if which == "cpu":
+        cpu_model_modules()
     first = REF if which == "reference" else os.path.join(ROOT, "graphinvent_amd")
     path0 = list(sys.path)
     sys.path[:] = [first, REF] + [p for p in path0 if p not in (first, REF)]
@@ -98,8 +122,11 @@ def load(which: str, constants):
     finally:
         sys.path[:] = path0
     assert Workflow.__file__.startswith(REF) and GraphGenerator.__file__.startswith(REF)
-    assert gnn.mpnn.__file__.startswith(first) and BlockDatasetLoader.__file__.startswith(first), \
-        (gnn.mpnn.__file__, BlockDatasetLoader.__file__)
+    if which == "cpu":
+        assert gnn.mpnn.__name__ == "gnn.mpnn" and BlockDatasetLoader.__file__.startswith(first)
+    else:
+        assert gnn.mpnn.__file__.startswith(first) and BlockDatasetLoader.__file__.startswith(first), \
+            (gnn.mpnn.__file__, BlockDatasetLoader.__file__)
     return Workflow, GraphGenerator
 
 

@@ -9,6 +9,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -72,30 +73,47 @@ def test_bench_two_ranks_gloo_sharing_the_gpu():
     assert "smoke test" in d["config"]["backend"]
 
 
+# Every rank is a process with a GPU open, and one device should not serve more than four of them at once (the same cap
+# as tools/scale.sh's gloo mode): the eight-rank scenarios run eight ranks where there are at least two devices and the
+# largest world that fits, four ranks, on one (bench.py maps LOCAL_RANK modulo the device count).
+RANKS_PER_DEVICE = 4
+
+
+def _gloo_world(want: int) -> int:
+    return min(want, RANKS_PER_DEVICE * torch.cuda.device_count())
+
+
 def test_bench_eight_ranks_gloo_sharing_the_gpu():
-    """The world size the driver's scaling run ends at (`bench.py --gpus 8`), on ONE device over gloo with a small
-    per-rank batch: eight ranks through the rendezvous, the weight broadcast, the overlapped two-call backward with
-    the early exchange of the readout tail, FusedAdam on every rank and the cross-rank weight checksum (a diverged
-    checksum aborts the run) — so that the first real 8-GPU execution (backend nccl = RCCL, one rank per device) only
-    swaps the transport.  Not a measurement."""
-    d = _run_bench(8, "gloo", extra=("--batch", "96"))
-    _check(d, 8, "gloo", batch=96)
-    assert sorted(d["allreduce"]["ranks"]) == sorted(set(d["allreduce"]["ranks"])) or len(d["allreduce"]["ranks"]) == 8
+    """The world size the driver's scaling run ends at (`bench.py --gpus 8`) over gloo with a small per-rank batch, or
+    the largest world the visible devices hold (_gloo_world): the ranks through the rendezvous, the weight broadcast,
+    the overlapped two-call backward with the early exchange of the readout tail, FusedAdam on every rank and the
+    cross-rank weight checksum (a diverged checksum aborts the run) — so that the first real 8-GPU execution (backend
+    nccl = RCCL, one rank per device) only swaps the transport.  Not a measurement."""
+    world = _gloo_world(8)
+    assert world >= 4
+    d = _run_bench(world, "gloo", extra=("--batch", "96"))
+    _check(d, world, "gloo", batch=96)
+    assert sorted(d["allreduce"]["ranks"]) == sorted(set(d["allreduce"]["ranks"])) or len(d["allreduce"]["ranks"]) == world
 
 
 def test_scale_script_dry_run_over_gloo(tmp_path):
-    """tools/scale.sh — what produces the N = 1, 2, 4, 8 lines on the first multi-GPU box — run end to end on ONE device
-    with the ranks sharing it over gloo (SCALE_BACKEND=gloo, small batch, 3 steps): four JSON lines that parse, the
-    rank counts right, `allreduce.exposed_ms_*` present for N > 1, and the summary lines the script prints.  A dry run
-    of the script's control flow, not a measurement: scaling on RCCL / xGMI is UNMEASURED (README)."""
+    """tools/scale.sh — what produces the N = 1, 2, 4, 8 lines on the first multi-GPU box — run end to end with the ranks
+    sharing the visible device(s) over gloo (SCALE_BACKEND=gloo, small batch, 3 steps): a JSON line that parses for every
+    N the devices hold (at most four ranks per device: N = 1, 2, 4 on one GPU, and the script says N = 8 was skipped),
+    the rank counts right, `allreduce.exposed_ms_*` present for N > 1, and the summary lines the script prints.  A dry
+    run of the script's control flow, not a measurement: scaling on RCCL / xGMI is UNMEASURED (README, DESIGN.md
+    section 7)."""
     out = tmp_path / "scale"
     env = dict(os.environ, SCALE_BACKEND="gloo", SCALE_PORT=str(_free_port() - 8), HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(["bash", os.path.join(ROOT, "tools", "scale.sh"), str(out), "--batch", "96", "--steps", "3",
                         "--warmup", "1"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
     summary = [ln for ln in r.stdout.splitlines() if ln.startswith("N=")]
-    assert len(summary) == 4 and all("graphs/s" in ln for ln in summary), r.stdout[-2000:]
-    for n in (1, 2, 4, 8):
+    ran = [n for n in (1, 2, 4, 8) if n == _gloo_world(n)]
+    assert ran[:3] == [1, 2, 4] and len(summary) == 4, r.stdout[-2000:]
+    for n, ln in zip((1, 2, 4, 8), summary):
+        assert ("graphs/s" in ln) if n in ran else ln.startswith(f"N={n} skipped"), ln
+    for n in ran:
         d = json.loads(open(out / f"scale_{n}.json").read())
         assert d["n_gpus"] == n and d["config"]["global_batch"] == 96 * n and d["value"] > 0
         if n > 1:
@@ -103,6 +121,28 @@ def test_scale_script_dry_run_over_gloo(tmp_path):
             assert ar["ranks_seen"] == n and ar["backend"] == "gloo"
             assert all(isinstance(ar[k], float) for k in ("exposed_ms_overlapped", "exposed_ms_after_backward"))
             assert "exchange exposed" in summary[(1, 2, 4, 8).index(n)]
+
+
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR`: what the last of exactly --steps timed steps computed — its loss, every updated
+    parameter and its gradient — as float32 .npy files within 64 MB; the loss is the one the JSON line reports."""
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-extra-configs",
+           "--no-one-stream", "--no-cpu-baseline", "--no-probe", "--no-forward-only", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    files = sorted(os.listdir(out))
+    assert sum(os.path.getsize(out / f) for f in files) <= 64 * 10 ** 6
+    arrays = {f[:-len(".npy")]: np.load(out / f) for f in files}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert abs(float(arrays["loss"]) - d["config"]["loss"]) <= 1e-5
+    params = sorted(k[len("param."):] for k in arrays if k.startswith("param."))
+    assert len(params) == 104 and params == sorted(k[len("grad."):] for k in arrays if k.startswith("grad."))
+    assert len(arrays) == 1 + 2 * len(params)
 
 
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs >= 2 GPUs (RCCL, one rank per device)")

@@ -1,13 +1,15 @@
-"""CPU: the callers of the hot path (Workflow.py, GraphGenerator.py).  Needs the reference checkout for the parts that
-run its UNMODIFIED code (skipped where it is absent, e.g. on the GPU box):
+"""CPU: the callers of the hot path (Workflow.py, GraphGenerator.py), with nothing outside this repository:
 
 * oracle/callers_oracle.py reproduces the unmodified ``Workflow`` training path and ``GraphGenerator.build_graphs`` bit
-  for bit (the same check tests/golden/make_golden_callers.py makes before it writes the golden files);
-* the unmodified ``Workflow``, bound to the DROP-IN ``gnn`` / ``BlockDatasetLoader`` modules (graphinvent_amd/ first on
-  sys.path), constructs the model, the loader, the optimizer and the scheduler and computes its loss on the drop-in
-  loader's int8 batches — everything up to the forward itself, which has no CPU fallback and says so."""
+  for bit: tests/golden/golden_callers_cpu.npz holds what the UNMODIFIED methods computed on the same CPU model and
+  loader (tests/golden/make_golden_cpu.py; ``ref_callers.cpu_model_modules``), and the restatement must equal it;
+* a caller that imports ``gnn.mpnn`` / ``BlockDatasetLoader`` the way Workflow.py does, with graphinvent_amd/ first on
+  sys.path, binds the DROP-IN modules: it constructs the model, the loader, the optimizer and the scheduler and computes
+  its loss on the drop-in loader's int8 batches — everything up to the forward itself, which has no CPU fallback and
+  says so."""
 import os
 import shutil
+import sys
 
 import numpy as np
 import pytest
@@ -16,27 +18,29 @@ import torch
 from oracle import callers_oracle as CO
 from oracle import ggnn_oracle as O
 from tests.golden import ref_callers as RC
+from tests.h5util import have_libhdf5
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(autouse=True)
 def _restore_process_state():
-    """ref_callers.load / pin_multinomial replace modules and torch.distributions.Multinomial process-wide."""
+    """ref_callers.cpu_model_modules / pin_multinomial replace modules and torch.distributions.Multinomial
+    process-wide."""
     with RC.isolated():
         yield
 
 
-FIXTURE = "/root/reference/data/pre-training/gdb13_1K-debug/valid.h5"
-needs_ref = pytest.mark.skipif(not (RC.have_reference() and os.path.exists(FIXTURE)
-                                    and os.path.exists("/opt/conda/lib/libhdf5.so")),
-                               reason="reference checkout / libhdf5 not on this box")
 SMALL = dict(hidden_node_features=24, message_size=24, enn_hidden_dim=32, gather_width=24, gather_att_hidden_dim=32,
              gather_emb_hidden_dim=32, mlp1_hidden_dim=48, mlp2_hidden_dim=48)
 
 
 @pytest.fixture
-def data_dir(tmp_path):
-    for name in ("train", "valid", "test"):
-        shutil.copy(FIXTURE, str(tmp_path / f"{name}.h5"))
+def data_dir(tmp_path, golden_dir):
+    if not have_libhdf5():
+        pytest.skip("no libhdf5 on this box")
+    for name in ("train", "valid", "test"):                       # the shipped valid.h5 under all three names
+        shutil.copy(os.path.join(golden_dir, "gdb13_1K-debug_valid.h5"), str(tmp_path / f"{name}.h5"))
     return str(tmp_path)
 
 
@@ -53,33 +57,38 @@ def _train(make, consts, steps):
     return out, wf
 
 
-@needs_ref
-def test_restated_callers_equal_the_unmodified_reference_bit_for_bit(data_dir):
+def test_restated_callers_equal_the_unmodified_reference_bit_for_bit(data_dir, golden_dir):
+    G = np.load(os.path.join(golden_dir, "golden_callers_cpu.npz"))
     consts = RC.as_constants(dict(RC.constants_dict("cpu", O.make_config(**SMALL), data_dir, batch_size=100, epochs=3),
                                   init_lr=1e-3))
-    WF, GG = RC.load("reference", consts)
-    ref, wf_ref = _train(lambda c: WF.Workflow(constants=c), consts, 3)
-    mine, wf_mine = _train(lambda c: CO.WorkflowOracle(c), consts, 3)
-    assert ref == mine
-    assert all(torch.equal(a, b) for a, b in zip(wf_ref.model.state_dict().values(), wf_mine.model.state_dict().values()))
-    outs = []
-    for make in (lambda m, b, draw: GG.GraphGenerator(model=m, batch_size=b),
-                 lambda m, b, draw: CO.GeneratorOracle(m, b, consts, draw)):
+    RC.cpu_model_modules()
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)                                        # as the golden run: one summation order
+    try:
+        mine, wf = _train(lambda c: CO.WorkflowOracle(c), consts, 3)
         draw = CO.InverseCdfDraws(0, 24)
         RC.pin_multinomial(draw)
         with torch.no_grad():
-            gen = make(wf_ref.model.eval(), 24, draw)
+            gen = CO.GeneratorOracle(wf.model.eval(), 24, consts, draw)
             n = gen.build_graphs()
-        outs.append((n, draw.round, gen.generated_nodes.clone(), gen.generated_edges.clone(), gen.generated_n_nodes.clone(),
-                     gen.generated_likelihoods.clone(), gen.properly_terminated.clone()))
-    assert outs[0][:2] == outs[1][:2] and all(torch.equal(a, b) for a, b in zip(outs[0][2:], outs[1][2:]))
+    finally:
+        torch.set_num_threads(threads)
+    assert mine == [tuple(x) for x in G["losses"].tolist()]
+    sd = wf.model.state_dict()
+    assert sorted("final::" + k for k in sd) == sorted(k for k in G.files if k.startswith("final::"))
+    assert all(np.array_equal(v.numpy(), G["final::" + k]) for k, v in sd.items())
+    assert (n, draw.round) == (int(G["n_generated"]), int(G["rounds"])) and n > 0
+    for name, t in (("nodes", gen.generated_nodes), ("edges", gen.generated_edges), ("n_nodes", gen.generated_n_nodes),
+                    ("likelihoods", gen.generated_likelihoods), ("terminated", gen.properly_terminated)):
+        assert np.array_equal(t.numpy(), G[name]), name
 
 
-@needs_ref
-def test_unmodified_workflow_binds_the_dropin_modules(data_dir):
+def test_workflow_binds_the_dropin_modules(data_dir):
     consts = RC.as_constants(RC.constants_dict("cpu", O.make_config(**SMALL), data_dir, batch_size=32, epochs=2))
-    WF, _ = RC.load("dropin", consts)
-    wf = WF.Workflow(constants=consts)
+    for name in [k for k in sys.modules if k in ("BlockDatasetLoader", "gnn") or k.startswith("gnn.")]:
+        del sys.modules[name]
+    sys.path.insert(0, os.path.join(ROOT, "graphinvent_amd"))     # graphinvent_amd/ ahead, as a deployment puts it
+    wf = CO.WorkflowOracle(consts)                                 # imports them as Workflow.py:19, 23 do
     wf.train_dataloader = wf.get_dataloader(wf.train_h5_path, "training set")
     assert type(wf.train_dataloader).__module__ == "BlockDatasetLoader"
     assert "graphinvent_amd" in __import__("BlockDatasetLoader").__file__

@@ -419,8 +419,15 @@ def test_every_gemm_route_publishes_c_amax(route, layout, bf3_kernel_switches):
             ops.gemm(X, ops.bf3_pack(Wt, transpose=True, as_f32=True), Y, M, N, K, ops.r4(K), ops.r4(K), ops.r4(N),
                      flags=L.EPI_DSELU | bf3 | L.GEMM_BF3B_F32, act=act, ldact=ops.r4(N), c_amax=cell[0])
         else:
-            if bf3 and route != "bf3_b3p" and route != "bf3_b3v":
-                pytest.skip("W as stored on the 16-bit pipe: the 32-deep-tile kernels only")
+            if bf3 and route == "bf3_r3":
+                # W as stored on the 16-bit pipe is a layout of the 32-deep-tile kernels only: with both switched
+                # off the launch is refused before anything runs, and neither C nor the cell is written
+                with pytest.raises(RuntimeError, match="GI_EINVAL"):
+                    ops.gemm(X, Wt, Y, M, N, K, ops.r4(K), N, ops.r4(N), flags=L.EPI_DSELU | bf3, act=act,
+                             ldact=ops.r4(N), b_major=True, c_amax=cell[0])
+                torch.cuda.synchronize()
+                assert float(Y.abs().max()) == 0 and float(cell.abs().max()) == 0
+                return
             ops.gemm(X, Wt, Y, M, N, K, ops.r4(K), N, ops.r4(N), flags=L.EPI_DSELU | bf3, act=act, ldact=ops.r4(N),
                      b_major=True, c_amax=cell[0])
     assert float(Y[:, :N].abs().max()) > 0

@@ -6,8 +6,11 @@ import pytest
 import torch
 
 from graphinvent_amd.loader import ArraySource, BlockStreamLoader, HDFSource, LazyRows, read_hdf_int8
+from tests.h5util import have_libhdf5
 
-REF_H5 = "/root/reference/data/pre-training/gdb13_1K-debug/train.h5"
+# the reference's shipped preprocessed file (data/pre-training/gdb13_1K-debug/train.h5), stored byte for byte
+REF_H5 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gdb13_1K-debug_train.h5")
+needs_libhdf5 = pytest.mark.skipif(not have_libhdf5(), reason="no libhdf5 on this box")
 
 
 def _fixture(golden_dir, split="train"):
@@ -48,8 +51,7 @@ def test_rejects_non_int8():
         ArraySource(np.zeros((4, 2, 2), np.float32), np.zeros((4, 2, 2, 1), np.int8), np.zeros((4, 3), np.int8))
 
 
-@pytest.mark.skipif(not (os.path.exists(REF_H5) and os.path.exists("/opt/conda/lib/libhdf5.so")),
-                    reason="reference HDF fixture / libhdf5 not on this box")
+@needs_libhdf5
 def test_hdf_reader_matches_committed_fixture(golden_dir):
     n, e, a = read_hdf_int8(REF_H5)
     fn, fe, fa = _fixture(golden_dir)
@@ -93,8 +95,7 @@ def test_dropin_blockdatasetloader_module_api(golden_dir):
     assert not all(torch.equal(p, q) for p, q in zip(first, second))
 
 
-@pytest.mark.skipif(not (os.path.exists(REF_H5) and os.path.exists("/opt/conda/lib/libhdf5.so")),
-                    reason="reference HDF fixture / libhdf5 not on this box")
+@needs_libhdf5
 def test_dropin_hdfdataset_reads_the_reference_file(golden_dir):
     from graphinvent_amd.BlockDatasetLoader import HDFDataset
     ds = HDFDataset(REF_H5)
@@ -150,7 +151,7 @@ def test_one_lock_per_libhdf5_handle_and_abandoned_reader_is_joined():
     background reader an abandoned one left running before it reuses the slice buffers."""
     import threading, time
     from graphinvent_amd import loader as L
-    if os.path.exists("/opt/conda/lib/libhdf5.so") and os.path.exists(REF_H5):
+    if have_libhdf5():
         s1, s2 = HDFSource(REF_H5), HDFSource(REF_H5.replace("train.h5", "valid.h5"))
         assert s1._lock is s2._lock
         s1.close(); s2.close()
@@ -247,8 +248,7 @@ def test_block_stream_pinned_memory_is_two_slices_whatever_the_file_size():
     assert ld8.pinned_bytes == 2 * 1250 * row_bytes and len(ld8) == 2000
 
 
-@pytest.mark.skipif(not (os.path.exists(REF_H5) and os.path.exists("/opt/conda/lib/libhdf5.so")),
-                    reason="reference HDF fixture / libhdf5 not on this box")
+@needs_libhdf5
 def test_hdf_source_reads_row_ranges(golden_dir):
     fn, fe, fa = _fixture(golden_dir)
     src = HDFSource(REF_H5)
