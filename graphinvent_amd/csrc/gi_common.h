@@ -50,6 +50,9 @@ int gi_seg_sum_n(const float* vals, int ldv, const int* perm, const int* off, in
                  int ldo, int accumulate, const int* rows_dev, void* stream);
 int gi_seg_softmax_fwd_n(const float* en, const float* emb, int ld, const int* perm, const int* off, int rows,
                          int cols, float* out, int ldo, const int* rows_dev, void* stream);
+int gi_typed_seg_sum_n(const float* h, int ldh, const int* u_src, const int* in_perm, const int* seg_off,
+                       const int* type_off, int rows, int H, int Fe, float* out, int ldo, const int* rows_dev,
+                       void* stream);
 int gi_gru_gates_fwd_n(float* gi, float* gh, int ldg, const float* hx_prev, float* hx_new, int ldh,
                        const int* seg_off, int rows, int H, int Fn, const int* rows_dev, void* stream);
 

@@ -42,6 +42,10 @@ struct Model {
     gi_ggnn_dims d;
     Mlp msg[GI_MAX_GROUPS], eatt[GI_MAX_GROUPS], att, emb, add1, conn1, add2, conn2, term2;
     int gru_wih, gru_whh, gru_bih, gru_bhh, nparams, NA, NC;
+    // GI_KIND_MNN: one [M, H, Fe] message weight (index mw) instead of the message stacks, and no gather stacks
+    bool mnn = false;
+    int mw = -1;
+    bool gather() const { return !mnn; }
 };
 
 int build_model(const gi_ggnn_dims* dp, Model& m) {
@@ -51,8 +55,13 @@ int build_model(const gi_ggnn_dims* dp, Model& m) {
         d.A <= 0 || d.C <= 0 || d.passes < 0 || d.Fn > d.H)
         return GI_EINVAL;
     if (d.N > GI_MAX_NODES || d.Fe > GI_MAX_GROUPS || d.passes > MAXP) return GI_ELIMIT;
-    if (d.kind != GI_KIND_GGNN && d.kind != GI_KIND_ATTGGNN) return GI_EINVAL;
+    if (d.kind != GI_KIND_GGNN && d.kind != GI_KIND_ATTGGNN && d.kind != GI_KIND_MNN) return GI_EINVAL;
     const bool attn = d.kind == GI_KIND_ATTGGNN;
+    m = Model{};
+    if (d.kind == GI_KIND_MNN &&
+        (d.G != d.H || d.enn_depth || d.att_depth || d.emb_depth || d.eatt_depth || d.drop_enn > 0.f ||
+         d.drop_eatt > 0.f || d.drop_att > 0.f || d.drop_emb > 0.f))
+        return GI_EINVAL;
     if (attn && d.eatt_hidden <= 0 && d.eatt_depth > 0) return GI_EINVAL;
     const int depths[] = {d.enn_depth, d.att_depth, d.emb_depth, d.mlp1_depth, d.mlp2_depth,
                           attn ? d.eatt_depth : 0};
@@ -70,6 +79,18 @@ int build_model(const gi_ggnn_dims* dp, Model& m) {
         idx += 2 * (depth + 1);
         return r;
     };
+    if (d.kind == GI_KIND_MNN) {   // MNN: message_weights, gru, APDReadout (gnn/mpnn.py:21-53)
+        m.mnn = true;
+        m.mw = idx++;
+        m.gru_wih = idx++; m.gru_whh = idx++; m.gru_bih = idx++; m.gru_bhh = idx++;
+        m.add1 = mk(d.H, d.mlp1_hidden, d.mlp1_depth, d.A, d.drop_mlp1);
+        m.conn1 = mk(d.H, d.mlp1_hidden, d.mlp1_depth, d.C, d.drop_mlp1);
+        m.add2 = mk(m.NA + d.G, d.mlp2_hidden, d.mlp2_depth, m.NA, d.drop_mlp2);
+        m.conn2 = mk(m.NC + d.G, d.mlp2_hidden, d.mlp2_depth, m.NC, d.drop_mlp2);
+        m.term2 = mk(d.G, d.mlp2_hidden, d.mlp2_depth, 1, d.drop_mlp2);
+        m.nparams = idx;
+        return 0;
+    }
     for (int t = 0; t < d.Fe; ++t) m.msg[t] = mk(d.H, d.enn_hidden, d.enn_depth, d.M, d.drop_enn);
     if (attn)   // AttentionGGNN registers msg_nns before att_nns (gnn/mpnn.py:316-317)
         for (int t = 0; t < d.Fe; ++t)
@@ -122,6 +143,10 @@ struct Ws {
     long long skinny, skinny_floats;
     long long bf3, bf3_floats;          // bf16x3 operand images of the node-level stacks' wide layers (gi_gemm_bf3.hip)
     long long amax;                     // fp16x2 launches: max |.| of their operand tensors, 3 (of 4) amax cells per layer (gi_x2.h)
+    // MNN: typed sums S_p [R, ldS] of every pass (contiguous: the weight gradient is one GEMM over all passes, as are
+    // the dagg[p]), the backward's dS [R, ldS], and the split-K slabs of dW [M, H Fe]
+    int ldS, mslab_split;
+    long long ssum[MAXP], dS, mslab, mslab_stride;
     long long total;
 };
 
@@ -189,7 +214,7 @@ void make_ws(const Model& m, int S, int E, int U, int D0, Ws& w) {
     const gi_ggnn_dims& d = m.d;
     memset(&w, 0, sizeof(w));
     w.R = S + 1; w.E = E; w.U = U; w.B = d.B;
-    w.D0 = d.passes > 0 ? D0 : 0;       // pass-0 class rows (both models)
+    w.D0 = (d.passes > 0 && !m.mnn) ? D0 : 0;       // pass-0 class rows (GGNN, AttentionGGNN)
     w.ldhx = gi_r4(d.H + d.Fn); w.ldH = gi_r4(d.H); w.ldM = gi_r4(d.M); w.ld3H = gi_r4(3 * d.H);
     w.ldG = gi_r4(d.G); w.ldA = gi_r4(d.A); w.ldC = gi_r4(d.C); w.ldEh = gi_r4(d.enn_hidden);
     w.ldAtt = gi_r4(d.att_hidden); w.ldEmb = gi_r4(d.emb_hidden); w.ldM1 = gi_r4(d.mlp1_hidden);
@@ -277,6 +302,7 @@ void make_ws(const Model& m, int S, int E, int U, int D0, Ws& w) {
         const Mlp* t1[4] = {&m.att, &m.emb, &m.add1, &m.conn1};
         long long elems = 0;
         for (const Mlp* q : t1)
+            if (m.gather() || (q != &m.att && q != &m.emb))
             for (int l = 0; l < q->layers(); ++l)
                 if (bf3_wide(*q, l))          // (sized whether or not the switch is on)
                     elems += std::max(gi_bf3_image_elems(q->fan_out(l), q->fan_in(l)),
@@ -285,7 +311,7 @@ void make_ws(const Model& m, int S, int E, int U, int D0, Ws& w) {
         w.bf3 = take(std::max(w.bf3_floats, 4LL), 1);
         w.amax = take(4LL * GI_AMAX_WORDS * GI_BF3_PACK_MAX, 1);
     }
-    for (int k = 0; k < (attn ? 2 : 1); ++k) {
+    for (int k = 0; k < (m.mnn ? 0 : attn ? 2 : 1); ++k) {
         const Mlp& q = k ? m.eatt[0] : m.msg[0];
         if (d.passes > 0 && !d.dropout && chain_fits(q, d.H)) {   // (dropout: layer by layer)
             w.img_f_n[k] = chain_image_floats(q, d.Fe, false, nullptr);
@@ -299,6 +325,17 @@ void make_ws(const Model& m, int S, int E, int U, int D0, Ws& w) {
         }
     }
     w.amax_pool = take((long long)AMAX_POOL_CELLS * GI_AMAX_WORDS, 1);
+    if (m.mnn) {
+        w.ldS = gi_r4(d.H * d.Fe);
+        for (int p = 0; p < d.passes; ++p) w.ssum[p] = take(R, w.ldS);
+        w.dS = take(R, w.ldS);
+        // dW = sum over passes and rows of dagg^T S: ~256 workgroups of 64 x 64 tiles over passes * R reduction rows
+        const int tiles = gi_cdiv(d.M, 64) * gi_cdiv(d.H * d.Fe, 64);
+        const int kt = gi_cdiv((int)std::min(R * std::max(d.passes, 1), (long long)1 << 30), 32);
+        w.mslab_split = std::min(std::max(256 / tiles, 1), std::max(1, kt / 2));
+        w.mslab_stride = gi_r4l((long long)d.M * w.ldS);
+        w.mslab = take((long long)w.mslab_split * w.mslab_stride, 1);
+    }
     w.fshift = d.dropout ? gi_r4l(o) : 0;
     w.total = d.dropout ? 2 * gi_r4l(o) : o;
 }
@@ -314,7 +351,7 @@ void wcache_layout(const Model& m, Wc& c) {
     auto take = [&](long long n) { long long r = o; o += gi_r4l(n); return r; };
     for (int k = 0; k < (d.kind == GI_KIND_ATTGGNN ? 2 : 1); ++k) {
         const Mlp& q = k ? m.eatt[0] : m.msg[0];
-        if (d.passes > 0 && chain_fits(q, d.H)) {
+        if (d.passes > 0 && !m.mnn && chain_fits(q, d.H)) {
             c.img_fx[k] = take(chain_image_floats(q, d.Fe, false, nullptr));
             c.chain_amax_f[k] = take((long long)GI_AMAX_WORDS * GI_CHAIN_MAXL * GI_MAX_GROUPS);
         } else {
@@ -393,7 +430,7 @@ bool wgrad_x2_pool_possible(const Model& m, bool call_x2) {
 bool wgrad_x2_all_possible(const Model& m, bool call_x2) { return wgrad_x2_all_enabled() && wgrad_x2_pool_possible(m, call_x2); }
 bool msg_wgrad_x2_possible(const Model& m, bool call_x2) {
     static const int v = getenv("GI_MSG_WGRAD_X2") ? atoi(getenv("GI_MSG_WGRAD_X2")) : 1;
-    return v != 0 && !m.d.dropout && m.d.passes > 0 && chain_fwd_x2_enabled(call_x2) && gi_b3p_enable(-1) &&
+    return v != 0 && !m.mnn && !m.d.dropout && m.d.passes > 0 && chain_fwd_x2_enabled(call_x2) && gi_b3p_enable(-1) &&
            chain_fits(m.msg[0], m.d.H) && (m.d.kind != GI_KIND_ATTGGNN || chain_fits(m.eatt[0], m.d.H));
 }
 
@@ -468,7 +505,7 @@ void plan_slabs(const Model& m, int S, int E, const int* Et, SlabPlan& sp) {   /
                 stack && l > 0 && msg_cells);
     };
     const int R = S + 1;
-    for (int t = 0; t < d.Fe; ++t) {
+    for (int t = 0; t < (m.mnn ? 0 : d.Fe); ++t) {   // (MNN: its message weight's gradient has slabs of its own, Ws.mslab)
         const int et = Et ? Et[t] : E / d.Fe;
         static const int force_msg = getenv("GI_B3W_MSG") ? atoi(getenv("GI_B3W_MSG")) : -1;   // (measurement aid)
         const bool m3 = force_msg >= 0 ? force_msg != 0 : E >= BF3_WGRAD_SMALL_MIN;
@@ -478,7 +515,8 @@ void plan_slabs(const Model& m, int S, int E, const int* Et, SlabPlan& sp) {   /
     }
     add(m.gru_wih, m.gru_bih, 3 * d.H, d.M, R, d.passes, 1.0);
     add(m.gru_whh, m.gru_bhh, 3 * d.H, d.H, R, d.passes, 1.0);
-    add_mlp(m.att, R, 1, 1.0, true); add_mlp(m.emb, R, 1, 1.0, true); add_mlp(m.add1, R, 1, 1.0, true);
+    if (m.gather()) { add_mlp(m.att, R, 1, 1.0, true); add_mlp(m.emb, R, 1, 1.0, true); }
+    add_mlp(m.add1, R, 1, 1.0, true);
     add_mlp(m.conn1, R, 1, 1.0, true);
     static const int force_g = getenv("GI_B3W_G") ? atoi(getenv("GI_B3W_G")) : -1;             // (measurement aid)
     const bool g3 = force_g >= 0 ? force_g != 0 : d.B >= BF3_WGRAD_SMALL_MIN / 4;
@@ -1531,7 +1569,7 @@ void bf3_prepare(Run& r, const Model& m, float* ws, const Ws& w, bool backward, 
     long long used = 0;
     int n = 0;
     for (const Mlp* q : t1)
-        for (int l = 0; l < q->layers() && n < GI_BF3_PACK_MAX; ++l) {
+        for (int l = 0; l < q->layers() && n < GI_BF3_PACK_MAX && (m.gather() || (q != &m.att && q != &m.emb)); ++l) {
             if (!bf3_layer_ok(*q, l)) continue;
             const int fi = q->fan_in(l), fo = q->fan_out(l);
             d[n].W = r.P[q->w(l)]; d[n].ld = fi; d[n].transpose = backward ? 1 : 0;
@@ -1668,9 +1706,13 @@ extern "C" int gi_ggnn_ws_query(const gi_ggnn_dims* d, int S, int E, int U, int 
         {"dcat_conn", w.dcat_conn, w.ldCC}, {"dgemb", w.dgemb, w.ldG}, {"dh", w.dh, w.ldH},
         {"dh2", w.dh2, w.ldH}, {"dxe", w.dxe, w.ldH},
         {"aact", w.aact[i < MAXP ? i : 0][j], w.ldEa}, {"een", w.een[i < MAXP ? i : 0], w.ldM},
+        {"ssum", m.mnn && i < d->passes ? w.ssum[i] : -1, w.ldS},
     };
     for (const Item& it : items)
-        if (!strcmp(it.n, name)) { *off = it.o; *ld = it.l; return 0; }
+        if (!strcmp(it.n, name)) {
+            if (it.o < 0) return GI_EINVAL;
+            *off = it.o; *ld = it.l; return 0;
+        }
     return GI_EINVAL;
 }
 
@@ -1680,6 +1722,315 @@ static int dropout_graph_ok(const gi_ggnn_dims& d, int S, int E, int U, int D0) 
     if (!d.dropout) return 0;
     if (S != d.B * d.N || U != E || D0 != 0) return GI_EINVAL;
     return 0;
+}
+
+// ================================ MNN (GI_KIND_MNN) ===============================================
+// `MNN.forward` = SummationMPNN.forward with the MNN hooks (gnn/summation_mpnn.py:80-149, gnn/mpnn.py:58-74), aggregate
+// first: per pass S_p = gi_typed_seg_sum(h_p) [R, H Fe], messages = S_p . W.view(M, H Fe)^T (one fp32-MFMA GEMM on the
+// parameter as stored), the GRU update of GGNN; readout = the node-level fAddNet1 / fConnNet1 stacks + the graph sum of
+// every slot's h (gi_graph_sum_fwd) into the three places GlobalReadout reads the graph embedding.  The readout keeps
+// GGNN's routes (bf16x3 / fp16x2 layers, dropout sites, split-K graph-level layers).
+static int mnn_forward(const Model& m, const float* const* params, const gi_graph* gp, float* ws, float* out,
+                       int ldout, hipStream_t stream, hipStream_t side_stream, int run_flags) {
+    const gi_ggnn_dims& d = m.d;
+    const int S = gp->S, E = gp->E, U = gp->U;
+    const int* gfix = gp->gfix;
+    if (!params || !gfix || !ws || !out || S < 0 || E < 0 || U < 0 || U > E || !gp->Ut) return GI_EINVAL;
+    if (E > 0 && (!gp->u_src || !gp->in_perm || U == 0)) return GI_EINVAL;
+    if (ldout < m.NA + m.NC + 1 || gp->D0 < 0 || gp->D0 > U) return GI_EINVAL;
+    gi_compact_layout_t L;
+    if (int rc = gi_compact_layout(d.B, d.N, d.Fe, &L)) return rc;
+    if (int drc = dropout_graph_ok(d, S, E, U, gp->D0)) return drc;
+    if (gp->bounded && d.dropout) return GI_EINVAL;
+    Ws w;
+    make_ws(m, S, E, U, gp->D0, w);
+    Run r{stream, params, 0};
+    r.drop = d.dropout != 0; r.seed = d.drop_seed; r.fshift = w.fshift;
+    r.skinny = ws + w.skinny; r.skinny_floats = w.skinny_floats;
+    r.x2 = x2_enabled() && !(run_flags & GI_RUN_NO_X2);
+    r.guard = gp->x2_guard; r.guard_host = gp->x2_guard_host;
+    const int R = w.R;
+    if (gp->bounded) { r.dims = gfix + L.dims; r.R_bound = R; }
+    Wc wc;
+    wcache_layout(m, wc);
+    float* const wcache = (gp->wcache && !r.drop && r.x2 && bf3_enabled()) ? gp->wcache : nullptr;
+    if (wcache && ((uintptr_t)wcache & 15)) return GI_EINVAL;
+    r.wc_valid = wcache && gp->wcache_valid != 0;
+    r.wc_bf3 = wcache ? wcache + wc.bf3_wamax : nullptr;
+    // what depends on the weights only goes to the side stream when there is one (as in gi_ggnn_forward_ex)
+    SideStream fside{side_stream, 0};
+    hipStream_t prep = r.st;
+    if (side_stream) {
+        hipEvent_t start = fside.next();
+        r.chk((int)hipEventRecord(start, r.st));
+        r.chk((int)hipStreamWaitEvent(fside.st, start, 0));
+        prep = fside.st;
+    }
+    if ((run_flags & GI_RUN_PREPACK_BWD) && !r.drop) bf3_prepare(r, m, ws, w, true, R, BF3_DO_PACK, prep);
+    bf3_prepare(r, m, ws, w, false, R, BF3_DO_AMAX, prep);
+    hipEvent_t packed = nullptr, cells_ready = nullptr;
+    if ((run_flags & GI_RUN_PREPACK_BWD) && !r.drop) packed = prepack_stamp(ws, r.x2);
+    else prepack_forget(ws);
+    if (side_stream) {
+        cells_ready = fside.next();
+        r.chk((int)hipEventRecord(cells_ready, fside.st));
+        if (packed) r.chk((int)hipEventRecord(packed, fside.st));
+    } else if (packed) {
+        r.chk((int)hipEventRecord(packed, r.st));
+    }
+    const int* seg_off = gfix + L.seg_off;
+    const int* cidx = gfix + L.cidx;
+    const int* type_off = gfix + L.type_off;
+    const int HF = d.H * d.Fe;
+    // ---- message passes ---------------------------------------------------------------------------
+    for (int p = 0; p < d.passes; ++p) {
+        const float* hx = ws + w.hx[p];
+        r.pass = p;
+        r.chk(gi_typed_seg_sum_n(hx, w.ldhx, gp->u_src, gp->in_perm, seg_off, type_off, R, d.H, d.Fe, ws + w.ssum[p],
+                                 w.ldS, r.dims, r.st));
+        if (r.ok()) {   // messages = S_p . W.view(M, H Fe)^T   (gnn/mpnn.py:58-63 + the sum of :141)
+            gi_gemm_params q;
+            gemm_defaults(q);
+            q.A = ws + w.ssum[p]; q.lda = w.ldS; q.B = params[m.mw]; q.ldb = HF;
+            q.C = ws + w.agg[p]; q.ldc = w.ldM; q.M = R; q.N = d.M; q.K = HF;
+            q.m_dev = r.dims;
+            pick_tile(R, d.M, q.tm, q.tn);
+            r.chk(gi_gemm(&q, r.st));
+        }
+        if (gi_gru_fused_ok(d.H, d.M, w.ldM, w.ldhx, w.ld3H)) {
+            r.chk(gi_gru_fused_fwd(ws + w.agg[p], w.ldM, hx, w.ldhx, params[m.gru_wih], params[m.gru_whh],
+                                   params[m.gru_bih], params[m.gru_bhh], ws + w.gi[p], ws + w.gh[p], w.ld3H,
+                                   ws + w.hx[p + 1], seg_off, R, r.dims, d.H, d.M, r.st));
+            continue;
+        }
+        {
+            Batch b;
+            add_fwd(b, r, params[m.gru_wih], params[m.gru_bih], d.M, 3 * d.H, ws + w.agg[p], w.ldM, R,
+                    ws + w.gi[p], w.ld3H, false);
+            add_fwd(b, r, params[m.gru_whh], params[m.gru_bhh], d.H, 3 * d.H, hx, w.ldhx, R,
+                    ws + w.gh[p], w.ld3H, false);
+            flush_batch(r, b, false);
+        }
+        r.chk(gi_gru_gates_fwd_n(ws + w.gi[p], ws + w.gh[p], w.ld3H, hx, ws + w.hx[p + 1], w.ldhx,
+                                 seg_off, R, d.H, d.Fn, r.dims, r.st));
+    }
+    // ---- readout (gnn/mpnn.py:69-74) ----------------------------------------------------------------
+    if (cells_ready) r.chk((int)hipStreamWaitEvent(r.st, cells_ready, 0));
+    const float* hx = ws + w.hx[d.passes];
+    {
+        MlpJob jobs[2] = {};
+        jobs[0] = {&m.add1, hx, w.ldhx, R, w.add1_act, w.ldM1, ws + w.add1o, w.ldA};
+        jobs[1] = {&m.conn1, hx, w.ldhx, R, w.conn1_act, w.ldM1, ws + w.conn1o, w.ldC};
+        mlp_jobs_forward(r, ws, jobs, 2);
+    }
+    if (r.ok())
+        r.chk(gi_graph_sum_fwd(hx, w.ldhx, cidx, d.B, d.N, d.H, ws + w.cat_add + m.NA, w.ldCA, ws + w.cat_conn + m.NC,
+                               w.ldCC, ws + w.gemb, w.ldG, r.st));
+    if (gi_fuse_flags() & GI_FUSE_SLOTS) {
+        r.chk(gi_expand_slots2(ws + w.add1o, w.ldA, d.A, ws + w.cat_add, w.ldCA, ws + w.conn1o, w.ldC, d.C,
+                               ws + w.cat_conn, w.ldCC, cidx, d.B, d.N, r.st));
+    } else {
+        r.chk(gi_expand_slots(ws + w.add1o, w.ldA, cidx, d.B, d.N, d.A, ws + w.cat_add, w.ldCA, r.st));
+        r.chk(gi_expand_slots(ws + w.conn1o, w.ldC, cidx, d.B, d.N, d.C, ws + w.cat_conn, w.ldCC, r.st));
+    }
+    {
+        MlpJob jobs[3] = {};
+        jobs[0] = {&m.add2, ws + w.cat_add, w.ldCA, d.B, w.add2_act, w.ldM2, out, ldout};
+        jobs[1] = {&m.conn2, ws + w.cat_conn, w.ldCC, d.B, w.conn2_act, w.ldM2, out + m.NA, ldout};
+        jobs[2] = {&m.term2, ws + w.gemb, w.ldG, d.B, w.term2_act, w.ldM2, out + m.NA + m.NC, ldout};
+        for (MlpJob& j : jobs) j.out_fshift = r.drop ? (long long)d.B * ldout : 0;
+        mlp_jobs_forward(r, ws, jobs, 3);
+    }
+    if (side_stream && packed) r.chk((int)hipStreamWaitEvent(r.st, packed, 0));
+    if (!r.ok()) prepack_forget(ws);
+    return r.rc;
+}
+
+// The MNN backward, in the phases of gi_ggnn_backward_phase: GI_BWD_READOUT = GlobalReadout + the graph sum (d h of the
+// last pass: dh, dhb from the two node-level stacks, dhc from the graph sum), GI_BWD_PASSES = the GRU, the message
+// GEMMs and the transposed typed sum, then dW = sum over passes of dagg_p^T S_p as ONE split-K GEMM over all passes.
+static int mnn_backward(const Model& m, const float* const* params, const gi_graph* gp, float* ws, float* slabs,
+                        const float* y_out, int ldout, const float* d_out, int lddout, float* const* grads,
+                        hipStream_t stream, hipStream_t side_stream, int phase, bool prepacked, bool no_x2) {
+    const gi_ggnn_dims& d = m.d;
+    const int S = gp->S, E = gp->E, U = gp->U;
+    const int* gfix = gp->gfix;
+    const int* Ut = gp->Ut;
+    if (!params || !gfix || !ws || !slabs || !y_out || !d_out || !grads || S < 0 || E < 0 || U < 0 || U > E || !Ut)
+        return GI_EINVAL;
+    if (E > 0 && (!gp->u_src || !gp->in_perm || !gp->mu_off || !gp->mu_dst || !gp->out_perm || U == 0))
+        return GI_EINVAL;
+    if (gp->wcache || gp->bounded || gp->D0 < 0 || gp->D0 > U) return GI_EINVAL;
+    gi_compact_layout_t L;
+    if (int rc = gi_compact_layout(d.B, d.N, d.Fe, &L)) return rc;
+    if (int drc = dropout_graph_ok(d, S, E, U, gp->D0)) return drc;
+    Ws w;
+    make_ws(m, S, E, U, gp->D0, w);
+    SlabPlan sp;
+    plan_slabs(m, S, U, Ut, sp);
+    Run r{stream, params, 0};
+    r.drop = d.dropout != 0; r.seed = d.drop_seed; r.fshift = w.fshift;
+    r.skinny = ws + w.skinny; r.skinny_floats = w.skinny_floats;
+    r.x2 = x2_enabled() && !no_x2;
+    r.guard = gp->x2_guard; r.guard_host = nullptr;
+    if (prepacked) {
+        if (hipEvent_t ev = prepack_lookup(ws, r.x2)) r.chk((int)hipStreamWaitEvent(r.st, ev, 0));
+        else prepacked = false;
+    }
+    const long long out_fshift = r.drop ? (long long)d.B * ldout : 0;
+    const int R = w.R;
+    const int* seg_off = gfix + L.seg_off;
+    const int* src_off = gfix + L.src_off;
+    const int* cidx = gfix + L.cidx;
+    const int* type_off = gfix + L.type_off;
+    const int NA = m.NA, NC = m.NC, HF = d.H * d.Fe;
+    Deferred dq;
+    SideStream side_obj{side_stream, 0};
+    r.side = side_stream ? &side_obj : nullptr;
+    r.sp = &sp; r.slabs = slabs; r.grads = grads;
+    r.wgrad_x2 = wgrad_x2_pool_possible(m, r.x2);
+    r.pool.base = r.wgrad_x2 ? ws + w.amax_pool : nullptr;
+    const Grp none{0, nullptr, 0};
+    const float* hxP = ws + w.hx[d.passes];
+    float* dh = ws + w.dh;
+    float* dh2 = ws + w.dh2;
+    float* dhb = ws + w.dhb;
+    float* dhc = ws + w.dhc;
+    auto readout_params = [&](auto&& fn) {
+        const Mlp* stacks[] = {&m.add1, &m.conn1, &m.add2, &m.conn2, &m.term2};
+        for (const Mlp* q : stacks)
+            for (int l = 0; l < q->layers(); ++l) fn(q->w(l));
+    };
+    if (phase == GI_BWD_PASSES) readout_params([&](int widx) { sp.e[widx].reduced = 1; });
+    if (phase != GI_BWD_PASSES) {
+        bf3_prepare(r, m, ws, w, true, S + 1, prepacked ? 0 : BF3_DO_PACK, r.st);
+        r.chk(gi_selu_bwd_cols3_f(d_out, lddout, y_out, ldout, out_fshift, d.B, NA, ws + w.dzA, w.ldNA, NC,
+                                  ws + w.dzC, w.ldNC, 1, ws + w.dzT, 4, r.st));
+        {
+            MlpJob jobs[3] = {};
+            jobs[0] = {&m.add2, ws + w.cat_add, w.ldCA, d.B, w.add2_act, w.ldM2, nullptr, 0, w.add2_dz,
+                       ws + w.dzA, w.ldNA, ws + w.dcat_add, w.ldCA, NA + d.G, false};
+            jobs[1] = {&m.conn2, ws + w.cat_conn, w.ldCC, d.B, w.conn2_act, w.ldM2, nullptr, 0,
+                       w.conn2_dz, ws + w.dzC, w.ldNC, ws + w.dcat_conn, w.ldCC, NC + d.G, false};
+            jobs[2] = {&m.term2, ws + w.gemb, w.ldG, d.B, w.term2_act, w.ldM2, nullptr, 0, w.term2_dz,
+                       ws + w.dzT, 4, ws + w.dgemb, w.ldG, d.G, false};
+            mlp_jobs_backward(r, ws, sp, slabs, dq, jobs, 3);
+        }
+        r.chk(gi_compress_slots2_f(ws + w.add1o, w.ldA, d.A, ws + w.dcat_add, w.ldCA, ws + w.zpart_a, w.ldA,
+                                   ws + w.conn1o, w.ldC, d.C, ws + w.dcat_conn, w.ldCC, ws + w.zpart_c,
+                                   w.ldC, cidx, d.B, d.N, S, r.fshift, r.st));
+        {   // zero-row gradients of the two node-level stacks: per-graph partial sums -> row S
+            float* add_z = ws + w.add1o + (long long)S * w.ldA;
+            float* conn_z = ws + w.conn1o + (long long)S * w.ldC;
+            const gi_colsum_desc cs[2] = {
+                {ws + w.zpart_a, w.ldA, d.B, d.A, add_z, add_z},
+                {ws + w.zpart_c, w.ldC, d.B, d.C, conn_z, conn_z}};
+            r.chk(gi_colsum_multi(cs, 2, r.st));
+        }
+        {
+            MlpJob jobs[2] = {};
+            jobs[0] = {&m.add1, hxP, w.ldhx, R, w.add1_act, w.ldM1, nullptr, 0, w.add1_dz, ws + w.add1o,
+                       w.ldA, dh, w.ldH, d.H, false};
+            jobs[1] = {&m.conn1, hxP, w.ldhx, R, w.conn1_act, w.ldM1, nullptr, 0, w.conn1_dz,
+                       ws + w.conn1o, w.ldC, dhb, w.ldH, d.H, false};
+            static const int hold_env = getenv("GI_HOLD_KICKS") ? atoi(getenv("GI_HOLD_KICKS")) : -1;
+            r.hold_kicks = hold_env >= 0 ? hold_env != 0 : R <= 9000;
+            mlp_jobs_backward(r, ws, sp, slabs, dq, jobs, 2);
+            r.hold_kicks = false;
+            if (r.side) kick_deferred(r, dq, r.side, false);
+        }
+        // graph sum: every row of graph b gets d g[b] summed over its three consumers (dhc; the zero row: 0)
+        if (r.ok())
+            r.chk(gi_graph_sum_bwd(ws + w.dgemb, w.ldG, ws + w.dcat_add + NA, w.ldCA, ws + w.dcat_conn + NC, w.ldCC,
+                                   gfix + L.slot_of, S, d.N, d.H, dhc, w.ldH, 0, r.st));
+    }
+    if (phase == GI_BWD_READOUT) {
+        hipStream_t rst = r.side ? r.side->st : r.st;
+        if (r.side) kick_deferred(r, dq, r.side, true);
+        else flush_deferred(r, dq);
+        flush_bias(r, dq, rst);
+        gi_reduce_desc descs[160];
+        int nd = 0;
+        readout_params([&](int widx) {
+            if (sp.e[widx].reduced) return;
+            sp.e[widx].reduced = 1;
+            descs[nd++] = reduce_desc(sp.e[widx], slabs, grads, widx);
+        });
+        if (nd && r.ok()) r.chk(gi_reduce_slabs(descs, nd, rst));
+        return r.rc;
+    }
+    // ---- message passes, reversed -------------------------------------------------------------------
+    for (int p = d.passes - 1; p >= 0; --p) {
+        const float* hx = ws + w.hx[p];
+        float* gi = ws + w.gi[p];
+        float* gh = ws + w.gh[p];
+        float* agg = ws + w.agg[p];
+        float* dagg = ws + w.dagg[p];
+        const bool last = (p == d.passes - 1);
+        r.chk(gi_gru_gates_bwd(gi, gh, w.ld3H, hx, w.ldhx, dh, last ? dhb : nullptr, last ? dhc : nullptr, nullptr,
+                               dh2, w.ldH, seg_off, R, d.H, r.st));
+        {
+            const int wih = m.gru_wih, whh = m.gru_whh;
+            defer_wgrad(r, dq, sp, slabs, &wih, none, gi, w.ld3H, agg, w.ldM, nullptr, R);
+            defer_wgrad(r, dq, sp, slabs, &whh, none, gh, w.ld3H, hx, w.ldhx, nullptr, R);
+            Batch bd;
+            add_dgrad(bd, r, m.gru_wih, 3 * d.H, d.M, d.M, gi, w.ld3H, R, dagg, w.ldM, nullptr, 0, false);
+            if (p > 0)
+                add_dgrad(bd, r, m.gru_whh, 3 * d.H, d.H, d.H, gh, w.ld3H, R, dh2, w.ldH, nullptr, 0, true);
+            flush_batch(r, bd, false);
+        }
+        if (p > 0 && E > 0 && r.ok()) {
+            // dS = dagg . W.view(M, H Fe), then d h_src += the transposed typed sum of dS
+            gi_gemm_params q;
+            gemm_defaults(q);
+            q.A = dagg; q.lda = w.ldM; q.B = params[m.mw]; q.ldb = HF; q.b_major = 1;
+            q.C = ws + w.dS; q.ldc = w.ldS; q.M = R; q.N = HF; q.K = d.M;
+            pick_tile(R, HF, q.tm, q.tn);
+            r.chk(gi_gemm(&q, r.st));
+            if (r.ok())
+                r.chk(gi_typed_seg_sum_t(ws + w.dS, w.ldS, gp->out_perm, src_off, gp->mu_off, gp->mu_dst, type_off, R,
+                                         d.H, d.Fe, dh2, w.ldH, 1, r.st));
+        }
+        std::swap(dh, dh2);
+    }
+    // dW.view(M, H Fe) = sum over passes of dagg_p^T S_p: the passes' buffers are contiguous -> one reduction of
+    // passes * R rows, split-K into slabs, summed in a fixed order
+    if (d.passes > 0 && r.ok()) {
+        gi_gemm_params q;
+        gemm_defaults(q);
+        q.A = ws + w.dagg[0]; q.lda = w.ldM; q.a_major = 1;
+        q.B = ws + w.ssum[0]; q.ldb = w.ldS; q.b_major = 1;
+        q.C = ws + w.mslab; q.ldc = w.ldS; q.M = d.M; q.N = HF; q.K = d.passes * R;
+        q.flags = GI_GEMM_SPLITK; q.nsplit = w.mslab_split; q.c_split_stride = w.mslab_stride;
+        q.tm = 1; q.tn = 1;
+        r.chk(gi_gemm(&q, r.st));
+        if (r.ok())
+            r.chk(gi_slab_epilogue(ws + w.mslab, w.mslab_split, w.mslab_stride, d.M, HF, w.ldS, 0, nullptr, nullptr, 0,
+                                   grads[m.mw], HF, r.st));
+    } else if (r.ok()) {
+        r.chk((int)hipMemsetAsync(grads[m.mw], 0, sizeof(float) * (size_t)d.M * HF, r.st));
+    }
+    if (r.side) {
+        kick_deferred(r, dq, r.side, true);
+        flush_bias(r, dq, r.side->st);
+        join_side(r, r.side);
+    } else {
+        flush_deferred(r, dq);
+        flush_bias(r, dq, r.st);
+    }
+    gi_reduce_desc descs[160];
+    int nd = 0;
+    auto add_desc = [&](int widx) {
+        SlabEntry& e = sp.e[widx];
+        if (e.reduced) return;
+        e.reduced = 1;
+        descs[nd++] = reduce_desc(e, slabs, grads, widx);
+    };
+    add_desc(m.gru_wih);
+    add_desc(m.gru_whh);
+    readout_params([&](int widx) { add_desc(widx); });
+    if (nd && r.ok()) r.chk(gi_reduce_slabs(descs, nd, r.st));
+    return r.rc;
 }
 
 extern "C" int gi_ggnn_forward(const gi_ggnn_dims* dp, const float* const* params,
@@ -1696,6 +2047,7 @@ extern "C" int gi_ggnn_forward_ex(const gi_ggnn_dims* dp, const float* const* pa
     int rc = build_model(dp, m);
     if (rc) return rc;
     if (!gp) return GI_EINVAL;
+    if (m.mnn) return mnn_forward(m, params, gp, ws, out, ldout, (hipStream_t)stream, (hipStream_t)side_stream, run_flags);
     const int S = gp->S, E = gp->E, U = gp->U;
     const int* gfix = gp->gfix;
     const int* u_src = gp->u_src;
@@ -1973,6 +2325,7 @@ extern "C" int gi_bf3_enable(int on) {
 extern "C" long long gi_p0_cache_words(const gi_ggnn_dims* d) {
     Model m;
     if (int rc = build_model(d, m)) return rc;
+    if (m.mnn) return 0;                          // (no pass-0 row cache: gi_graph.p0_cache is ignored)
     Ws w;
     make_ws(m, 0, 0, 0, 0, w);
     return gi_p0_cache_words_for((m.d.kind == GI_KIND_ATTGGNN ? 2 : 1) * w.ldM);
@@ -1989,7 +2342,7 @@ extern "C" long long gi_ggnn_wcache_floats(const gi_ggnn_dims* d) {
 extern "C" int gi_ggnn_first_readout_param(const gi_ggnn_dims* d) {
     Model m;
     const int rc = build_model(d, m);
-    return rc ? rc : m.att.base;
+    return rc ? rc : m.mnn ? m.add1.base : m.att.base;
 }
 
 extern "C" int gi_ggnn_backward(const gi_ggnn_dims* dp, const float* const* params,
@@ -2013,6 +2366,9 @@ extern "C" int gi_ggnn_backward_phase(const gi_ggnn_dims* dp, const float* const
     int rc = build_model(dp, m);
     if (rc) return rc;
     if (!gp) return GI_EINVAL;
+    if (m.mnn)
+        return mnn_backward(m, params, gp, ws, slabs, y_out, ldout, d_out, lddout, grads, (hipStream_t)stream,
+                            (hipStream_t)side_stream, phase, prepacked, no_x2);
     const int S = gp->S, E = gp->E, U = gp->U;
     const int* gfix = gp->gfix;
     const int* u_src = gp->u_src;

@@ -15,6 +15,7 @@ missing library or a CPU tensor raises.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from collections import namedtuple
 from typing import List
 
@@ -39,8 +40,15 @@ def _dims_from_constants(c, B: int, kind: int = _L.KIND_GGNN) -> "_L.GgnnDims":
     d = _L.GgnnDims()
     d.kind = kind
     d.B, d.N, d.Fn, d.Fe = B, c.max_n_nodes, c.n_node_features, c.n_edge_features
-    d.H, d.M, d.G = c.hidden_node_features, c.message_size, c.gather_width
     d.A, d.C, d.passes = c.len_f_add_per_node, c.len_f_conn_per_node, c.message_passes
+    d.H, d.M = c.hidden_node_features, c.message_size
+    d.mlp1_depth, d.mlp1_hidden = c.mlp1_depth, c.mlp1_hidden_dim
+    d.mlp2_depth, d.mlp2_hidden = c.mlp2_depth, c.mlp2_hidden_dim
+    d.big_positive = float(getattr(c, "big_positive", 1e6))
+    if kind == _L.KIND_MNN:             # no message stacks, no gather: graph_emb_size = H (gnn/mpnn.py:37-39)
+        d.G = c.hidden_node_features
+        return d
+    d.G = c.gather_width
     if kind == _L.KIND_ATTGGNN:         # per-bond-type message + energy MLPs (gnn/mpnn.py:319-335)
         d.enn_depth, d.enn_hidden = c.msg_depth, c.msg_hidden_dim
         d.eatt_depth, d.eatt_hidden = c.att_depth, c.att_hidden_dim
@@ -48,9 +56,6 @@ def _dims_from_constants(c, B: int, kind: int = _L.KIND_GGNN) -> "_L.GgnnDims":
         d.enn_depth, d.enn_hidden = c.enn_depth, c.enn_hidden_dim
     d.att_depth, d.att_hidden = c.gather_att_depth, c.gather_att_hidden_dim
     d.emb_depth, d.emb_hidden = c.gather_emb_depth, c.gather_emb_hidden_dim
-    d.mlp1_depth, d.mlp1_hidden = c.mlp1_depth, c.mlp1_hidden_dim
-    d.mlp2_depth, d.mlp2_hidden = c.mlp2_depth, c.mlp2_hidden_dim
-    d.big_positive = float(c.big_positive)
     return d
 
 
@@ -62,11 +67,13 @@ def _set_dropout(dims, c, kind: int, seed: int) -> None:
     """AlphaDropout training mode (gnn/modules.py:130-142): per-stack probabilities + the mask seed."""
     attn = kind == _L.KIND_ATTGGNN
     dims.dropout = 1
+    dims.drop_mlp1, dims.drop_mlp2 = float(c.mlp1_dropout_p), float(c.mlp2_dropout_p)
+    dims.drop_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    if kind == _L.KIND_MNN:             # (only GlobalReadout has dropout sites)
+        return
     dims.drop_enn = float(c.msg_dropout_p if attn else c.enn_dropout_p)
     dims.drop_eatt = float(c.att_dropout_p) if attn else 0.0
     dims.drop_att, dims.drop_emb = float(c.gather_att_dropout_p), float(c.gather_emb_dropout_p)
-    dims.drop_mlp1, dims.drop_mlp2 = float(c.mlp1_dropout_p), float(c.mlp2_dropout_p)
-    dims.drop_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
 
 
 def ggnn_forward_raw(consts, nodes, edges, params, kind: int = _L.KIND_GGNN, dropout_seed=None,
@@ -104,8 +111,8 @@ def ggnn_forward_raw(consts, nodes, edges, params, kind: int = _L.KIND_GGNN, dro
                                 wcache)
     drop = dropout_seed is not None
     nodes, lay, gfix, S, E, U, D0, Ut = _ops.compact_count(nodes, edges, nodedup=drop,
-                                                           allow_multi_bond=kind == _L.KIND_GGNN)
-    attn = kind != _L.KIND_GGNN
+                                                           allow_multi_bond=kind != _L.KIND_ATTGGNN)
+    attn = kind == _L.KIND_ATTGGNN
     B = nodes.shape[0]
     dims = _dims_from_constants(consts, B, kind)
     if drop:
@@ -160,7 +167,7 @@ def _forward_bounded(lib, consts, nodes, edges, params, kind, bounds, p0_cache=N
     if nodes.dim() != 3:
         raise ValueError("nodes must be [B, N, Fn]")
     B, N = nodes.shape[0], nodes.shape[1]
-    attn = kind != _L.KIND_GGNN
+    attn = kind == _L.KIND_ATTGGNN
     dims = _dims_from_constants(consts, B, kind)
     if lib.gi_ggnn_num_params(C.byref(dims)) != len(params):
         raise RuntimeError("parameter table does not match the model dimensions")
@@ -534,7 +541,7 @@ class _FusedMPNN(torch.nn.Module):
             if bits:
                 w.zero_()
                 err |= bits
-        if self._KIND == _L.KIND_GGNN:
+        if self._KIND != _L.KIND_ATTGGNN:
             err &= ~_ops.ERR_MULTI_BOND              # several bond types on a pair = parallel edges, like the reference
         if err:
             raise ValueError("sync-free forward: " + ", ".join(
@@ -567,10 +574,14 @@ class _FusedMPNN(torch.nn.Module):
         self.last_dropout_seed = seed
         return seed
 
+    def _first_param(self) -> torch.nn.Parameter:
+        """The first parameter in state_dict order (the parameter cache's key, with the last one)."""
+        return getattr(self.msg_nns[0].seq, "0").weight
+
     def _params(self) -> List[torch.nn.Parameter]:
         cache = self.__dict__.get("_param_cache")
         term = self.APDReadout.fTermNet2.seq
-        if cache is None or cache[0] is not getattr(self.msg_nns[0].seq, "0").weight or \
+        if cache is None or cache[0] is not self._first_param() or \
                 cache[-1] is not getattr(term, str(3 * (len(term._modules) - 1))).bias:
             # (re)built when a Parameter object was replaced: load_state_dict(assign=True),
             # module surgery, parameter swapping on .to()
@@ -748,3 +759,46 @@ class AttentionGGNN(_FusedMPNN):
                                              [c.att_hidden_dim] * c.att_depth, c.message_size,
                                              c.att_dropout_p))
         self._build_update_and_readout(c)
+
+
+class MNN(_FusedMPNN):
+    """The "message neural network" model (gnn/mpnn.py:16-74) on MI355X HIP kernels: the message of an edge i <- j
+    with bond vector e is (sum_f e_f W[:, :, f]) h_j, computed aggregate-first (``gi_typed_seg_sum`` + one GEMM on
+    ``message_weights`` as stored); the readout feeds the sum of every slot's hidden state to GlobalReadout."""
+
+    _KIND = _L.KIND_MNN
+    cache_pass0 = False             # (no pass-0 row shortcut for this model)
+
+    def __init__(self, constants: namedtuple) -> None:
+        super().__init__()
+        c = constants
+        # attributes SummationMPNN.__init__ caches (gnn/summation_mpnn.py:14-22)
+        self.hidden_node_features = c.hidden_node_features
+        self.edge_features = c.n_edge_features
+        self.message_size = c.message_size
+        self.message_passes = c.message_passes
+        self.constants = c
+
+        # registration order and RNG consumption of gnn/mpnn.py:21-53: message_weights (uninitialised), GRUCell,
+        # GlobalReadout (graph_emb_size = hidden_node_features), then reset_parameters draws message_weights
+        message_weights = torch.Tensor(c.message_size, c.hidden_node_features, c.n_edge_features)
+        if c.device == "cuda":
+            message_weights = message_weights.to("cuda", non_blocking=True)
+        self.message_weights = torch.nn.Parameter(message_weights)
+        self.gru = torch.nn.GRUCell(input_size=c.message_size, hidden_size=c.hidden_node_features, bias=True)
+        self._grad_bucket = None
+        self.APDReadout = _modules.GlobalReadout(
+            node_emb_size=c.hidden_node_features, graph_emb_size=c.hidden_node_features,
+            mlp1_hidden_dim=c.mlp1_hidden_dim, mlp1_depth=c.mlp1_depth,
+            mlp1_dropout_p=c.mlp1_dropout_p, mlp2_hidden_dim=c.mlp2_hidden_dim,
+            mlp2_depth=c.mlp2_depth, mlp2_dropout_p=c.mlp2_dropout_p,
+            f_add_elems=c.len_f_add_per_node, f_conn_elems=c.len_f_conn_per_node, f_term_elems=1,
+            max_n_nodes=c.max_n_nodes, device=c.device)
+        self.reset_parameters()
+
+    def reset_parameters(self) -> None:
+        stdev = 1.0 / math.sqrt(self.message_weights.size(1))
+        self.message_weights.data.uniform_(-stdev, stdev)
+
+    def _first_param(self) -> torch.nn.Parameter:
+        return self.message_weights

@@ -30,7 +30,7 @@ AMAX_WORDS = 2048     # floats of an amax cell (include/graphinvent_amd.h GI_AMA
 GEMM_T128 = 2048      # with GEMM_BF3 | GEMM_X2, weight-gradient layout: the 128 x 128-tile kernel (gi_gemm_b3v.hip)
 GEMM_X2 = 1024        # with GEMM_BF3 and fp32 operands: two scaled fp16 planes per operand, three products (needs a_amax / b_amax)
 GEMM_BF3 = 128        # GI_GEMM_BF3: B is a gi_bf3_pack image; the launch runs as bf16x3 splits on the bf16 MFMA pipe
-KIND_GGNN, KIND_ATTGGNN = 0, 1
+KIND_GGNN, KIND_ATTGGNN, KIND_MNN = 0, 1, 2
 BWD_ALL, BWD_READOUT, BWD_PASSES = 0, 1, 2
 BWD_PREPACKED, BWD_NO_X2 = 0x100, 0x200        # OR-ed into the phase (GI_BWD_PREPACKED, GI_BWD_NO_X2)
 RUN_PREPACK_BWD, RUN_NO_X2 = 1, 2              # gi_ggnn_forward_ex flags (GI_RUN_*)
@@ -165,6 +165,10 @@ SIGNATURES = {
                                    vp, ci, vp, ci, vp, ci, vp, vp]),
     "gi_gather_readout_bwd_f": (ci, [vp, vp, ci, vp, vp, ci, ci, ci, ci, C.c_float,
                                      vp, ci, vp, ci, vp, ci, vp, cll, vp]),
+    "gi_typed_seg_sum": (ci, [vp, ci, vp, vp, vp, vp, ci, ci, ci, vp, ci, vp]),
+    "gi_typed_seg_sum_t": (ci, [vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, ci, ci, vp]),
+    "gi_graph_sum_fwd": (ci, [vp, ci, vp, ci, ci, ci, vp, ci, vp, ci, vp, ci, vp]),
+    "gi_graph_sum_bwd": (ci, [vp, ci, vp, ci, vp, ci, vp, ci, ci, ci, vp, ci, ci, vp]),
     "gi_expand_slots": (ci, [vp, ci, vp, ci, ci, ci, vp, ci, vp]),
     "gi_compress_slots": (ci, [vp, ci, vp, ci, ci, ci, ci, vp, ci, vp, ci, vp]),
     "gi_colsum": (ci, [vp, ci, ci, ci, vp, vp, vp]),

@@ -581,6 +581,26 @@ int gi_compress_slots2_f(float* t1a, int ldta, int Wa, const float* dcata, int l
                          float* t1b, int ldtb, int Wb, const float* dcatb, int ldcb, float* zpartb, int ldzb,
                          const int* cidx, int B, int N, int S, long long fshift, void* stream);
 
+/* MNN message function, aggregate first (gnn/mpnn.py:58-63 + the sum of gnn/summation_mpnn.py:141):
+ *   out[c, k * Fe + t] = sum over the dst-CSR slots s in [seg_off[c], seg_off[c+1]) whose message row u = in_perm[s]
+ *                        has bond type t (type_off buckets) of h[u_src[u], k],     c < rows, k < H
+ * (ldh % 4 == 0, ldh >= H rounded up to 4, 16-byte aligned h / out, ldo >= H * Fe; rows without in-edges get 0). */
+int gi_typed_seg_sum(const float* h, int ldh, const int* u_src, const int* in_perm, const int* seg_off,
+                     const int* type_off, int rows, int H, int Fe, float* out, int ldo, void* stream);
+/* its transpose (backward onto the source rows):
+ *   dh[c, k] (+)= sum over u in out_perm[src_off[c] .. src_off[c+1]) of sum over e in [mu_off[u], mu_off[u+1]) of
+ *                 dS[mu_dst[e], k * Fe + type(u)]                                  c < rows, k < H */
+int gi_typed_seg_sum_t(const float* dS, int lds, const int* out_perm, const int* src_off, const int* mu_off,
+                       const int* mu_dst, const int* type_off, int rows, int H, int Fe, float* dh, int lddh,
+                       int accumulate, void* stream);
+/* MNN readout graph sum (gnn/mpnn.py:69-74): g[b, 0:H] = sum_{n < N} h[cidx[b*N + n], 0:H], written to up to three
+ * destinations (NULL: skipped).  Backward: dh[c, 0:H] (+)= dg0[b] + dg1[b] + dg2[b] for every compact row c < S with
+ * b = slot_of[c] / N; row S (the zero row shared by padded slots) is left alone when accumulating, else set to 0. */
+int gi_graph_sum_fwd(const float* h, int ldh, const int* cidx, int B, int N, int H, float* out0, int ld0,
+                     float* out1, int ld1, float* out2, int ld2, void* stream);
+int gi_graph_sum_bwd(const float* dg0, int ld0, const float* dg1, int ld1, const float* dg2, int ld2,
+                     const int* slot_of, int S, int N, int H, float* dh, int lddh, int accumulate, void* stream);
+
 /* K7 gather readout — gnn/modules.py:44-52: g[b,:] = sum_n softmax_n(en[cidx[b,n]] - big*[mask==0]) * emb[cidx[b,n]],
  * written to up to three destinations (tier-2 concat inputs). */
 int gi_gather_readout_fwd(const float* en, const float* emb, int ld, const int* cidx,
@@ -691,6 +711,13 @@ typedef struct gi_ggnn_dims {
 } gi_ggnn_dims;
 #define GI_KIND_GGNN 0
 #define GI_KIND_ATTGGNN 1
+/* GI_KIND_MNN — `MNN` (gnn/mpnn.py:16-74): message m(i <- j) = (sum_f e_f W[:, :, f]) h_j with ONE parameter
+ * message_weights [M, H, Fe] (no per-bond-type MLPs), the same GRU update, and a readout that feeds the plain sum of
+ * every slot's hidden state (graph_emb[b] = sum_n h[b, n], no gather stacks) to GlobalReadout.  G must equal H; every
+ * depth other than mlp1_depth / mlp2_depth is 0.  Parameter table order: message_weights, gru, APDReadout.  Computed
+ * aggregate-first: S_p = gi_typed_seg_sum of h, messages = S_p . W.view(M, H Fe)^T (gi_gemm).  No pass-0 row cache
+ * (gi_p0_cache_words = 0, gi_graph.p0_cache ignored). */
+#define GI_KIND_MNN 2
 
 /* Creates / destroys a lowest-priority, non-blocking stream on the current device for
  * gi_ggnn_backward's `side_stream` argument (caller-owned handle; any other stream of the same
@@ -707,7 +734,8 @@ long long gi_ggnn_slab_floats(const gi_ggnn_dims* d, int S, int U, const int* Ut
 long long gi_ggnn_hx0_offset(const gi_ggnn_dims* d, int S, int E, int U, int D0);
 int gi_ggnn_ldhx(const gi_ggnn_dims* d);
 /* test/debug hook: offset (floats) and leading dimension of a named workspace buffer
- * ("hx" i=pass, "eact" i=pass j=layer, "m","agg","gi","gh" i=pass, "att_act" j=layer, "en", ...) */
+ * ("hx" i=pass, "eact" i=pass j=layer, "m","agg","gi","gh" i=pass, "att_act" j=layer, "en", ...;
+ * MNN: "ssum" i=pass — the typed sums S_p [R, H * Fe]) */
 int gi_ggnn_ws_query(const gi_ggnn_dims* d, int S, int E, int U, int D0, const char* name, int i,
                      int j, long long* off, int* ld);
 int gi_ggnn_forward(const gi_ggnn_dims* d, const float* const* params, const gi_graph* g,

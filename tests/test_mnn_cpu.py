@@ -1,0 +1,168 @@
+"""MNN (gnn/mpnn.py:16-74) without a GPU: the CPU restatement against the reference goldens, the drop-in class's
+construction contract (state_dict, seed-for-seed weights, MNN-only constants), and the aggregate-first identity the
+HIP path computes (typed sums + one GEMM) on the index arrays of a numpy model of the compaction."""
+import copy
+import hashlib
+import os
+import pickle
+
+import numpy as np
+import pytest
+import torch
+
+from graphinvent_amd import synthetic
+from graphinvent_amd.gnn import mpnn
+from tests import mnn_oracle as MO
+from tests.golden.spec import digest
+from tests.ref_dataflow import compact
+
+
+def rel(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return float(np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-30))
+
+
+def _tiny(golden_dir):
+    g = np.load(os.path.join(golden_dir, "golden_mnn_tiny.npz"))
+    cfg = MO.tiny_config()
+    P = {k[len("param."):]: torch.from_numpy(g[k]) for k in g.files if k.startswith("param.")}
+    return g, cfg, P
+
+
+@pytest.mark.parametrize("tag", ["", "one."])
+def test_oracle_tiny_matches_reference(golden_dir, tag):
+    g, cfg, P = _tiny(golden_dir)
+    keys = list(MO.param_shapes(cfg))
+    assert sorted(keys) == sorted(P)
+    P = {k: P[k] for k in keys}
+    nodes, edges, tgt = (torch.from_numpy(g[tag + k]).float() for k in ("nodes", "edges", "apds"))
+    out, loss, grads = MO.forward_backward(P, cfg, nodes, edges, tgt)
+    assert rel(out.numpy(), g[tag + "logits"]) < 2e-6
+    assert abs(float(loss) - float(g[tag + "loss"])) < 1e-6 * abs(float(g[tag + "loss"]))
+    for k, v in grads.items():
+        assert rel(v.numpy(), g[tag + "grad." + k]) < 2e-5, k
+
+
+def test_oracle_tiny_fp64_agrees_with_reference(golden_dir):
+    g, cfg, P = _tiny(golden_dir)
+    P = {k: v.double() for k, v in P.items()}
+    nodes, edges = (torch.from_numpy(g[k]).double() for k in ("nodes", "edges"))
+    out = MO.mnn_forward(P, cfg, nodes, edges)
+    assert rel(out.numpy(), g["logits"]) < 1e-5
+
+
+def test_oracle_gdb13_matches_reference(golden_dir):
+    g = np.load(os.path.join(golden_dir, "golden_mnn_gdb13.npz"))
+    sh = synthetic.SHAPES["gdb13"]
+    cfg = MO.mnn_config(sh["n_atom_types"], sh["n_formal_charge"], sh["max_n_nodes"])
+    P = MO.init_params(cfg, seed=int(g["seed"]))
+    nodes, edges, tgt = (torch.from_numpy(g[k]).float() for k in ("nodes", "edges", "apds"))
+    out, loss, grads = MO.forward_backward(P, cfg, nodes, edges, tgt)
+    assert rel(out.numpy(), g["logits"]) < 5e-6
+    assert abs(float(loss) - float(g["loss"])) < 1e-6 * abs(float(g["loss"]))
+    for k, v in grads.items():
+        d, ref = digest(v), g["gdigest." + k]
+        scale = max(np.max(np.abs(ref[2:])), 1e-12)
+        assert np.max(np.abs(d[2:] - ref[2:])) / scale < 1e-4, k
+        assert abs(d[1] - ref[1]) <= 1e-4 * ref[1] + 1e-12, k
+
+
+def _gdb13_cfg():
+    sh = synthetic.SHAPES["gdb13"]
+    return MO.mnn_config(sh["n_atom_types"], sh["n_formal_charge"], sh["max_n_nodes"])
+
+
+def test_constants_with_mnn_fields_only():
+    c = MO.as_constants(_gdb13_cfg())
+    for prefix in ("enn_", "gather_", "msg_", "att_"):
+        assert not any(f.startswith(prefix) for f in c._fields)
+    model = mpnn.MNN(c)
+    assert model.hidden_node_features == c.hidden_node_features and model.edge_features == c.n_edge_features
+    assert model.message_size == c.message_size and model.message_passes == c.message_passes
+    assert model.constants is c
+    dims = mpnn._dims_from_constants(c, 7, model._KIND)
+    assert (dims.kind, dims.G, dims.H, dims.enn_depth, dims.att_depth, dims.emb_depth) == (2, 100, 100, 0, 0, 0)
+
+
+def test_state_dict_keys_shapes_order():
+    cfg = _gdb13_cfg()
+    sd = mpnn.MNN(MO.as_constants(cfg)).state_dict()
+    shapes = MO.param_shapes(cfg)
+    assert list(sd) == list(shapes)
+    assert all(tuple(sd[k].shape) == shapes[k] for k in sd)
+
+
+@pytest.mark.parametrize("seed", [0, 1])
+def test_weights_seed_for_seed(golden_dir, seed):
+    g = np.load(os.path.join(golden_dir, "golden_mnn_gdb13.npz"))
+    torch.manual_seed(seed)
+    sd = mpnn.MNN(MO.as_constants(_gdb13_cfg())).state_dict()
+    for k, v in sd.items():
+        h = np.frombuffer(hashlib.sha256(v.contiguous().numpy().tobytes()).digest(), dtype=np.uint8)
+        assert np.array_equal(h, g[f"hash.{seed}.{k}"]), k
+
+
+def test_load_state_dict_deepcopy_pickle(golden_dir):
+    g, cfg, P = _tiny(golden_dir)
+    model = mpnn.MNN(MO.as_constants(cfg))
+    res = model.load_state_dict(P, strict=True)
+    assert not res.missing_keys and not res.unexpected_keys
+    for k, v in model.state_dict().items():
+        assert torch.equal(v, P[k])
+    for clone in (copy.deepcopy(model), pickle.loads(pickle.dumps(model))):
+        assert isinstance(clone, mpnn.MNN)
+        assert all(torch.equal(a, b) for a, b in zip(clone.state_dict().values(), model.state_dict().values()))
+        assert clone._params()[0] is clone.message_weights
+
+
+def test_cpu_tensor_raises(golden_dir):
+    g, cfg, P = _tiny(golden_dir)
+    model = mpnn.MNN(MO.as_constants(cfg))
+    model.load_state_dict(P)
+    with pytest.raises(Exception):
+        model(torch.from_numpy(g["nodes"]).float(), torch.from_numpy(g["edges"]).float())
+
+
+def _batch_with_cases():
+    n, e, _ = synthetic.make_batch(6, 7, 3, 2, 3, seed=5, frac_empty=0.0, frac_single=0.0)
+    n[0] = 0; e[0] = 0; n[0, 0, 0] = 1; n[0, 0, 3] = 1
+    e[0, 0, 0, 0] = 1; e[0, 0, 0, 1] = 1                      # self-loop, multi-hot (the generation dummy graph)
+    e[1, 0, 1, :] = 0; e[1, 0, 1, 0] = 1; e[1, 0, 1, 2] = 1   # a pair with two bond types (parallel edges)
+    n[2] = 0; e[2] = 0; n[2, 0, 1] = 1; n[2, 0, 4] = 1        # isolated atom
+    return n, e
+
+
+@pytest.mark.parametrize("nodedup", [False, True])
+def test_aggregate_first_identity_fp64(nodedup):
+    """messages = typed sums . W.view(M, H Fe)^T equals the reference's per-edge (sum_f e_f W_f) h_j summed into i;
+    and the transposed typed sum (the backward) is its adjoint."""
+    n, e = _batch_with_cases()
+    B, N, _, Fe = e.shape
+    H, M = 8, 5
+    g = compact(n, e, nodedup=nodedup)
+    R = g["S"] + 1
+    rng = np.random.default_rng(0)
+    h = rng.standard_normal((R, H))
+    h[R - 1] = 0.0                                             # the shared zero row
+    W = rng.standard_normal((M, H, Fe))
+    # the reference: one message per (b, i, j) with the pair's whole bond vector
+    ref = np.zeros((R, M))
+    eb, ei, ej = np.nonzero(e.sum(3))
+    for b, i, j in zip(eb, ei, ej):
+        Wij = np.einsum("f,mhf->mh", e[b, i, j].astype(np.float64), W)
+        ref[g["cidx"][b * N + i]] += Wij @ h[g["cidx"][b * N + j]]
+    u_type = np.searchsorted(g["type_off"], np.arange(g["U"]), side="right") - 1
+    S = MO.typed_sums(h, g["in_perm"], g["u_src"], u_type, g["seg_off"], Fe)
+    got = S @ W.reshape(M, H * Fe).T
+    assert np.abs(got - ref).max() < 1e-12 * max(1.0, np.abs(ref).max())
+    assert not S[R - 1].any()
+    # transpose over the source CSR, then the message rows' edges: <dS, T h> == <T^t dS, h>
+    dS = rng.standard_normal((R, H * Fe)).reshape(R, H, Fe)
+    dh = np.zeros((R, H))
+    for c in range(R):
+        for s in range(g["src_off"][c], g["src_off"][c + 1]):
+            u = g["out_perm"][s]
+            for k in range(g["mu_off"][u], g["mu_off"][u + 1]):
+                dh[c] += dS[g["mu_dst"][k], :, u_type[u]]
+    lhs = float((dS.reshape(R, -1) * S).sum())
+    assert abs(lhs - float((dh * h).sum())) < 1e-10 * max(1.0, abs(lhs))
