@@ -15,24 +15,86 @@ namespace {
 
 constexpr int SAMPLE_MAX_W = 15360;        // floats of one APD row kept in LDS (60 KB)
 
-template <typename ET>
+// RL variant (GraphGeneratorRL.get_actions, GraphGeneratorRL.py:521-633): the draw from the agent's row
+// is the same code path as above, bit for bit; the prior's row is streamed once (online maximum and
+// rescaled sum, never kept in LDS) and read at the drawn index.  Saved for the backward: the flat
+// index and the log-sum-exp of both rows.
+struct RlOut {
+    const float* prior;
+    int ldp;
+    int vec_agent, vec_prior;                // 16-byte aligned rows with a pitch % 4 == 0: float4 loads
+    float* like_prior;
+    int* idx;
+    float* lse;                              // [B, 2]: agent, prior
+};
+
+// online softmax state: (m, s) = (running maximum, sum of exp(v - m))
+__device__ __forceinline__ void osm_add(float& m, float& s, float v) {
+    if (v > m) { s = s * expf(m - v) + 1.f; m = v; }
+    else if (v != -INFINITY) s += expf(v - m);
+}
+
+__device__ __forceinline__ void osm_merge(float& m, float& s, float m2, float s2) {
+    const float M = fmaxf(m, m2);
+    if (M == -INFINITY) return;
+    s = (s > 0.f ? s * expf(m - M) : 0.f) + (s2 > 0.f ? s2 * expf(m2 - M) : 0.f);
+    m = M;
+}
+
+template <typename ET, bool RL>
 __global__ __launch_bounds__(256) void sample_actions_kernel(
     const float* __restrict__ logits, int ldl, const float* __restrict__ uniform,
     const int* __restrict__ n_nodes, const ET* __restrict__ edges, int N, int A, int Fe,
-    int* __restrict__ action, float* __restrict__ likelihood, int* __restrict__ flags) {
+    int* __restrict__ action, float* __restrict__ likelihood, int* __restrict__ flags, RlOut rl) {
     __shared__ float e[SAMPLE_MAX_W];
     __shared__ float red[256];
     __shared__ float wtot[4];
     __shared__ int found_s;
+    __shared__ float pm_s[4], ps_s[4];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int NA = N * A, NC = N * Fe, W = NA + NC + 1;
     const float* row = logits + (long long)b * ldl;
-    // pass 1: row -> LDS, maximum
+    // pass 1: row -> LDS, maximum (a maximum does not depend on the order: float4 loads change nothing)
     float mx = -INFINITY;
-    for (int i = tid; i < W; i += 256) {
-        const float v = row[i];
-        e[i] = v;
-        mx = fmaxf(mx, v);
+    if (RL && rl.vec_agent) {
+        const float4* row4 = reinterpret_cast<const float4*>(row);
+        for (int i = tid; i < W / 4; i += 256) {
+            const float4 v = row4[i];
+            e[4 * i] = v.x; e[4 * i + 1] = v.y; e[4 * i + 2] = v.z; e[4 * i + 3] = v.w;
+            mx = fmaxf(mx, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
+        }
+        for (int i = (W & ~3) + tid; i < W; i += 256) {
+            const float v = row[i];
+            e[i] = v;
+            mx = fmaxf(mx, v);
+        }
+    } else {
+        for (int i = tid; i < W; i += 256) {
+            const float v = row[i];
+            e[i] = v;
+            mx = fmaxf(mx, v);
+        }
+    }
+    if constexpr (RL) {
+        // the prior's row: one streamed pass, per-thread online softmax, then wave and block merges
+        const float* prow = rl.prior + (long long)b * rl.ldp;
+        float pm = -INFINITY, ps = 0.f;
+        if (rl.vec_prior) {
+            const float4* prow4 = reinterpret_cast<const float4*>(prow);
+            for (int i = tid; i < W / 4; i += 256) {
+                const float4 v = prow4[i];
+                osm_add(pm, ps, v.x); osm_add(pm, ps, v.y); osm_add(pm, ps, v.z); osm_add(pm, ps, v.w);
+            }
+            for (int i = (W & ~3) + tid; i < W; i += 256) osm_add(pm, ps, prow[i]);
+        } else {
+            for (int i = tid; i < W; i += 256) osm_add(pm, ps, prow[i]);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float m2 = __shfl_xor(pm, o), s2 = __shfl_xor(ps, o);
+            osm_merge(pm, ps, m2, s2);
+        }
+        if (lane == 0) { pm_s[wid] = pm; ps_s[wid] = ps; }
     }
     red[tid] = mx;
     if (tid == 0) found_s = 0x7fffffff;
@@ -107,7 +169,65 @@ __global__ __launch_bounds__(256) void sample_actions_kernel(
     action[4 * b + 0] = kind; action[4 * b + 1] = node; action[4 * b + 2] = rem; action[4 * b + 3] = from;
     likelihood[b] = e[idx] / total;                  // :541 apds[one_hot == 1]
     flags[b] = invalid | (reset << 1);
+    if constexpr (RL) {                              // GraphGeneratorRL.py:607-608 prior_apds[one_hot == 1]
+        float pm = pm_s[0], ps = ps_s[0];
+        for (int w = 1; w < 4; ++w) osm_merge(pm, ps, pm_s[w], ps_s[w]);
+        rl.like_prior[b] = expf(rl.prior[(long long)b * rl.ldp + idx] - pm) / ps;
+        rl.idx[b] = idx;
+        rl.lse[2 * b + 0] = mx + logf(total);
+        rl.lse[2 * b + 1] = pm + logf(ps);
+    }
 }
+
+// d_logits[b, j] = g[b] * like[b] * (delta(j, idx[b]) - exp(l[b, j] - lse[b])): the Jacobian of
+// softmax(l[b])[idx[b]] applied to the upstream gradient.  blockIdx.x = row * chunks + chunk,
+// blockIdx.z = side (0 agent, 1 prior); 1024 columns per block.
+struct LikeBwdSide {
+    const float* logits;
+    int ldl;
+    const float* g;                          // NULL: this side is skipped
+    const float* like;
+    float* d;
+    int ldd;
+    int vec;                                 // float4 loads and stores allowed
+};
+
+constexpr int LBWD_COLS = 1024;
+
+__global__ __launch_bounds__(256) void likelihood_bwd_kernel(LikeBwdSide s0, LikeBwdSide s1,
+                                                             const int* __restrict__ idx,
+                                                             const float* __restrict__ lse, int W,
+                                                             int chunks) {
+    const LikeBwdSide& s = blockIdx.z ? s1 : s0;
+    if (!s.g) return;
+    const int b = blockIdx.x / chunks, c0 = (blockIdx.x - b * chunks) * LBWD_COLS;
+    const float gl = s.g[b] * s.like[b], L = lse[2 * b + blockIdx.z];
+    const int k = idx[b];
+    const float* row = s.logits + (long long)b * s.ldl;
+    float* out = s.d + (long long)b * s.ldd;
+    if (s.vec) {
+        const int j = c0 + 4 * threadIdx.x;
+        if (j + 3 < W) {
+            const float4 v = *reinterpret_cast<const float4*>(row + j);
+            float4 r;
+            r.x = gl * ((j == k ? 1.f : 0.f) - expf(v.x - L));
+            r.y = gl * ((j + 1 == k ? 1.f : 0.f) - expf(v.y - L));
+            r.z = gl * ((j + 2 == k ? 1.f : 0.f) - expf(v.z - L));
+            r.w = gl * ((j + 3 == k ? 1.f : 0.f) - expf(v.w - L));
+            *reinterpret_cast<float4*>(out + j) = r;
+        } else {
+            for (int jj = j; jj < W; ++jj) out[jj] = gl * ((jj == k ? 1.f : 0.f) - expf(row[jj] - L));
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < LBWD_COLS / 256; ++q) {
+            const int j = c0 + q * 256 + threadIdx.x;
+            if (j < W) out[j] = gl * ((j == k ? 1.f : 0.f) - expf(row[j] - L));
+        }
+    }
+}
+
+bool aligned16(const void* p) { return ((unsigned long long)p & 15ull) == 0; }
 
 }  // namespace
 
@@ -124,14 +244,74 @@ extern "C" int gi_sample_actions(const float* logits, int ldl, const float* unif
     if (W > SAMPLE_MAX_W) return GI_ELIMIT;
     if (ldl < W) return GI_EINVAL;
     hipStream_t st = (hipStream_t)stream;
+    const RlOut none{};
     if (edges_dtype == GI_DTYPE_F32)
-        hipLaunchKernelGGL(sample_actions_kernel<float>, dim3(B), dim3(256), 0, st, logits, ldl,
-                           uniform, n_nodes, (const float*)edges, N, A, Fe, action, likelihood, flags);
+        hipLaunchKernelGGL((sample_actions_kernel<float, false>), dim3(B), dim3(256), 0, st, logits,
+                           ldl, uniform, n_nodes, (const float*)edges, N, A, Fe, action, likelihood,
+                           flags, none);
     else if (edges_dtype == GI_DTYPE_I8)
-        hipLaunchKernelGGL(sample_actions_kernel<signed char>, dim3(B), dim3(256), 0, st, logits,
-                           ldl, uniform, n_nodes, (const signed char*)edges, N, A, Fe, action,
-                           likelihood, flags);
+        hipLaunchKernelGGL((sample_actions_kernel<signed char, false>), dim3(B), dim3(256), 0, st,
+                           logits, ldl, uniform, n_nodes, (const signed char*)edges, N, A, Fe, action,
+                           likelihood, flags, none);
     else
         return GI_EINVAL;
+    return gi_launch_status();
+}
+
+extern "C" int gi_sample_actions_rl(const float* agent_logits, int lda, const float* prior_logits,
+                                    int ldp, const float* uniform, const int* n_nodes,
+                                    const void* edges, int edges_dtype, int B, int N, int A, int Fe,
+                                    int* action, float* like_agent, float* like_prior, int* flags,
+                                    int* idx, float* lse, void* stream) {
+    (void)hipGetLastError();
+    if (B <= 0) return 0;
+    if (!agent_logits || !prior_logits || !uniform || !n_nodes || !edges || !action ||
+        !like_agent || !like_prior || !flags || !idx || !lse || N <= 0 || A <= 0 || Fe <= 0)
+        return GI_EINVAL;
+    const long long W = (long long)N * A + (long long)N * Fe + 1;
+    if (W > SAMPLE_MAX_W) return GI_ELIMIT;
+    if (lda < W || ldp < W) return GI_EINVAL;
+    RlOut rl;
+    rl.prior = prior_logits;
+    rl.ldp = ldp;
+    rl.vec_agent = (lda % 4 == 0) && aligned16(agent_logits);
+    rl.vec_prior = (ldp % 4 == 0) && aligned16(prior_logits);
+    rl.like_prior = like_prior;
+    rl.idx = idx;
+    rl.lse = lse;
+    hipStream_t st = (hipStream_t)stream;
+    if (edges_dtype == GI_DTYPE_F32)
+        hipLaunchKernelGGL((sample_actions_kernel<float, true>), dim3(B), dim3(256), 0, st,
+                           agent_logits, lda, uniform, n_nodes, (const float*)edges, N, A, Fe,
+                           action, like_agent, flags, rl);
+    else if (edges_dtype == GI_DTYPE_I8)
+        hipLaunchKernelGGL((sample_actions_kernel<signed char, true>), dim3(B), dim3(256), 0, st,
+                           agent_logits, lda, uniform, n_nodes, (const signed char*)edges, N, A, Fe,
+                           action, like_agent, flags, rl);
+    else
+        return GI_EINVAL;
+    return gi_launch_status();
+}
+
+extern "C" int gi_sample_likelihood_bwd(int B, int W, const int* idx, const float* lse,
+                                        const float* agent_logits, int lda, const float* g_agent,
+                                        const float* like_agent, float* d_agent, int ldda,
+                                        const float* prior_logits, int ldp, const float* g_prior,
+                                        const float* like_prior, float* d_prior, int lddp,
+                                        void* stream) {
+    (void)hipGetLastError();
+    if (B <= 0 || (!g_agent && !g_prior)) return 0;
+    if (W <= 0 || !idx || !lse) return GI_EINVAL;
+    if (W > SAMPLE_MAX_W) return GI_ELIMIT;
+    if (g_agent && (!agent_logits || !like_agent || !d_agent || lda < W || ldda < W)) return GI_EINVAL;
+    if (g_prior && (!prior_logits || !like_prior || !d_prior || ldp < W || lddp < W)) return GI_EINVAL;
+    const LikeBwdSide s0{agent_logits, lda, g_agent, like_agent, d_agent, ldda,
+                         lda % 4 == 0 && ldda % 4 == 0 && aligned16(agent_logits) && aligned16(d_agent)};
+    const LikeBwdSide s1{prior_logits, ldp, g_prior, like_prior, d_prior, lddp,
+                         ldp % 4 == 0 && lddp % 4 == 0 && aligned16(prior_logits) && aligned16(d_prior)};
+    const int chunks = (W + LBWD_COLS - 1) / LBWD_COLS;
+    if ((long long)B * chunks > 0x7fffffffLL) return GI_ELIMIT;
+    hipLaunchKernelGGL(likelihood_bwd_kernel, dim3(B * chunks, 1, 2), dim3(256), 0,
+                       (hipStream_t)stream, s0, s1, idx, lse, W, chunks);
     return gi_launch_status();
 }

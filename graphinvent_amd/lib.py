@@ -182,6 +182,8 @@ SIGNATURES = {
     "gi_prof_collect": (ci, [vp, vp, vp, vp]),
     "gi_prof_pipes": (ci, [vp, vp, vp]),
     "gi_sample_actions": (ci, [vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
+    "gi_sample_actions_rl": (ci, [vp, ci, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]),
+    "gi_sample_likelihood_bwd": (ci, [ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp, ci, vp, vp, vp, ci, vp]),
     "gi_side_stream_create": (ci, [C.POINTER(vp)]),
     "gi_side_stream_destroy": (ci, [vp]),
     "gi_ggnn_num_params": (ci, [C.POINTER(GgnnDims)]),

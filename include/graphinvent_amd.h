@@ -669,6 +669,29 @@ int gi_sample_actions(const float* logits, int ldl, const float* uniform, const 
                       const void* edges, int edges_dtype, int B, int N, int A, int Fe, int* action,
                       float* likelihood, int* flags, void* stream);
 
+/* Sampling step of RL fine-tuning — replaces `softmax(agent(...))`, `softmax(prior(...))` +
+ * GraphGeneratorRL.get_actions / get_invalid_actions (GraphGeneratorRL.py:131-135, 521-720): the
+ * draw, decode and validity rules of gi_sample_actions on the agent's logits (action, like_agent and
+ * flags are bit-identical to gi_sample_actions for the same agent row and uniform), plus
+ *   like_prior[b] = softmax(prior_logits[b])[drawn index]
+ *   idx[b]        = the drawn flat index;  lse[2b + 0 / 1] = log-sum-exp of the agent / prior row
+ * (the state gi_sample_likelihood_bwd needs).  lda / ldp: row pitches of the two logits matrices. */
+int gi_sample_actions_rl(const float* agent_logits, int lda, const float* prior_logits, int ldp,
+                         const float* uniform, const int* n_nodes, const void* edges,
+                         int edges_dtype, int B, int N, int A, int Fe, int* action,
+                         float* like_agent, float* like_prior, int* flags, int* idx, float* lse,
+                         void* stream);
+
+/* Backward of the two likelihoods of gi_sample_actions_rl (softmax Jacobian at the drawn index):
+ *   d[b, j] = g[b] * like[b] * (delta(j, idx[b]) - exp(logits[b, j] - lse[b, side]))
+ * for the agent (side 0) and the prior (side 1) in one launch; a side whose g is NULL is skipped.
+ * d_agent / d_prior are written (not accumulated), W <= the sampler's row limit (GI_ELIMIT). */
+int gi_sample_likelihood_bwd(int B, int W, const int* idx, const float* lse,
+                             const float* agent_logits, int lda, const float* g_agent,
+                             const float* like_agent, float* d_agent, int ldda,
+                             const float* prior_logits, int ldp, const float* g_prior,
+                             const float* like_prior, float* d_prior, int lddp, void* stream);
+
 /* Optional per-launch timing for the benchmark's roofline leg: when enabled, every gi_gemm and
  * gi_seg_sum launch is bracketed by hipEvents on its stream.  gi_prof_collect blocks until the
  * recorded work finished and returns, per kernel family k (0 = GEMM, 1 = seg_sum): summed elapsed
