@@ -1,0 +1,223 @@
+// Growth step of graph generation (gfx950): the bookkeeping of one GraphGenerator.build_graphs round —
+// properly_terminated, copy_terminated_graphs, apply_actions, reset_graphs and the dummy graph's restore
+// (GraphGenerator.py:126-157, 211-465) — from gi_sample_actions' raw per-graph action / likelihood / flags, in place on
+// the generator's tensors.  The reference lays the draw out as index tuples through boolean masks, `nonzero` and
+// `len(...)`, each a read-back; here nothing leaves the device, and a whole round (forward, draw, growth) can be
+// recorded into one hipGraph.
+//
+// Three launches in stream order, so that every reader of the round's n and r sees the values of the round's entry:
+//   1. grow_scan_kernel (one workgroup): ranks inside S, |T|, |S|, every index check, the round's go / error decision,
+//      properly_terminated;
+//   2. grow_apply_kernel (one workgroup per graph): copy to the generated rows, apply, reset, restore graph 0;
+//   3. grow_commit_kernel (one thread): n += |S|, r += 1 or the error bits; the mapped host mirror.
+// Workspace in desc.state: [0] n, [1] r, [2] target, [3] error (persistent); [4] go, [5] |S|, [6] |T \ {0}|,
+// [7] |T|, [8] new error bits (this round's); [GI_GROW_STATE_WORDS + g] = graph g's slot: k >= 0 at position k of
+// T \ {0}, -2 - k at position k of I \ {0}, -1 outside S.
+#include "gi_common.h"
+
+namespace {
+
+constexpr int SCAN_THREADS = 1024;           // 16 waves of 64
+constexpr int APPLY_THREADS = 256;
+constexpr int SLOT_NONE = -1;
+
+struct GrowArgs {
+    gi_grow_desc d;
+    int A;                                   // add actions per node: prod(group) * Fe
+};
+
+__device__ __forceinline__ long long node_off(const gi_grow_desc& d, int g) { return (long long)g * d.N * d.Fn; }
+__device__ __forceinline__ long long edge_off(const gi_grow_desc& d, int g) {
+    return (long long)g * d.N * d.N * d.Fe;
+}
+
+__global__ __launch_bounds__(SCAN_THREADS) void grow_scan_kernel(GrowArgs a) {
+    const gi_grow_desc& d = a.d;
+    __shared__ int wsum[SCAN_THREADS / 64];
+    __shared__ int bits_s;
+    __shared__ int sh[4];                    // go, n, |T|
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    int* slot = d.state + GI_GROW_STATE_WORDS;
+    if (tid == 0) bits_s = 0;
+    __syncthreads();
+    int carry_t = 0, carry_i = 0, graph0_term = 0;
+    // packed counts: terminated (g != 0) in the low 16 bits, invalid (g != 0) in the high ones; a chunk of 1024 fits
+    for (int base = 0; base < d.B; base += SCAN_THREADS) {
+        const int g = base + tid;
+        int is_t = 0, is_i = 0, bad = 0;
+        if (g < d.B) {
+            const int kind = d.action[4 * g + 0], to = d.action[4 * g + 1], rem = d.action[4 * g + 2],
+                      from = d.action[4 * g + 3];
+            const int inv = d.flags[g] & 1;
+            const int nn = d.n_nodes[g];
+            if (kind < 0 || kind > 2) bad |= GI_GROW_ERR_ACTION;
+            if (kind == 2 && inv) bad |= GI_GROW_ERR_ACTION;
+            if (kind == 0 && (to < 0 || to >= d.N || rem < 0 || rem >= a.A || from < 0 || from >= d.N))
+                bad |= GI_GROW_ERR_ACTION;
+            if (kind == 1 && (to < 0 || to >= d.N || rem < 0 || rem >= d.Fe || from < -1 || from >= d.N))
+                bad |= GI_GROW_ERR_ACTION;
+            // an add that survives the round (not reset, not the restored graph 0) must not wrap the int8 count
+            if (kind == 0 && !inv && g != 0 && nn >= 127) bad |= GI_GROW_ERR_NNODES;
+            if (g == 0 && kind == 2) graph0_term = 1;
+            is_t = (kind == 2 && g != 0);
+            is_i = (inv && g != 0);
+        }
+        if (bad) atomicOr(&bits_s, bad);
+        const int v = is_t | (is_i << 16);
+        int x = v;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int y = __shfl_up(x, o);
+            if (lane >= o) x += y;
+        }
+        if (lane == 63) wsum[wid] = x;
+        __syncthreads();
+        int woff = 0, tot = 0;
+        for (int w = 0; w < SCAN_THREADS / 64; ++w) {
+            if (w < wid) woff += wsum[w];
+            tot += wsum[w];
+        }
+        const int excl = woff + x - v;
+        if (g < d.B)
+            slot[g] = is_t ? carry_t + (excl & 0xffff) : (is_i ? -2 - (carry_i + (excl >> 16)) : SLOT_NONE);
+        carry_t += tot & 0xffff;
+        carry_i += tot >> 16;
+        __syncthreads();                     // wsum is reused by the next chunk
+    }
+    if (graph0_term) atomicOr(&bits_s, 1 << 30);   // (graph 0 is in the first chunk: carried through bits_s)
+    __syncthreads();
+    if (tid == 0) {
+        const int n = d.state[0], r = d.state[1], target = d.state[2], err = d.state[3];
+        const int n_s = carry_t + carry_i;
+        const int n_t = carry_t + ((bits_s >> 30) & 1);
+        int bits = bits_s & ~(1 << 30);
+        int go = 0;
+        if (n < target && err == 0) {
+            if (r >= d.L) bits |= GI_GROW_ERR_ROUND;
+            if ((long long)n + n_s > d.C) bits |= GI_GROW_ERR_CAPACITY;
+            go = bits == 0;
+        } else {
+            bits = 0;                        // frozen: this round neither writes nor reports
+        }
+        d.state[4] = go;
+        d.state[5] = n_s;
+        d.state[6] = carry_t;
+        d.state[7] = n_t;
+        d.state[8] = bits;
+        sh[0] = go; sh[1] = n; sh[2] = n_t;
+    }
+    __syncthreads();
+    if (!sh[0]) return;
+    const int n = sh[1], end = min(n + sh[2], d.C);           // torch clips the slice at C (:127)
+    for (int i = n + tid; i < end; i += SCAN_THREADS) d.properly_terminated[i] = 1;
+}
+
+__global__ __launch_bounds__(APPLY_THREADS) void grow_apply_kernel(GrowArgs a) {
+    const gi_grow_desc& d = a.d;
+    const int* st = d.state;
+    if (!st[4]) return;
+    const int g = blockIdx.x, tid = threadIdx.x;
+    const int n = st[0], r = st[1], n_t0 = st[6];
+    const int s = st[GI_GROW_STATE_WORDS + g];
+    const float like = d.likelihood[g];
+    const int NF = d.N * d.Fn, NNF = d.N * d.N * d.Fe;
+    float* nodes = d.nodes + node_off(d, g);
+    float* edges = d.edges + edge_off(d, g);
+    float* lrow = d.likelihoods + (long long)g * d.L;
+    if (s != SLOT_NONE) {
+        // copy (:365-383) with likelihoods[g, r] = likelihood[g], then the reset (:430-465): the action applied in
+        // between (:211-338) only touches what the reset clears
+        const int k = s >= 0 ? s : n_t0 + (-2 - s);
+        const long long row = (long long)n + k;
+        float* gn = d.gen_nodes + (long long)row * NF;
+        float* ge = d.gen_edges + (long long)row * NNF;
+        float* gl = d.gen_likelihoods + row * d.L;
+        for (int i = tid; i < NF; i += APPLY_THREADS) { gn[i] = nodes[i]; nodes[i] = 0.f; }
+        for (int i = tid; i < NNF; i += APPLY_THREADS) { ge[i] = edges[i]; edges[i] = 0.f; }
+        for (int j = tid; j < d.L; j += APPLY_THREADS) { gl[j] = j == r ? like : lrow[j]; lrow[j] = 0.f; }
+        if (tid == 0) { d.gen_n_nodes[row] = d.n_nodes[g]; d.n_nodes[g] = 0; }
+        return;
+    }
+    // every other graph applies its action; graph 0 is then restored
+    if (g == 0)
+        for (int i = tid; i < NF; i += APPLY_THREADS) nodes[i] = 1.f;   // (what an add would set is 1 already)
+    if (tid != 0) return;
+    const int kind = d.action[4 * g + 0], to = d.action[4 * g + 1], rem = d.action[4 * g + 2],
+              from = d.action[4 * g + 3];
+    const int N = d.N, Fe = d.Fe;
+    if (kind == 0) {                                              // add (:264-317)
+        const int nn = d.n_nodes[g];
+        const int bt = rem % Fe;
+        if (g != 0) {
+            int q = rem / Fe, off = d.Fn;
+            for (int j = d.n_groups - 1; j >= 0; --j) {          // unravel over the node-feature groups, last fastest
+                const int size = d.group[j];
+                off -= size;
+                nodes[from * d.Fn + off + q % size] = 1.f;
+                q /= size;
+            }
+        }
+        if (nn != 0) {                                            // no bond for a first atom (:304-311)
+            edges[((long long)to * N + from) * Fe + bt] = 1.f;
+            edges[((long long)from * N + to) * Fe + bt] = 1.f;
+        }
+        d.n_nodes[g] = g == 0 ? 1 : (signed char)(nn + 1);       // :314 (graph 0: restored, :463)
+        lrow[r] = like;                                           // :315
+    } else if (kind == 1) {                                       // connect (:319-337)
+        const int f = from < 0 ? from + N : from;                 // torch's wrap of -1
+        edges[((long long)f * N + to) * Fe + rem] = 1.f;
+        edges[((long long)to * N + f) * Fe + rem] = 1.f;
+        lrow[r] = like;
+    }
+    if (g == 0) {
+        edges[0] = 1.f;                                           // :462
+        d.n_nodes[0] = 1;
+    }
+}
+
+__global__ __launch_bounds__(64) void grow_commit_kernel(int* state, int* host_state) {
+    if (threadIdx.x != 0) return;
+    if (state[4]) {
+        state[0] += state[5];
+        state[1] += 1;
+    } else {
+        state[3] |= state[8];
+    }
+    if (host_state) {
+        volatile int* h = host_state;
+        h[0] = state[0]; h[1] = state[1]; h[2] = state[2]; h[3] = state[3];
+        __threadfence_system();
+    }
+}
+
+}  // namespace
+
+extern "C" int gi_grow_state_words(int B) { return B < 0 ? GI_EINVAL : GI_GROW_STATE_WORDS + B; }
+
+extern "C" int gi_grow_graphs(const gi_grow_desc* desc, void* stream) {
+    (void)hipGetLastError();
+    if (!desc) return GI_EINVAL;
+    const gi_grow_desc& d = *desc;
+    if (d.B <= 0 || d.N <= 0 || d.Fn <= 0 || d.Fe <= 0 || d.L <= 0 || d.C <= 0) return GI_EINVAL;
+    if (d.N > GI_MAX_NODES || d.n_groups < 1 || d.n_groups > GI_GROW_MAX_GROUPS) return GI_ELIMIT;
+    if (!d.nodes || !d.edges || !d.n_nodes || !d.likelihoods || !d.gen_nodes || !d.gen_edges || !d.gen_n_nodes ||
+        !d.gen_likelihoods || !d.properly_terminated || !d.action || !d.likelihood || !d.flags || !d.state)
+        return GI_EINVAL;
+    long long A = d.Fe, sum = 0;
+    for (int j = 0; j < d.n_groups; ++j) {
+        if (d.group[j] <= 0) return GI_EINVAL;
+        A *= d.group[j];
+        sum += d.group[j];
+        if (A > 0x7fffffffLL) return GI_ELIMIT;
+    }
+    if (sum != d.Fn) return GI_EINVAL;       // every add writes one feature per group: the groups tile the node row
+    if ((long long)d.N * d.N * d.Fe > 0x7fffffffLL) return GI_ELIMIT;
+    GrowArgs a;
+    a.d = d;
+    a.A = (int)A;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(grow_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, a);
+    hipLaunchKernelGGL(grow_apply_kernel, dim3(d.B), dim3(APPLY_THREADS), 0, st, a);
+    hipLaunchKernelGGL(grow_commit_kernel, dim3(1), dim3(64), 0, st, d.state, d.host_state);
+    return gi_launch_status();
+}

@@ -114,6 +114,18 @@ class GgnnDims(C.Structure):
                                          "drop_mlp2")] + [("drop_seed", C.c_ulonglong)]
 
 
+GROW_MAX_GROUPS, GROW_STATE_WORDS = 8, 16     # GI_GROW_MAX_GROUPS, GI_GROW_STATE_WORDS
+GROW_ERR_ROUND, GROW_ERR_CAPACITY, GROW_ERR_ACTION, GROW_ERR_NNODES = 1, 2, 4, 8   # GI_GROW_ERR_*
+
+
+class GrowDesc(C.Structure):
+    """gi_grow_desc"""
+    _fields_ = [(n, vp) for n in ("nodes", "edges", "n_nodes", "likelihoods", "gen_nodes", "gen_edges",
+                                  "gen_n_nodes", "gen_likelihoods", "properly_terminated", "action", "likelihood",
+                                  "flags", "state", "host_state")] + \
+               [(n, ci) for n in ("B", "N", "Fn", "Fe", "L", "C", "n_groups")] + [("group", ci * GROW_MAX_GROUPS)]
+
+
 class DropoutParams(C.Structure):                       # gi_dropout_params
     _fields_ = [("seed", C.c_ulonglong), ("id", C.c_uint), ("thresh", C.c_uint),
                 ("a", C.c_float), ("b_keep", C.c_float), ("b_drop", C.c_float)]
@@ -184,6 +196,8 @@ SIGNATURES = {
     "gi_sample_actions": (ci, [vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
     "gi_sample_actions_rl": (ci, [vp, ci, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]),
     "gi_sample_likelihood_bwd": (ci, [ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp, ci, vp, vp, vp, ci, vp]),
+    "gi_grow_state_words": (ci, [ci]),
+    "gi_grow_graphs": (ci, [C.POINTER(GrowDesc), vp]),
     "gi_side_stream_create": (ci, [C.POINTER(vp)]),
     "gi_side_stream_destroy": (ci, [vp]),
     "gi_ggnn_num_params": (ci, [C.POINTER(GgnnDims)]),

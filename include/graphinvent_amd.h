@@ -692,6 +692,54 @@ int gi_sample_likelihood_bwd(int B, int W, const int* idx, const float* lse,
                              const float* prior_logits, int ldp, const float* g_prior,
                              const float* like_prior, float* d_prior, int lddp, void* stream);
 
+/* Growth step of graph generation — the bookkeeping of one GraphGenerator.build_graphs round after the draw
+ * (GraphGenerator.py:126-157 with copy_terminated_graphs :340-387, apply_actions :211-338 and reset_graphs
+ * :430-465), in place on the generator's own tensors, from gi_sample_actions' raw action / likelihood / flags
+ * (no index tuples, no read-back).  Let n = state[0] (graphs generated so far), r = state[1] (round) at entry:
+ *   - frozen: nothing at all when n >= state[2] (target = batch_size) or state[3] (error) != 0;
+ *   - T = graphs with kind == 2 (graph 0 included), I = graphs with flags & 1, both ascending;
+ *     S = (T without 0) followed by (I without 0) (:130-133); properly_terminated[n : n + |T|] = 1 (:127, clipped at C);
+ *   - graph S[k] is copied to generated row n + k: nodes, edges, n_nodes and its likelihood row with
+ *     likelihoods[g, r] = likelihood[g] (:365-383);
+ *   - every graph's action is applied (:211-338: graph 0's and the terminated ones' too): add sets
+ *     nodes[g, from, off_j + sub_j] = 1 per node-feature group j (rem unravelled over group[] then Fe), both edge
+ *     directions of bond type rem % Fe unless n_nodes[g] was 0, n_nodes[g] += 1; connect sets both directions (from = -1
+ *     wraps to N - 1); both write likelihoods[g, r]; terminate does nothing;
+ *   - S is reset (zeros, :430-465), graph 0 restored (nodes[0] = 1, edges[0,0,0,0] = 1, n_nodes[0] = 1; its other
+ *     edges stay), then state[0] += |S|, state[1] += 1.
+ * Every index is checked before any write of the round.  Where the reference raises, the round writes nothing and
+ * OR-s a GI_GROW_ERR_* bit into state[3], which freezes every later round.  state = GI_GROW_STATE_WORDS + B ints of
+ * device memory (gi_grow_state_words), zero-filled with state[2] = target before the first round; host_state = NULL
+ * or 4 ints of mapped host memory (gi_host_flag_create) that receive state[0..3] at the end of every round.
+ * Three launches in stream order (scan and validate / per-graph copy, apply, reset / counters). */
+#define GI_GROW_MAX_GROUPS 8
+#define GI_GROW_STATE_WORDS 16
+#define GI_GROW_ERR_ROUND    1   /* r >= L: IndexError at the round's first likelihood write (:365, :305, :330) */
+#define GI_GROW_ERR_CAPACITY 2   /* n + |S| > C: the slice assignment of :379-382 fails */
+#define GI_GROW_ERR_ACTION   4   /* kind / node_to / rem / from out of range, or a graph both terminated and invalid */
+#define GI_GROW_ERR_NNODES   8   /* n_nodes would overflow int8 */
+typedef struct gi_grow_desc {
+    float* nodes;                  /* [B, N, Fn] */
+    float* edges;                  /* [B, N, N, Fe] */
+    signed char* n_nodes;          /* [B] */
+    float* likelihoods;            /* [B, L] */
+    float* gen_nodes;              /* [C, N, Fn] */
+    float* gen_edges;              /* [C, N, N, Fe] */
+    signed char* gen_n_nodes;      /* [C] */
+    float* gen_likelihoods;        /* [C, L] */
+    signed char* properly_terminated;  /* [C] */
+    const int* action;             /* [B, 4] of gi_sample_actions */
+    const float* likelihood;       /* [B] */
+    const int* flags;              /* [B] */
+    int* state;                    /* device, gi_grow_state_words(B) ints */
+    int* host_state;               /* NULL or mapped host memory, 4 ints */
+    int B, N, Fn, Fe, L, C;
+    int n_groups;                  /* node-feature groups of the add action (dim_f_add[1:-1]); sum(group) == Fn */
+    int group[GI_GROW_MAX_GROUPS];
+} gi_grow_desc;
+int gi_grow_state_words(int B);
+int gi_grow_graphs(const gi_grow_desc* desc, void* stream);
+
 /* Optional per-launch timing for the benchmark's roofline leg: when enabled, every gi_gemm and
  * gi_seg_sum launch is bracketed by hipEvents on its stream.  gi_prof_collect blocks until the
  * recorded work finished and returns, per kernel family k (0 = GEMM, 1 = seg_sum): summed elapsed
