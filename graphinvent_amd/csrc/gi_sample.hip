@@ -9,6 +9,14 @@
 // whose cumulative un-normalised probability exceeds u * total.  Cumulative sums run in a fixed
 // order (256 contiguous chunks, sequential inside a chunk), so a (logits, u) pair always gives the
 // same action.  HBM-bound: reads B*W*4 bytes once; the row lives in LDS between the passes.
+//
+// The claim rule is one fp32 cumulative function, monotone in the index, with no gaps at the chunk
+// seams.  The running maximum of the inclusive scan of the chunk sums, clamped to the total, gives
+// non-decreasing boundaries B(t) with B(255) = total, and chunk t owns the targets in [B(t-1), B(t));
+// the last chunk also owns everything at or past the total (u = 1 included).  Inside its range the chunk
+// walks from B(t-1) and takes the first element whose running sum exceeds the target.  When its walk
+// ends below B(t) (fp32 rounding), or the target is at or past the total, it takes the last element
+// with e > 0 at or before its end.  Only elements with e > 0 can be drawn.
 #include "gi_common.h"
 
 namespace {
@@ -48,8 +56,9 @@ __global__ __launch_bounds__(256) void sample_actions_kernel(
     int* __restrict__ action, float* __restrict__ likelihood, int* __restrict__ flags, RlOut rl) {
     __shared__ float e[SAMPLE_MAX_W];
     __shared__ float red[256];
-    __shared__ float wtot[4];
+    __shared__ float wtot[4], wmax[4];
     __shared__ int found_s;
+    __shared__ int lastpos[256];             // per chunk: its last index with e > 0, or -1
     __shared__ float pm_s[4], ps_s[4];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int NA = N * A, NC = N * Fe, W = NA + NC + 1;
@@ -111,34 +120,58 @@ __global__ __launch_bounds__(256) void sample_actions_kernel(
     const int L = (W + 255) / 256;
     const int lo = min(tid * L, W), hi = min(lo + L, W);
     float csum = 0.f;
-    for (int i = lo; i < hi; ++i) csum += e[i];
-    // exclusive scan of the chunk sums in chunk order (wave shuffle + 4 wave totals)
+    int lp = -1;
+    for (int i = lo; i < hi; ++i) {
+        csum += e[i];
+        if (e[i] > 0.f) lp = i;
+    }
+    lastpos[tid] = lp;
+    // inclusive scan of the chunk sums in chunk order (wave shuffle + 4 wave totals): woff + x.  Its
+    // intermediate window sums are not monotone, so neither is woff + x after a chunk of zeros: the
+    // boundaries are its running maximum B(t), clamped to the total.  fl(woff + max x) = max fl(woff + x),
+    // so the maximum is taken per wave on x and across waves on woff + wave maximum: exact.
     float x = csum;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
         const float y = __shfl_up(x, o);
         if (lane >= o) x += y;
     }
-    if (lane == 63) wtot[wid] = x;
+    float xm = x;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float y = __shfl_up(xm, o);
+        if (lane >= o) xm = fmaxf(xm, y);
+    }
+    const float xmprev = __shfl_up(xm, 1);
+    if (lane == 63) { wtot[wid] = x; wmax[wid] = xm; }
     __syncthreads();
-    float woff = 0.f;
-    for (int w = 0; w < wid; ++w) woff += wtot[w];
-    const float excl = woff + x - csum;
+    float woff = 0.f, carry = 0.f;                   // carry: B of the previous wave's last chunk
+    for (int w = 0; w < wid; ++w) {
+        carry = fmaxf(carry, woff + wmax[w]);
+        woff += wtot[w];
+    }
     const float total = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    // B(t-1) is the very value chunk t-1 computed as its B(t)
+    const float bprev = lane ? fminf(fmaxf(carry, woff + xmprev), total) : fminf(carry, total);
+    const float bend = fminf(fmaxf(carry, woff + xm), total);
     const float target = uniform[b] * total;
-    // the chunk whose cumulative range contains the target walks its elements
-    if (hi > lo && excl <= target) {
-        float c = excl;
-        for (int i = lo; i < hi; ++i) {
-            c += e[i];
-            if (c > target) { atomicMin(&found_s, i); break; }
+    // exactly one chunk owns any target >= 0 (a NaN target is owned by none: see the fallback below)
+    if (bprev <= target && (target < bend || tid == 255)) {
+        int k = -1;
+        if (target < bend) {
+            float c = bprev;
+            for (int i = lo; i < hi; ++i) {
+                c += e[i];                           // c > target >= c - e[i] only if e[i] > 0
+                if (c > target) { k = i; break; }
+            }
         }
+        for (int t = tid; k < 0 && t >= 0; --t) k = lastpos[t];
+        if (k >= 0) found_s = k;
     }
     __syncthreads();
     if (tid != 0) return;
-    // every chunk starting at or below the target walks; the one containing it finds c > target.  The
-    // smallest index wins (rounding at a chunk edge can give two candidates), and a target that
-    // rounding puts past the total falls back to the last action.
+    // the only ways to leave no claim are a NaN target (NaN or +inf logits) or a row with no e > 0:
+    // both fall back to the last action
     int idx = found_s;
     if (idx >= W) idx = W - 1;
     const int nn = n_nodes[b];

@@ -658,8 +658,8 @@ int gi_scale_by_scalar(float* x, long long n, const float* scale, void* stream);
 /* Sampling step of graph generation — replaces `softmax(model(nodes, edges))` +
  * GraphGenerator.get_actions / get_invalid_actions (GraphGenerator.py:121, 467-657) with one launch:
  * per graph b, softmax of logits[b, 0:W] (W = N*A + N*Fe + 1), ONE categorical draw = the first
- * action whose cumulative probability exceeds uniform[b] (inverse CDF; uniform in [0,1)), decode and
- * validity rules.  n_nodes[B] int32 = atoms currently in each graph; edges [B,N,N,Fe] (GI_DTYPE).
+ * action whose cumulative probability exceeds uniform[b] (inverse CDF; uniform in [0,1]), decode and
+ * validity rules.  Only actions of positive fp32 probability are drawn; u = 1 draws the last of them.  n_nodes[B] int32 = atoms currently in each graph; edges [B,N,N,Fe] (GI_DTYPE).
  *   action[b] = {kind (0 add, 1 connect, 2 terminate), node_to, rem, from}: rem = index inside the
  *               node's block (add: ravelled (atom type, charge, ..., bond type); connect: bond type);
  *               from = n_nodes (add; 0 where the reference resets it, :567) or n_nodes-1 (connect)

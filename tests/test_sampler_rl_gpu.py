@@ -66,6 +66,7 @@ def test_rl_sampler_on_the_reference_fixture(golden_dir, edge_dtype):
         assert np.array_equal(out[3].cpu().numpy(), ref["invalid"])
         assert np.abs(out[4].cpu().numpy() - pa[rows, k]).max() < 1e-6
         assert np.abs(out[5].cpu().numpy() - pp[rows, k]).max() < 1e-6
+        assert np.all(like_a.cpu().numpy() > 0) and np.all(out[4].cpu().numpy() > 0)
         lse_ref = np.stack([np.log(np.exp(g[n].astype(np.float64)).sum(1)) for n in ("agent_logits", "prior_logits")], 1)
         assert np.abs(lse.cpu().numpy() - lse_ref).max() < 1e-5
     # uniforms inside the reference's drawn intervals: the reference's tuples, exactly
@@ -83,6 +84,7 @@ def test_rl_sampler_on_the_reference_fixture(golden_dir, edge_dtype):
     assert np.array_equal(invalid.cpu().numpy(), g["invalid"])
     assert np.abs(like_a.detach().cpu().numpy() - g["agent_likelihoods"]).max() < 1e-6
     assert np.abs(like_p.detach().cpu().numpy() - g["prior_likelihoods"]).max() < 1e-6
+    assert np.all(like_a.detach().cpu().numpy() > 0) and np.all(like_p.detach().cpu().numpy() > 0)
     ((like_a * torch.from_numpy(g["wa"]).to(DEV)).sum() + (like_p * torch.from_numpy(g["wp"]).to(DEV)).sum()).backward()
     assert np.abs(la_g.grad.cpu().numpy() - g["grad_agent"]).max() < 2e-7
     assert np.abs(lp_g.grad.cpu().numpy() - g["grad_prior"]).max() < 2e-7
