@@ -2094,26 +2094,36 @@ extern "C" int gi_ggnn_forward_ex(const gi_ggnn_dims* dp, const float* const* pa
     if (wcache && ((uintptr_t)wcache & 15)) return GI_EINVAL;
     r.wc_valid = wcache && gp->wcache_valid != 0;
     r.wc_bf3 = wcache ? wcache + wc.bf3_wamax : nullptr;
-    if (d.passes > 0 && E > 0)          // packed weight images of the chain kernel, once per forward
-        for (int k = 0; k < (attn ? 2 : 1); ++k)
-            if (w.img_f_n[k] > 0) {
-                r.img_f[k] = ws + w.img_f[k];
-                if (!r.drop && chain_fwd_x2_enabled(r.x2)) {   // the row-independent fp16x2 chain: its image instead of the fp32 one
-                    float* const img = (wcache && wc.img_fx[k] >= 0) ? wcache + wc.img_fx[k] : ws + w.img_fx[k];
-                    float* const cells = (wcache && wc.img_fx[k] >= 0) ? wcache + wc.chain_amax_f[k] : ws + w.chain_amax_f[k];
-                    if (!(r.wc_valid && wc.img_fx[k] >= 0)) {
-                    Run rp = r;
-                    rp.chain_amax[k] = cells;
-                    chain_pack(rp, k ? m.eatt : m.msg, d.Fe, false, img);
-                    r.chk(rp.rc);
-                    }
-                    r.img_fx[k] = img;
-                    r.chain_amax_f[k] = cells;
-                    r.img_f[k] = r.img_fx[k];                   // (nothing may read the fp32 image: it was not packed)
-                } else {
-                    chain_pack(r, k ? m.eatt : m.msg, d.Fe, false, r.img_f[k]);
-                }
+    // Packed weight images of the chain kernel, once per forward.  A forward whose chains do not run (no edges) still
+    // derives the fp16x2 image, its cells and (below) its weight guard into a cache that is not valid yet: the caller
+    // marks the cache valid after this call, and a later forward with edges reads the image from it.
+    const bool chains_run = d.passes > 0 && E > 0;
+    float* guard_cells[2] = {nullptr, nullptr};     // the forward chains' max |W| cells packed by this call
+    for (int k = 0; k < (attn ? 2 : 1); ++k) {
+        if (w.img_f_n[k] <= 0) continue;
+        const bool fx = !r.drop && chain_fwd_x2_enabled(r.x2);      // the row-independent fp16x2 chain, not the fp32 one
+        const bool cached = fx && wcache && wc.img_fx[k] >= 0;
+        if (!chains_run && !(cached && !r.wc_valid)) continue;
+        if (fx) {
+            float* const img = cached ? wcache + wc.img_fx[k] : ws + w.img_fx[k];
+            float* const cells = cached ? wcache + wc.chain_amax_f[k] : ws + w.chain_amax_f[k];
+            if (!(r.wc_valid && cached)) {
+                Run rp = r;
+                rp.chain_amax[k] = cells;
+                chain_pack(rp, k ? m.eatt : m.msg, d.Fe, false, img);
+                r.chk(rp.rc);
+                guard_cells[k] = cells;
             }
+            if (chains_run) {
+                r.img_fx[k] = img;
+                r.chain_amax_f[k] = cells;
+                r.img_f[k] = r.img_fx[k];                       // (nothing may read the fp32 image: it was not packed)
+            }
+        } else {
+            r.img_f[k] = ws + w.img_f[k];
+            chain_pack(r, k ? m.eatt : m.msg, d.Fe, false, r.img_f[k]);
+        }
+    }
     // Everything else that depends on the weights only goes to the side stream when there is one: the amax cells of
     // the fp16x2 layers (needed by the readout, hundreds of microseconds from here) and — GI_RUN_PREPACK_BWD — the
     // images the backward would otherwise pack at its start, in front of its first launches.
@@ -2155,9 +2165,9 @@ extern "C" int gi_ggnn_forward_ex(const gi_ggnn_dims* dp, const float* const* pa
                 }
     }
     // the forward chains' weights through the fp16x2 guard (output channels / input columns below the per-tensor range)
-    if (r.guard && r.ok() && !r.wc_valid)
+    if (r.guard && r.ok())
         for (int k = 0; k < (attn ? 2 : 1); ++k)
-            if (r.img_fx[k]) {
+            if (guard_cells[k]) {
                 const Mlp* mlps = k ? m.eatt : m.msg;
                 gi_absmax_desc wd[GI_ABSMAX_MAX];
                 int n = 0;
@@ -2166,7 +2176,7 @@ extern "C" int gi_ggnn_forward_ex(const gi_ggnn_dims* dp, const float* const* pa
                     for (int t = 0; t < d.Fe; ++t) {
                         wd[n].x = r.P[mlps[t].w(l)]; wd[n].rows = mlps[0].fan_out(l); wd[n].cols = mlps[0].fan_in(l);
                         wd[n].ld = wd[n].cols;
-                        wd[n].out = r.chain_amax_f[k] + ((long long)l * d.Fe + t) * GI_AMAX_WORDS;
+                        wd[n].out = guard_cells[k] + ((long long)l * d.Fe + t) * GI_AMAX_WORDS;
                         if (++n == GI_ABSMAX_MAX || (l == L - 1 && t == d.Fe - 1)) {
                             r.chk(gi_x2_weight_guard(wd, n, r.guard + 1, r.guard_host, prep));
                             n = 0;

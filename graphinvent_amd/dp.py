@@ -87,7 +87,7 @@ class DataParallel:
 
     def broadcast_parameters(self, src: int = 0) -> None:
         """Make every rank start from rank `src`'s weights."""
-        if self.world_size == 1:
+        if self.world_size == 1 and not self.always_reduce:
             return
         with torch.no_grad():
             for p in self.params:

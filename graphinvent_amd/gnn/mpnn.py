@@ -193,12 +193,13 @@ def _forward_bounded(lib, consts, nodes, edges, params, kind, bounds, p0_cache=N
         gs.x2_guard, gs.x2_guard_host = guard[0].data_ptr(), guard[1]
     if wcache is not None:
         gs.wcache, gs.wcache_valid = wcache["buf"].data_ptr(), int(bool(wcache["valid"]))
-        wcache["valid"] = True
     # (no side stream: everything in line on the caller's stream — this forward may be recorded into a hipGraph)
     _L.check(lib.gi_ggnn_forward_ex(C.byref(dims), _ptr_table(params), C.byref(gs), box["ws"].data_ptr(),
                                     out.data_ptr(), apd, torch.cuda.current_stream(dev).cuda_stream, 0,
                                     _L.RUN_NO_X2 if no_x2 else 0),
              "gi_ggnn_forward (bounded)")
+    if wcache is not None:
+        wcache["valid"] = True                              # (only once the call that derives it has succeeded)
     return out, (dims, graph, box["ws"])
 
 
@@ -496,9 +497,13 @@ class _FusedMPNN(torch.nn.Module):
     cache_weights = True
 
     def _cache_key(self, params):
+        # every run-time switch the derivation reads: bf3_prepare writes the max |W| cells only with fp16x2 AND the
+        # pipelined kernel (gi_b3p_enable), the chains' weight guard runs only with the guard on.  GI_CHAIN_X2 and
+        # GI_CHAIN_FWD_X2 are read once from the environment and fixed for the life of the process.
         lib = _L.load()
         return (_L.WEIGHTS_EPOCH[0], id(params), tuple((_ops._version(p), p.data_ptr()) for p in params),
-                self._x2_off(), lib.gi_bf3_enable(-1), lib.gi_x2_enable(-1))
+                self._x2_off(), bool(self.x2_guard), lib.gi_bf3_enable(-1), lib.gi_x2_enable(-1),
+                lib.gi_b3p_enable(-1))
 
     def _weights_cache(self, params, nodes):
         if not self.cache_weights or not nodes.is_cuda:
