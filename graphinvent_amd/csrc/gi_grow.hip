@@ -13,6 +13,12 @@
 // Workspace in desc.state: [0] n, [1] r, [2] target, [3] error (persistent); [4] go, [5] |S|, [6] |T \ {0}|,
 // [7] |T|, [8] new error bits (this round's); [GI_GROW_STATE_WORDS + g] = graph g's slot: k >= 0 at position k of
 // T \ {0}, -2 - k at position k of I \ {0}, -1 outside S.
+//
+// gi_grow_graphs_rl runs the same three launches with the RL fields of GrowArgs set: the prior's likelihood stream
+// beside the agent's (d.likelihoods / d.gen_likelihoods / d.likelihood), and the trajectory record of every generated
+// row (source graph, first and last round) from the per-graph start rounds in state[GI_GROW_STATE_WORDS + B + g].
+// gi_grow_traj_gather / gi_grow_traj_scatter rebuild the generated likelihood rows from the per-round likelihoods with
+// that record, and take the gradient back, for the autograd of the RL loop.
 #include "gi_common.h"
 
 namespace {
@@ -24,6 +30,12 @@ constexpr int SLOT_NONE = -1;
 struct GrowArgs {
     gi_grow_desc d;
     int A;                                   // add actions per node: prod(group) * Fe
+    // gi_grow_graphs_rl only (NULL in gi_grow_graphs): the prior's stream, the trajectory record, the start rounds
+    float* p_likelihoods;                    // [B, L]
+    float* p_gen;                            // [C, L]
+    const float* p_like;                     // [B]
+    int* traj;                               // [3, C]
+    int* start;                              // [B], in state
 };
 
 __device__ __forceinline__ long long node_off(const gi_grow_desc& d, int g) { return (long long)g * d.N * d.Fn; }
@@ -135,7 +147,24 @@ __global__ __launch_bounds__(APPLY_THREADS) void grow_apply_kernel(GrowArgs a) {
         for (int i = tid; i < NF; i += APPLY_THREADS) { gn[i] = nodes[i]; nodes[i] = 0.f; }
         for (int i = tid; i < NNF; i += APPLY_THREADS) { ge[i] = edges[i]; edges[i] = 0.f; }
         for (int j = tid; j < d.L; j += APPLY_THREADS) { gl[j] = j == r ? like : lrow[j]; lrow[j] = 0.f; }
-        if (tid == 0) { d.gen_n_nodes[row] = d.n_nodes[g]; d.n_nodes[g] = 0; }
+        if (a.p_likelihoods) {
+            const float plike = a.p_like[g];
+            float* prow = a.p_likelihoods + (long long)g * d.L;
+            float* pg = a.p_gen + row * d.L;
+            for (int j = tid; j < d.L; j += APPLY_THREADS) { pg[j] = j == r ? plike : prow[j]; prow[j] = 0.f; }
+        }
+        if (tid == 0) {
+            d.gen_n_nodes[row] = d.n_nodes[g];
+            d.n_nodes[g] = 0;
+            if (a.start) {                   // (only block g touches start[g])
+                if (a.traj) {
+                    a.traj[row] = g;
+                    a.traj[d.C + row] = a.start[g];
+                    a.traj[2LL * d.C + row] = r;
+                }
+                a.start[g] = r + 1;
+            }
+        }
         return;
     }
     // every other graph applies its action; graph 0 is then restored
@@ -163,11 +192,13 @@ __global__ __launch_bounds__(APPLY_THREADS) void grow_apply_kernel(GrowArgs a) {
         }
         d.n_nodes[g] = g == 0 ? 1 : (signed char)(nn + 1);       // :314 (graph 0: restored, :463)
         lrow[r] = like;                                           // :315
+        if (a.p_likelihoods) a.p_likelihoods[(long long)g * d.L + r] = a.p_like[g];
     } else if (kind == 1) {                                       // connect (:319-337)
         const int f = from < 0 ? from + N : from;                 // torch's wrap of -1
         edges[((long long)f * N + to) * Fe + rem] = 1.f;
         edges[((long long)to * N + f) * Fe + rem] = 1.f;
         lrow[r] = like;
+        if (a.p_likelihoods) a.p_likelihoods[(long long)g * d.L + r] = a.p_like[g];
     }
     if (g == 0) {
         edges[0] = 1.f;                                           // :462
@@ -194,10 +225,10 @@ __global__ __launch_bounds__(64) void grow_commit_kernel(int* state, int* host_s
 
 extern "C" int gi_grow_state_words(int B) { return B < 0 ? GI_EINVAL : GI_GROW_STATE_WORDS + B; }
 
-extern "C" int gi_grow_graphs(const gi_grow_desc* desc, void* stream) {
-    (void)hipGetLastError();
-    if (!desc) return GI_EINVAL;
-    const gi_grow_desc& d = *desc;
+namespace {
+
+// gi_grow_desc's checks; fills a (the RL fields NULL)
+int grow_args(const gi_grow_desc& d, GrowArgs& a) {
     if (d.B <= 0 || d.N <= 0 || d.Fn <= 0 || d.Fe <= 0 || d.L <= 0 || d.C <= 0) return GI_EINVAL;
     if (d.N > GI_MAX_NODES || d.n_groups < 1 || d.n_groups > GI_GROW_MAX_GROUPS) return GI_ELIMIT;
     if (!d.nodes || !d.edges || !d.n_nodes || !d.likelihoods || !d.gen_nodes || !d.gen_edges || !d.gen_n_nodes ||
@@ -212,12 +243,112 @@ extern "C" int gi_grow_graphs(const gi_grow_desc* desc, void* stream) {
     }
     if (sum != d.Fn) return GI_EINVAL;       // every add writes one feature per group: the groups tile the node row
     if ((long long)d.N * d.N * d.Fe > 0x7fffffffLL) return GI_ELIMIT;
-    GrowArgs a;
+    a = GrowArgs{};
     a.d = d;
     a.A = (int)A;
+    return 0;
+}
+
+int grow_launch(const GrowArgs& a, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(grow_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, a);
-    hipLaunchKernelGGL(grow_apply_kernel, dim3(d.B), dim3(APPLY_THREADS), 0, st, a);
-    hipLaunchKernelGGL(grow_commit_kernel, dim3(1), dim3(64), 0, st, d.state, d.host_state);
+    hipLaunchKernelGGL(grow_apply_kernel, dim3(a.d.B), dim3(APPLY_THREADS), 0, st, a);
+    hipLaunchKernelGGL(grow_commit_kernel, dim3(1), dim3(64), 0, st, a.d.state, a.d.host_state);
+    return gi_launch_status();
+}
+
+constexpr int TRAJ_THREADS = 256;
+
+// one workgroup per generated row k: gen[k, c] for every column c, both sides
+__global__ __launch_bounds__(TRAJ_THREADS) void traj_gather_kernel(int n, int R, int B, int C, int L,
+                                                                   const int* __restrict__ traj,
+                                                                   const float* __restrict__ like_a,
+                                                                   const float* __restrict__ like_p,
+                                                                   float* __restrict__ gen_a, float* __restrict__ gen_p) {
+    const int k = blockIdx.x;
+    int g = -1, lo = 1, hi = 0;
+    if (k < n) {
+        g = traj[k]; lo = traj[C + k]; hi = min(traj[2 * C + k], R - 1);
+        if (g < 0 || g >= B) lo = 1, hi = 0;                      // (never recorded so: nothing read out of range)
+    }
+    for (int c = threadIdx.x; c < L; c += TRAJ_THREADS) {
+        const bool in = c >= lo && c <= hi;
+        const long long src = (long long)c * B + g;
+        if (gen_a) gen_a[(long long)k * L + c] = in ? like_a[src] : 0.f;
+        if (gen_p) gen_p[(long long)k * L + c] = in ? like_p[src] : 0.f;
+    }
+}
+
+// one workgroup per round c: zero d[c, :], then every row covering c writes its (c, graph) element
+__global__ __launch_bounds__(TRAJ_THREADS) void traj_scatter_kernel(int n, int B, int C,
+                                                                    const int* __restrict__ traj,
+                                                                    const float* __restrict__ g_a, int ldg_a,
+                                                                    const float* __restrict__ g_p, int ldg_p,
+                                                                    float* __restrict__ d_a, float* __restrict__ d_p) {
+    const int c = blockIdx.x;
+    for (int g = threadIdx.x; g < B; g += TRAJ_THREADS) {
+        if (d_a) d_a[(long long)c * B + g] = 0.f;
+        if (d_p) d_p[(long long)c * B + g] = 0.f;
+    }
+    __syncthreads();                         // (the zeros are visible to the workgroup's own writes below)
+    for (int k = threadIdx.x; k < n; k += TRAJ_THREADS) {
+        const int g = traj[k];
+        if (g < 0 || g >= B || c < traj[C + k] || c > traj[2 * C + k]) continue;
+        if (d_a) d_a[(long long)c * B + g] = g_a[(long long)k * ldg_a + c];
+        if (d_p) d_p[(long long)c * B + g] = g_p[(long long)k * ldg_p + c];
+    }
+}
+
+}  // namespace
+
+extern "C" int gi_grow_graphs(const gi_grow_desc* desc, void* stream) {
+    (void)hipGetLastError();
+    if (!desc) return GI_EINVAL;
+    GrowArgs a;
+    const int rc = grow_args(*desc, a);
+    if (rc) return rc;
+    return grow_launch(a, stream);
+}
+
+extern "C" int gi_grow_rl_state_words(int B) { return B < 0 ? GI_EINVAL : GI_GROW_STATE_WORDS + 2 * B; }
+
+extern "C" int gi_grow_graphs_rl(const gi_grow_rl_desc* desc, void* stream) {
+    (void)hipGetLastError();
+    if (!desc) return GI_EINVAL;
+    GrowArgs a;
+    const int rc = grow_args(desc->base, a);
+    if (rc) return rc;
+    const int n_prior = !!desc->prior_likelihoods + !!desc->gen_prior_likelihoods + !!desc->prior_likelihood;
+    if (n_prior != 0 && n_prior != 3) return GI_EINVAL;
+    if ((long long)3 * desc->base.C > 0x7fffffffLL) return GI_ELIMIT;
+    a.p_likelihoods = desc->prior_likelihoods;
+    a.p_gen = desc->gen_prior_likelihoods;
+    a.p_like = desc->prior_likelihood;
+    a.traj = desc->traj;
+    a.start = desc->base.state + GI_GROW_STATE_WORDS + desc->base.B;
+    return grow_launch(a, stream);
+}
+
+extern "C" int gi_grow_traj_gather(int n, int R, int B, int C, int L, const int* traj, const float* like_a,
+                                   const float* like_p, float* gen_a, float* gen_p, void* stream) {
+    (void)hipGetLastError();
+    if (n < 0 || R < 0 || B <= 0 || C <= 0 || L <= 0 || n > C || R > L || !traj) return GI_EINVAL;
+    if (!gen_a != !like_a || !gen_p != !like_p || (!gen_a && !gen_p)) return GI_EINVAL;
+    if ((long long)3 * C > 0x7fffffffLL) return GI_ELIMIT;
+    hipLaunchKernelGGL(traj_gather_kernel, dim3(C), dim3(TRAJ_THREADS), 0, (hipStream_t)stream, n, R, B, C, L, traj,
+                       like_a, like_p, gen_a, gen_p);
+    return gi_launch_status();
+}
+
+extern "C" int gi_grow_traj_scatter(int n, int R, int B, int C, int L, const int* traj, const float* g_a, int ldg_a,
+                                    const float* g_p, int ldg_p, float* d_a, float* d_p, void* stream) {
+    (void)hipGetLastError();
+    if (n < 0 || R < 0 || B <= 0 || C <= 0 || L <= 0 || n > C || R > L || !traj) return GI_EINVAL;
+    if (!d_a != !g_a || !d_p != !g_p || (!d_a && !d_p)) return GI_EINVAL;
+    if ((d_a && ldg_a < L) || (d_p && ldg_p < L)) return GI_EINVAL;
+    if ((long long)3 * C > 0x7fffffffLL) return GI_ELIMIT;
+    if (R == 0) return 0;
+    hipLaunchKernelGGL(traj_scatter_kernel, dim3(R), dim3(TRAJ_THREADS), 0, (hipStream_t)stream, n, B, C, traj,
+                       g_a, ldg_a, g_p, ldg_p, d_a, d_p);
     return gi_launch_status();
 }

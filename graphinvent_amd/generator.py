@@ -13,6 +13,13 @@ that change nothing, so the host only has to look every few rounds.
 ``build_graphs(gen, constants.dim_f_add, constants.dim_f_conn)`` is the drop-in for ``gen.build_graphs()``; after it
 every tensor the reference's loop writes (``generated_*``, ``properly_terminated``, ``nodes``, ``edges``,
 ``n_nodes``, ``likelihoods``) holds what the reference leaves for the same draws.
+
+``build_graphs_rl(gen, constants.dim_f_add, constants.dim_f_conn)`` is the same for ``GraphGeneratorRL.build_graphs``
+(GraphGeneratorRL.py:109-172), with gradients: both models run with grad, ``sample_actions_rl``'s autograd Function
+draws, and ``gi_grow_graphs_rl`` carries both likelihood streams and records each generated row's trajectory (source
+graph, first and last round).  The generated likelihood rows are then rebuilt from the stacked per-round likelihoods
+by an autograd Function (``gi_grow_traj_gather`` forward, ``gi_grow_traj_scatter`` backward), so that
+``Workflow.compute_loss_component`` differentiates through every applied round into both models.
 """
 from __future__ import annotations
 
@@ -24,7 +31,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import lib as L
-from .sampler import _add_dims, sample_actions_raw
+from .sampler import _add_dims, _SampleRL, sample_actions_raw
 
 #: the generator tensors the step reads and writes, in gi_grow_desc's order, with their dtypes
 _STATE_TENSORS = (("nodes", torch.float32), ("edges", torch.float32), ("n_nodes", torch.int8),
@@ -33,11 +40,52 @@ _STATE_TENSORS = (("nodes", torch.float32), ("edges", torch.float32), ("n_nodes"
                   ("generated_likelihoods", torch.float32), ("properly_terminated", torch.int8))
 
 
-def new_state(batch_size: int, target: int, device) -> torch.Tensor:
-    """The step's device state: int32 [GI_GROW_STATE_WORDS + B], zero with ``state[2] = target``."""
-    state = torch.zeros(L.GROW_STATE_WORDS + batch_size, dtype=torch.int32, device=device)
+def new_state(batch_size: int, target: int, device, rl: bool = False) -> torch.Tensor:
+    """The step's device state: int32 [GI_GROW_STATE_WORDS + B] (``rl``: + 2 B, ``gi_grow_rl_state_words``), zero
+    with ``state[2] = target``."""
+    words = L.GROW_STATE_WORDS + (2 if rl else 1) * batch_size
+    state = torch.zeros(words, dtype=torch.int32, device=device)
     state.narrow(0, 2, 1).fill_(int(target))          # a fill launch: no host -> device copy
     return state
+
+
+def _validate(t: dict, dim_f_add: Sequence[int], dim_f_conn: Sequence[int]):
+    """What gi_grow_desc needs of the generator tensors ``t`` (dtypes, layout, shapes, one CUDA device); returns
+    ``(B, N, Fn, Fe, L, C)``, the add's sub-dimensions and its node-feature groups."""
+    nodes, edges = t["nodes"], t["edges"]
+    for name, dtype in _STATE_TENSORS:
+        x = t[name]
+        if x.dtype != dtype:
+            raise TypeError(f"{name} must be {dtype} (the reference's dtype), got {x.dtype}")
+        if not x.is_contiguous():
+            raise ValueError(f"{name} must be contiguous: the step writes it in place")
+    if nodes.dim() != 3 or edges.dim() != 4:
+        raise ValueError("nodes must be [B, N, Fn] and edges [B, N, N, Fe]")
+    B, N, Fn = nodes.shape
+    Fe = edges.shape[3]
+    sub, _ = _add_dims(edges, dim_f_add, dim_f_conn)
+    groups = sub[:-1]
+    if sub[-1] != Fe or not groups or len(groups) > L.GROW_MAX_GROUPS or sum(groups) != Fn:
+        raise ValueError(f"dim_f_add {list(dim_f_add)} does not match nodes {tuple(nodes.shape)} / edges "
+                         f"{tuple(edges.shape)}: the add's node-feature groups must tile Fn, bond type last")
+    Lc = t["likelihoods"].shape[1] if t["likelihoods"].dim() == 2 else -1
+    Cg = t["generated_nodes"].shape[0]
+    want = {"edges": (B, N, N, Fe), "n_nodes": (B,), "likelihoods": (B, Lc),
+            "generated_nodes": (Cg, N, Fn), "generated_edges": (Cg, N, N, Fe), "generated_n_nodes": (Cg,),
+            "generated_likelihoods": (Cg, Lc), "properly_terminated": (Cg,)}
+    for name, shape in want.items():
+        if tuple(t[name].shape) != shape:
+            raise ValueError(f"{name} has shape {tuple(t[name].shape)}, expected {shape}")
+    if Lc < 1 or Cg < 1:
+        raise ValueError("the likelihood and generated buffers must not be empty")
+    for name, _ in _STATE_TENSORS:
+        x = t[name]
+        if not x.is_cuda:
+            raise RuntimeError(f"grow_step needs CUDA (ROCm) tensors ({name} is on {x.device}): the MI355X HIP "
+                               "path has no CPU fallback")
+        if x.device != nodes.device:
+            raise ValueError(f"{name} is on {x.device}, nodes on {nodes.device}")
+    return (B, N, Fn, Fe, Lc, Cg), sub, groups
 
 
 class _Grower:
@@ -45,39 +93,8 @@ class _Grower:
 
     def __init__(self, t: dict, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], state: torch.Tensor,
                  host_state: Optional[int] = None):
-        nodes, edges = t["nodes"], t["edges"]
-        for name, dtype in _STATE_TENSORS:
-            x = t[name]
-            if x.dtype != dtype:
-                raise TypeError(f"{name} must be {dtype} (the reference's dtype), got {x.dtype}")
-            if not x.is_contiguous():
-                raise ValueError(f"{name} must be contiguous: the step writes it in place")
-        if nodes.dim() != 3 or edges.dim() != 4:
-            raise ValueError("nodes must be [B, N, Fn] and edges [B, N, N, Fe]")
-        B, N, Fn = nodes.shape
-        Fe = edges.shape[3]
-        sub, _ = _add_dims(edges, dim_f_add, dim_f_conn)
-        groups = sub[:-1]
-        if sub[-1] != Fe or not groups or len(groups) > L.GROW_MAX_GROUPS or sum(groups) != Fn:
-            raise ValueError(f"dim_f_add {list(dim_f_add)} does not match nodes {tuple(nodes.shape)} / edges "
-                             f"{tuple(edges.shape)}: the add's node-feature groups must tile Fn, bond type last")
-        Lc = t["likelihoods"].shape[1] if t["likelihoods"].dim() == 2 else -1
-        Cg = t["generated_nodes"].shape[0]
-        want = {"edges": (B, N, N, Fe), "n_nodes": (B,), "likelihoods": (B, Lc),
-                "generated_nodes": (Cg, N, Fn), "generated_edges": (Cg, N, N, Fe), "generated_n_nodes": (Cg,),
-                "generated_likelihoods": (Cg, Lc), "properly_terminated": (Cg,)}
-        for name, shape in want.items():
-            if tuple(t[name].shape) != shape:
-                raise ValueError(f"{name} has shape {tuple(t[name].shape)}, expected {shape}")
-        if Lc < 1 or Cg < 1:
-            raise ValueError("the likelihood and generated buffers must not be empty")
-        for name, _ in _STATE_TENSORS:
-            x = t[name]
-            if not x.is_cuda:
-                raise RuntimeError(f"grow_step needs CUDA (ROCm) tensors ({name} is on {x.device}): the MI355X HIP "
-                                   "path has no CPU fallback")
-            if x.device != nodes.device:
-                raise ValueError(f"{name} is on {x.device}, nodes on {nodes.device}")
+        (B, N, Fn, Fe, Lc, Cg), sub, groups = _validate(t, dim_f_add, dim_f_conn)
+        nodes = t["nodes"]
         if state.dtype != torch.int32 or state.device != nodes.device or not state.is_contiguous() or \
                 state.numel() < L.GROW_STATE_WORDS + B:
             raise ValueError("state must be a contiguous int32 tensor of GI_GROW_STATE_WORDS + B words on the "
@@ -246,15 +263,247 @@ def build_graphs(gen, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], *, un
             del graph
             mirror.close()
     gen.generation_rounds = rounds
+    _raise_for_outcome("build_graphs", n, rounds, target, err, t["likelihoods"], uniforms)
+    return n
+
+
+def _raise_for_outcome(what: str, n: int, rounds: int, target: int, err: int, likelihoods: torch.Tensor,
+                       uniforms: Optional[torch.Tensor]) -> None:
+    """The reference's exceptions for a loop's final counters: IndexError past the last likelihood column,
+    RuntimeError for the other rejected states and for pinned uniforms that ran out."""
     if err & L.GROW_ERR_ROUND:
-        raise IndexError(f"build_graphs: generation round {rounds} has no likelihood column "
-                         f"(likelihoods has {t['likelihoods'].shape[1]})")
+        raise IndexError(f"{what}: generation round {rounds} has no likelihood column "
+                         f"(likelihoods has {likelihoods.shape[1]})")
     if err:
-        raise RuntimeError("build_graphs: the growth step rejected round %d: %s" % (rounds, ", ".join(
+        raise RuntimeError("%s: the growth step rejected round %d: %s" % (what, rounds, ", ".join(
             m for bit, m in ((L.GROW_ERR_CAPACITY, "more finished graphs than generated_* rows"),
                              (L.GROW_ERR_ACTION, "an action index out of range"),
                              (L.GROW_ERR_NNODES, "n_nodes overflows int8")) if err & bit)))
     if n < target:
-        raise RuntimeError(f"build_graphs: the {uniforms.shape[0]} rows of uniforms ran out after {rounds} rounds "
+        raise RuntimeError(f"{what}: the {uniforms.shape[0]} rows of uniforms ran out after {rounds} rounds "
                            f"with {n} of {target} graphs generated")
+
+
+# ---- RL fine-tuning (GraphGeneratorRL.build_graphs) ----------------------------------------------------------------
+
+def _tensors_rl(gen) -> dict:
+    """GraphGeneratorRL's tensors under gi_grow_desc's names (the agent's likelihood stream as the base one)."""
+    t = {name: getattr(gen, name) for name, _ in _STATE_TENSORS
+         if name not in ("likelihoods", "generated_likelihoods")}
+    t["likelihoods"], t["generated_likelihoods"] = gen.agent_likelihoods, gen.generated_agent_likelihoods
+    return t
+
+
+def _validate_rl(t: dict, prior: Sequence[torch.Tensor], dim_f_add: Sequence[int], dim_f_conn: Sequence[int]):
+    """_validate with the prior's (likelihoods, generated_likelihoods) checked like the agent's, in the same order
+    (dtypes and layout, shapes, then the device)."""
+    pairs = (("prior_likelihoods", prior[0], t["likelihoods"]),
+             ("generated_prior_likelihoods", prior[1], t["generated_likelihoods"]))
+    for name, x, _ in pairs:
+        if x.dtype != torch.float32:
+            raise TypeError(f"{name} must be torch.float32 (the reference's dtype), got {x.dtype}")
+        if not x.is_contiguous():
+            raise ValueError(f"{name} must be contiguous: the step writes it in place")
+    for name, x, like in pairs:
+        if x.shape != like.shape:
+            raise ValueError(f"{name} has shape {tuple(x.shape)}, expected {tuple(like.shape)}")
+    dims, sub, groups = _validate(t, dim_f_add, dim_f_conn)
+    for name, x, like in pairs:
+        if x.device != like.device:
+            raise ValueError(f"{name} is on {x.device}, the agent's on {like.device}")
+    return dims, sub, groups
+
+
+class _GrowerRL(_Grower):
+    """Validated gi_grow_rl_desc: the agent's stream in ``t``, the prior's in ``prior`` (likelihoods, generated
+    likelihoods), the trajectory record in ``traj`` (int32 [3, C] or None)."""
+
+    def __init__(self, t: dict, prior: Sequence[torch.Tensor], traj: Optional[torch.Tensor],
+                 dim_f_add: Sequence[int], dim_f_conn: Sequence[int], state: torch.Tensor,
+                 host_state: Optional[int] = None):
+        (B, _, _, _, _, Cg), _, _ = _validate_rl(t, prior, dim_f_add, dim_f_conn)
+        super().__init__(t, dim_f_add, dim_f_conn, state, host_state)
+        if state.numel() < L.GROW_STATE_WORDS + 2 * B:
+            raise ValueError("state must hold gi_grow_rl_state_words(B) = GI_GROW_STATE_WORDS + 2 B words "
+                             "(generator.new_state(..., rl=True))")
+        if traj is not None and (traj.dtype != torch.int32 or tuple(traj.shape) != (3, Cg) or
+                                 not traj.is_contiguous() or traj.device != self.device):
+            raise ValueError(f"traj must be a contiguous int32 [3, {Cg}] tensor on {self.device}")
+        self.prior, self.traj = prior, traj
+        d = L.GrowRlDesc()
+        d.base = self.desc
+        d.prior_likelihoods, d.gen_prior_likelihoods = prior[0].data_ptr(), prior[1].data_ptr()
+        d.traj = traj.data_ptr() if traj is not None else None
+        self.desc_rl = d
+
+    def step(self, action: torch.Tensor, like_agent: torch.Tensor, like_prior: torch.Tensor,
+             flags: torch.Tensor) -> None:
+        B = self.B
+        for name, x, shape, dtype in (("action", action, (B, 4), torch.int32),
+                                      ("like_agent", like_agent, (B,), torch.float32),
+                                      ("like_prior", like_prior, (B,), torch.float32),
+                                      ("flags", flags, (B,), torch.int32)):
+            if not x.is_cuda or x.device != self.device:
+                raise RuntimeError(f"grow_step_rl: {name} must be a CUDA tensor on {self.device}")
+            if x.dtype != dtype or tuple(x.shape) != shape or not x.is_contiguous():
+                raise ValueError(f"grow_step_rl: {name} must be contiguous {dtype} {shape} "
+                                 "(gi_sample_actions_rl's output)")
+        d = self.desc_rl
+        d.base.action, d.base.likelihood, d.base.flags = action.data_ptr(), like_agent.data_ptr(), flags.data_ptr()
+        d.prior_likelihood = like_prior.data_ptr()
+        with torch.cuda.device(self.device):
+            L.check(L.load().gi_grow_graphs_rl(C.byref(d), torch.cuda.current_stream(self.device).cuda_stream),
+                    "gi_grow_graphs_rl")
+
+
+def grow_step_rl(nodes, edges, n_nodes, agent_likelihoods, prior_likelihoods, generated_nodes, generated_edges,
+                 generated_n_nodes, generated_agent_likelihoods, generated_prior_likelihoods, properly_terminated,
+                 action, like_agent, like_prior, flags, dim_f_add: Sequence[int], dim_f_conn: Sequence[int],
+                 state: torch.Tensor, traj: Optional[torch.Tensor] = None) -> None:
+    """One RL growth step (gi_grow_graphs_rl) on GraphGeneratorRL's tensors, in place, from
+    ``sample_actions_rl_raw``'s ``(action, like_agent, like_prior, flags)``.  ``state`` = ``new_state(..., rl=True)``;
+    ``traj`` (int32 [3, C], optional) receives each generated row's source graph, first and last round."""
+    L.load()
+    t = dict(nodes=nodes, edges=edges, n_nodes=n_nodes, likelihoods=agent_likelihoods,
+             generated_nodes=generated_nodes, generated_edges=generated_edges, generated_n_nodes=generated_n_nodes,
+             generated_likelihoods=generated_agent_likelihoods, properly_terminated=properly_terminated)
+    _GrowerRL(t, (prior_likelihoods, generated_prior_likelihoods), traj, dim_f_add, dim_f_conn,
+              state).step(action, like_agent, like_prior, flags)
+
+
+def traj_gather(like_agent: Optional[torch.Tensor], like_prior: Optional[torch.Tensor], traj: torch.Tensor, n: int,
+                L_cols: int):
+    """gi_grow_traj_gather: the generated likelihood rows [C, L_cols] of both sides from the per-round likelihoods
+    [R, B] (a side given as None is skipped and returned as None)."""
+    lib = L.load()
+    ref = like_agent if like_agent is not None else like_prior
+    R, B = ref.shape
+    Cg = traj.shape[1]
+    ins = [x.detach().float().contiguous() if x is not None else None for x in (like_agent, like_prior)]
+    outs = [torch.empty((Cg, L_cols), dtype=torch.float32, device=ref.device) if x is not None else None
+            for x in ins]
+    ptr = lambda x: x.data_ptr() if x is not None else None
+    with torch.cuda.device(ref.device):
+        L.check(lib.gi_grow_traj_gather(n, R, B, Cg, L_cols, traj.data_ptr(), ptr(ins[0]), ptr(ins[1]),
+                                        ptr(outs[0]), ptr(outs[1]), torch.cuda.current_stream(ref.device).cuda_stream),
+                "gi_grow_traj_gather")
+    return outs[0], outs[1]
+
+
+def traj_scatter(g_agent: Optional[torch.Tensor], g_prior: Optional[torch.Tensor], traj: torch.Tensor, n: int,
+                 R: int, B: int):
+    """gi_grow_traj_scatter: the gradients [R, B] of the per-round likelihoods from those of the generated rows
+    [C, L] (a side given as None is skipped and returned as None)."""
+    lib = L.load()
+    ref = g_agent if g_agent is not None else g_prior
+    Cg, L_cols = ref.shape
+    gs = [x.float().contiguous() if x is not None else None for x in (g_agent, g_prior)]
+    outs = [torch.empty((R, B), dtype=torch.float32, device=ref.device) if x is not None else None for x in gs]
+    ptr = lambda x: x.data_ptr() if x is not None else None
+    with torch.cuda.device(ref.device):
+        L.check(lib.gi_grow_traj_scatter(n, R, B, Cg, L_cols, traj.data_ptr(), ptr(gs[0]), L_cols, ptr(gs[1]),
+                                         L_cols, ptr(outs[0]), ptr(outs[1]),
+                                         torch.cuda.current_stream(ref.device).cuda_stream),
+                "gi_grow_traj_scatter")
+    return outs[0], outs[1]
+
+
+class _TrajGather(torch.autograd.Function):
+    """The generated likelihood rows of both sides as a differentiable function of the per-round likelihoods."""
+
+    @staticmethod
+    def forward(ctx, like_agent, like_prior, traj, n, L_cols):
+        ctx.set_materialize_grads(False)
+        gen_a, gen_p = traj_gather(like_agent, like_prior, traj, n, L_cols)
+        ctx.save_for_backward(traj)
+        ctx.n, ctx.RB = n, tuple(like_agent.shape)
+        for needs, out in zip(ctx.needs_input_grad[:2], (gen_a, gen_p)):
+            if not needs:
+                ctx.mark_non_differentiable(out)
+        return gen_a, gen_p
+
+    @staticmethod
+    def backward(ctx, g_agent, g_prior):
+        (traj,) = ctx.saved_tensors
+        g_a = g_agent if ctx.needs_input_grad[0] else None
+        g_p = g_prior if ctx.needs_input_grad[1] else None
+        if g_a is None and g_p is None:
+            return (None,) * 5
+        d_a, d_p = traj_scatter(g_a, g_p, traj, ctx.n, *ctx.RB)
+        return d_a, d_p, None, None, None
+
+
+def build_graphs_rl(gen, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], *,
+                    uniforms: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
+                    poll_every: int = 1) -> int:
+    """Drop-in for ``GraphGeneratorRL.build_graphs`` (GraphGeneratorRL.py:109-172): ``gen`` is the reference's RL
+    generator (duck-typed: ``agent_model``, ``prior_model``, ``batch_size`` and the tensors of its
+    ``allocate_graph_tensors`` / ``initialize_graph_batch``), mutated in place; returns ``n_generated_so_far`` and
+    sets ``gen.generation_rounds`` (rounds applied).
+
+    Every round runs both forwards with grad, ``sample_actions_rl``'s draw (no index tuples) and
+    ``gi_grow_graphs_rl``; nothing is read back inside a round but the forwards' own counts.
+    ``gen.generated_agent_likelihoods`` / ``gen.generated_prior_likelihoods`` are then REPLACED by the outputs of an
+    autograd Function over the stacked likelihoods of the applied rounds (rounds enqueued past the target are not in
+    the graph), with the values the step wrote in place; ``agent_likelihoods`` / ``prior_likelihoods`` hold their
+    values without an autograd graph.  ``uniforms``, ``generator`` and the exceptions are ``build_graphs``'.  The host
+    reads the mapped counters every ``poll_every`` rounds after waiting for the round ``poll_every - 1`` rounds back:
+    every round already waits for its forwards' counts, so the default 1 costs a short wait per round and enqueues
+    no round past the target (each would cost two forwards with grad); the result does not depend on it."""
+    if poll_every < 1:
+        raise ValueError("poll_every must be >= 1")
+    agent, prior, B = gen.agent_model, gen.prior_model, int(gen.batch_size)
+    t = _tensors_rl(gen)
+    prior_t = (gen.prior_likelihoods, gen.generated_prior_likelihoods)
+    _validate_rl(t, prior_t, dim_f_add, dim_f_conn)          # TypeError / ValueError / RuntimeError before any launch
+    dev = t["nodes"].device
+    if uniforms is not None:
+        if uniforms.dim() != 2 or uniforms.shape[1] != B:
+            raise ValueError(f"uniforms must be [R, {B}], got {tuple(uniforms.shape)}")
+        with _host_sync_allowed():
+            uniforms = uniforms.to(device=dev, dtype=torch.float32).contiguous()
+    Cg, L_cols = t["generated_likelihoods"].shape
+    state = new_state(B, B, dev, rl=True)
+    traj = torch.zeros((3, Cg), dtype=torch.int32, device=dev)
+    mirror = _HostMirror(B)
+    try:
+        grower = _GrowerRL(t, prior_t, traj, dim_f_add, dim_f_conn, state, mirror.dev.value)
+        nodes, edges, n_nodes, A = t["nodes"], t["edges"], t["n_nodes"], grower.A
+        stream = torch.cuda.current_stream(dev)
+        likes_a, likes_p = [], []
+        with torch.cuda.device(dev):
+            pending = collections.deque()
+            r = 0
+            while uniforms is None or r < uniforms.shape[0]:
+                u = uniforms[r] if uniforms is not None else torch.rand(B, device=dev, generator=generator)
+                action, like_a, like_p, flags = _SampleRL.apply(agent(nodes, edges), prior(nodes, edges), n_nodes,
+                                                                edges, A, u, None)
+                grower.step(action, like_a, like_p, flags)
+                likes_a.append(like_a)
+                likes_p.append(like_p)
+                r += 1
+                ev = torch.cuda.Event()
+                ev.record(stream)
+                pending.append(ev)
+                if r % poll_every == 0:
+                    with _host_sync_allowed():
+                        last = None
+                        while len(pending) > poll_every - 1:
+                            last = pending.popleft()
+                        if last is not None:
+                            last.synchronize()
+                    n, _, target, err = mirror.read()
+                    if n >= target or err:
+                        break
+            with _host_sync_allowed():
+                stream.synchronize()
+                n, rounds, target, err = (int(x) for x in state[:4].cpu())
+    finally:
+        with _host_sync_allowed():
+            mirror.close()
+    gen.generation_rounds = rounds
+    _raise_for_outcome("build_graphs_rl", n, rounds, target, err, t["likelihoods"], uniforms)
+    del likes_a[rounds:], likes_p[rounds:]               # frozen rounds leave the autograd graph with these
+    gen_a, gen_p = _TrajGather.apply(torch.stack(likes_a), torch.stack(likes_p), traj, n, L_cols)
+    gen.generated_agent_likelihoods, gen.generated_prior_likelihoods = gen_a, gen_p
     return n

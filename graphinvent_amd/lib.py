@@ -126,6 +126,12 @@ class GrowDesc(C.Structure):
                [(n, ci) for n in ("B", "N", "Fn", "Fe", "L", "C", "n_groups")] + [("group", ci * GROW_MAX_GROUPS)]
 
 
+class GrowRlDesc(C.Structure):
+    """gi_grow_rl_desc"""
+    _fields_ = [("base", GrowDesc)] + [(n, vp) for n in ("prior_likelihoods", "gen_prior_likelihoods",
+                                                         "prior_likelihood", "traj")]
+
+
 class DropoutParams(C.Structure):                       # gi_dropout_params
     _fields_ = [("seed", C.c_ulonglong), ("id", C.c_uint), ("thresh", C.c_uint),
                 ("a", C.c_float), ("b_keep", C.c_float), ("b_drop", C.c_float)]
@@ -198,6 +204,10 @@ SIGNATURES = {
     "gi_sample_likelihood_bwd": (ci, [ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp, ci, vp, vp, vp, ci, vp]),
     "gi_grow_state_words": (ci, [ci]),
     "gi_grow_graphs": (ci, [C.POINTER(GrowDesc), vp]),
+    "gi_grow_rl_state_words": (ci, [ci]),
+    "gi_grow_graphs_rl": (ci, [C.POINTER(GrowRlDesc), vp]),
+    "gi_grow_traj_gather": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]),
+    "gi_grow_traj_scatter": (ci, [ci, ci, ci, ci, ci, vp, vp, ci, vp, ci, vp, vp, vp]),
     "gi_side_stream_create": (ci, [C.POINTER(vp)]),
     "gi_side_stream_destroy": (ci, [vp]),
     "gi_ggnn_num_params": (ci, [C.POINTER(GgnnDims)]),

@@ -740,6 +740,44 @@ typedef struct gi_grow_desc {
 int gi_grow_state_words(int B);
 int gi_grow_graphs(const gi_grow_desc* desc, void* stream);
 
+/* Growth step of RL fine-tuning — one GraphGeneratorRL.build_graphs round after the draw (GraphGeneratorRL.py:109-172
+ * with apply_actions :227-380, copy_terminated_graphs :382-421 and reset_graphs :476-520), from
+ * gi_sample_actions_rl's action / like_agent / like_prior / flags.  base is gi_grow_graphs' descriptor with
+ * likelihoods / gen_likelihoods / likelihood = the agent's agent_likelihoods [B, L] / generated_agent_likelihoods
+ * [C, L] / like_agent [B]; the round is gi_grow_graphs' (same launches, slots, properly_terminated, dummy graph 0,
+ * error bits and freeze) with, in addition:
+ *   - the prior stream (prior_likelihoods, gen_prior_likelihoods, prior_likelihood: all three set or all NULL) gets
+ *     what the agent's does: written at column r by every applied add / connect and by the copy of S, copied to the
+ *     generated row, reset for S;
+ *   - start[g] = state[GI_GROW_STATE_WORDS + B + g] is the round in which graph g's current row began: 0 at first,
+ *     r + 1 after g is reset in round r;
+ *   - traj (NULL or [3, C] ints): the copy of graph g in round r to generated row k writes traj[k] = g,
+ *     traj[C + k] = start[g], traj[2 C + k] = r.  Every graph other than 0 writes column r in every applied round
+ *     (its add or connect, or the copy of S) and a reset zeroes the whole row, so generated row k holds
+ *     like_c[traj[k]] (the round-c likelihood) at columns traj[C + k] .. traj[2 C + k] and 0 elsewhere.
+ * state = gi_grow_rl_state_words(B) ints (GI_GROW_STATE_WORDS + 2 B), zero-filled with state[2] = target. */
+typedef struct gi_grow_rl_desc {
+    gi_grow_desc base;                 /* the agent's stream and everything else */
+    float* prior_likelihoods;          /* [B, L] or NULL */
+    float* gen_prior_likelihoods;      /* [C, L] or NULL */
+    const float* prior_likelihood;     /* [B] or NULL (like_prior of gi_sample_actions_rl) */
+    int* traj;                         /* [3, C] or NULL: source graph, first and last round of each generated row */
+} gi_grow_rl_desc;
+int gi_grow_rl_state_words(int B);
+int gi_grow_graphs_rl(const gi_grow_rl_desc* desc, void* stream);
+
+/* The generated likelihood rows of a finished RL loop from the per-round likelihoods, and the backward of that map;
+ * both sides (agent a, prior p) in one launch each, a side with NULL pointers skipped.  like_* are [R, B] (row c =
+ * round c's like_agent / like_prior), traj is the [3, C] record of gi_grow_graphs_rl, n = rows generated.
+ *   gather:  gen[k, c] = like[c, traj[k]] for k < n and traj[C + k] <= c <= traj[2 C + k] (c < R), 0 elsewhere of
+ *            gen [C, L] (bit-identical to what gi_grow_graphs_rl wrote into gen_likelihoods);
+ *   scatter: d_like[c, traj[k]] = g[k * ldg + c] on the same index set, 0 elsewhere of d_like [R, B].  No two rows
+ *            share a (c, graph) pair: no atomics, every element written once. */
+int gi_grow_traj_gather(int n, int R, int B, int C, int L, const int* traj, const float* like_a,
+                        const float* like_p, float* gen_a, float* gen_p, void* stream);
+int gi_grow_traj_scatter(int n, int R, int B, int C, int L, const int* traj, const float* g_a, int ldg_a,
+                         const float* g_p, int ldg_p, float* d_a, float* d_p, void* stream);
+
 /* Optional per-launch timing for the benchmark's roofline leg: when enabled, every gi_gemm and
  * gi_seg_sum launch is bracketed by hipEvents on its stream.  gi_prof_collect blocks until the
  * recorded work finished and returns, per kernel family k (0 = GEMM, 1 = seg_sum): summed elapsed
