@@ -196,6 +196,7 @@ SIGNATURES = {
                           C.c_double, ci, vp]),
     "gi_kl_loss": (ci, [vp, ci, vp, ci, ci, ci, ci, vp, vp, ci, vp, vp]),
     "gi_scale_by_scalar": (ci, [vp, cll, vp, vp]),
+    "gi_eval_nll": (ci, [vp, ci, vp, ci, ci, ci, ci, vp, cll, cll, vp, vp, vp, vp]),
     "gi_prof_enable": (ci, [ci]),
     "gi_prof_collect": (ci, [vp, vp, vp, vp]),
     "gi_prof_pipes": (ci, [vp, vp, vp]),

@@ -651,6 +651,19 @@ int gi_adam_step(float* p, const float* g, float* m, float* v, long long n, doub
 int gi_kl_loss(const float* out, int ldo, const void* target, int tgt_dtype, int ldt, int B,
                int width, float* row_loss, float* d_out, int ldd, float* loss_mean, void* stream);
 
+/* Validation NLL of the correct actions, Analyzer.get_validation_likelihood (Analyzer.py:754-774), for one
+ * batch in two launches with no host read-back.  Per row b of out [B, width] (row stride ldo) and target
+ * [B, width] (GI_DTYPE, row stride ldt):
+ *   s_b = sum_j (t_j / T) * softmax(out_b)_j,  T = sum_j t_j   (linear space, the reference's element order)
+ * Rows whose s_b is NaN (T == 0, a NaN or +inf logit) are dropped; the others' -log(s_b) (+inf where s_b
+ * underflows) go to dst[start + rank] in row order.  Entries past the kept rows keep their contents.
+ * *n_structures += sum_b target[b, width-1] (every row, in a fixed order).  If the kept rows would run past
+ * dst_len, the batch writes and counts nothing and sets *err = 1; while *err != 0 every call is a no-op.
+ * ws: 2 B floats of workspace.  Deterministic (no atomics). */
+int gi_eval_nll(const float* out, int ldo, const void* target, int tgt_dtype, int ldt, int B, int width,
+                float* dst, long long dst_len, long long start, float* n_structures, int* err, float* ws,
+                void* stream);
+
 /* x[0:n] *= *scale with the scalar read on the device (the upstream gradient autograd hands to the
  * loss node: `loss.backward()` passes ones, RL-style callers pass a weight) — no host read-back. */
 int gi_scale_by_scalar(float* x, long long n, const float* scale, void* stream);
