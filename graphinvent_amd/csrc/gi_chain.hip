@@ -63,17 +63,9 @@ struct ChainArgs {
     // XCDs (private 4 MB L2 each).  Row blocks are sorted by bond type, and a block streams its TYPE's whole ~1 MB
     // weight image: in dispatch order every XCD's L2 sees all three images (3.5 MB + the activations: 17 % / 32 % of
     // the L2 requests of the fp32 / fp16x2 chain missed, profiles/r04/pmc_chain_kernels.txt); with the bijective remap
-    // of gi_gemm.hip one XCD walks CONSECUTIVE blocks, i.e. one or two types.  GI_CHAIN_XCD=0: dispatch order.
+    // of gi_gemm.hip one XCD walks CONSECUTIVE blocks, i.e. one or two types.
     int remap;
-    int dbg;                                // TIMING-ONLY lab switches of the fp16x2 kernel (GI_DBG_X2 bit mask; results wrong)
 };
-// The TIMING-ONLY lab switches (results wrong) exist in a lab build only (make EXTRA=-DGI_CHAIN_X2_LAB): release kernels
-// carry no such branches (round-5 advisor).
-#ifdef GI_CHAIN_X2_LAB
-#define CH_DBG(m) (args.dbg & (m))
-#else
-#define CH_DBG(m) 0
-#endif
 __device__ __forceinline__ int chain_block_id(const ChainArgs& a, int bid) {
     const int total = a.chain_off[a.nchains];
     if (!a.remap || (int)gridDim.x != total) return bid;
@@ -260,12 +252,6 @@ __global__ __launch_bounds__(512) void gi_chain_kernel(const ChainArgs args) {
         const int coff = col_ok ? 4 * col : 0x40000000;     // beyond any tile: dropped / reads 0
         float av[RB][16];
         const bool dselu = BWD && Ly.act != nullptr;
-        if (dselu && CH_DBG(1)) {
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) av[rb][r] = 1.f;
-        } else
         if (dselu) {
             const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
                 (void*)(Ly.act + (long long)r0 * Ly.ldact), 0, nrows * Ly.ldact * 4, 0x00020000);
@@ -735,13 +721,6 @@ __global__ __launch_bounds__(512) void gi_chain_x2_kernel(const ChainArgs args) 
         const gi_chain_layer& Ly = P.layer[l];
         const int col = wid * 32 + l31;
         const int coff = col < Ly.N ? 4 * col : 0x40000000;
-        if (CH_DBG(1)) {
-#pragma unroll
-            for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) av[rb][r] = 1.f;
-            return;
-        }
         const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
             (void*)(Ly.act + (long long)r0 * Ly.ldact), 0, nvalid * Ly.ldact * 4, 0x00020000);
 #pragma unroll
@@ -783,7 +762,7 @@ __global__ __launch_bounds__(512) void gi_chain_x2_kernel(const ChainArgs args) 
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __syncthreads();
         if (Ly.out_amax && tid == 0) cx_amax_publish_wg(wg_max_from_lds(), Ly.out_amax);   // for the stack's fp16x2 weight gradients
-        if (l + 1 < L && !CH_DBG(4)) {                  // next layer's A operand: split, in place
+        if (l + 1 < L) {                                // next layer's A operand: split, in place
             gx_scale(wg_max_from_lds(), sa, ia);
             // A lane holds ONE column of 16 rows per row block: written one by one that is 64 two-byte stores per
             // thread into 8 of the 32 banks (round 4: 45 % of the kernel's LDS cycles were bank conflicts).  Neighbouring
@@ -810,7 +789,6 @@ __global__ __launch_bounds__(512) void gi_chain_x2_kernel(const ChainArgs args) 
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the new planes are written (no barrier in the k loop)
         const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
             (void*)(Ly.out + (long long)r0 * ldo), 0, nvalid * ldo * 4, 0x00020000);
-        if (!CH_DBG(2))
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
@@ -891,7 +869,7 @@ __global__ __launch_bounds__(512) void gi_chain_x2_kernel(const ChainArgs args) 
         since_epi = __builtin_amdgcn_readfirstlane(since_epi + 1);
         dma_tile(s + 3);
         const int slot = s & (CX_RING - 1);
-        if (swid * 32 < __builtin_amdgcn_readfirstlane(lN) && !CH_DBG(8)) {
+        if (swid * 32 < __builtin_amdgcn_readfirstlane(lN)) {
             read_frags(slot, kt, af, bf);
             __builtin_amdgcn_sched_barrier(0);
             mma(af, bf);
@@ -899,10 +877,6 @@ __global__ __launch_bounds__(512) void gi_chain_x2_kernel(const ChainArgs args) 
         }
         kt = __builtin_amdgcn_readfirstlane(kt + 1);
         if (kt == __builtin_amdgcn_readfirstlane(nk)) {       // layer done
-            if (CH_DBG(16)) {                              // (lab: no epilogue at all)
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                __syncthreads();
-            } else
             epilogue(l);
             since_epi = 0;
             l = __builtin_amdgcn_readfirstlane(l + 1);
@@ -1080,7 +1054,7 @@ __global__ __launch_bounds__(512, DUAL ? 4 : 1) void gi_chain_x2r_kernel(const C
         // vmcnt arithmetic of the k loop assumes.
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         // Part two: the row's planes for the next layer (its own scale), its outputs
-        const bool more = l + 1 < L && !CH_DBG(8);      // (lab bit 8: no rewrite of the activation planes)
+        const bool more = l + 1 < L;
         if (more) {
             row_scale_from_lds(l31, sa, ia);
 #pragma unroll
@@ -1107,35 +1081,33 @@ __global__ __launch_bounds__(512, DUAL ? 4 : 1) void gi_chain_x2r_kernel(const C
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the new planes are written (the output tile is staged)
         if (Ly.out_amax && swid == 0 && lane == 0) cx_amax_publish_wg(blk_max, Ly.out_amax);
-        if (!CH_DBG(16)) {
-            if (DUAL) {                                      // the lane's 4 x 4 channels of its row straight to HBM
-                if (live) {
-                    float* orow = Ly.out + (long long)(r0 + l31) * ldo;
+        if (DUAL) {                                      // the lane's 4 x 4 channels of its row straight to HBM
+            if (live) {
+                float* orow = Ly.out + (long long)(r0 + l31) * ldo;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int c = nb + 8 * j;
-                        if (c + 3 < N) *reinterpret_cast<v4f_u*>(orow + c) = x[j];
-                        else {
-                            if (c < N) orow[c] = x[j].x;
-                            if (c + 1 < N) orow[c + 1] = x[j].y;
-                            if (c + 2 < N) orow[c + 2] = x[j].z;
-                        }
+                for (int j = 0; j < 4; ++j) {
+                    const int c = nb + 8 * j;
+                    if (c + 3 < N) *reinterpret_cast<v4f_u*>(orow + c) = x[j];
+                    else {
+                        if (c < N) orow[c] = x[j].x;
+                        if (c + 1 < N) orow[c + 1] = x[j].y;
+                        if (c + 2 < N) orow[c + 2] = x[j].z;
                     }
                 }
-            } else {                                         // whole rows: 16 lanes x 16 bytes per row, 4 passes over the 256 columns
-                const int row = tid >> 4, c0 = 4 * (tid & 15);
-                if (row < nvalid) {
-                    float* orow = Ly.out + (long long)(r0 + row) * ldo;
+            }
+        } else {                                         // whole rows: 16 lanes x 16 bytes per row, 4 passes over the 256 columns
+            const int row = tid >> 4, c0 = 4 * (tid & 15);
+            if (row < nvalid) {
+                float* orow = Ly.out + (long long)(r0 + row) * ldo;
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int c = c0 + 64 * q;
-                        const v4f v = *reinterpret_cast<const v4f*>(&Os[row * CR_OLD + c]);
-                        if (c + 3 < N) *reinterpret_cast<v4f_u*>(orow + c) = v;
-                        else {
-                            if (c < N) orow[c] = v.x;
-                            if (c + 1 < N) orow[c + 1] = v.y;
-                            if (c + 2 < N) orow[c + 2] = v.z;
-                        }
+                for (int q = 0; q < 4; ++q) {
+                    const int c = c0 + 64 * q;
+                    const v4f v = *reinterpret_cast<const v4f*>(&Os[row * CR_OLD + c]);
+                    if (c + 3 < N) *reinterpret_cast<v4f_u*>(orow + c) = v;
+                    else {
+                        if (c < N) orow[c] = v.x;
+                        if (c + 1 < N) orow[c + 1] = v.y;
+                        if (c + 2 < N) orow[c + 2] = v.z;
                     }
                 }
             }
@@ -1218,23 +1190,19 @@ __global__ __launch_bounds__(512, DUAL ? 4 : 1) void gi_chain_x2r_kernel(const C
         if (__builtin_amdgcn_readfirstlane(since_epi) < (DUAL ? 2 : 3)) { GI_CHAIN_WAIT(60); }
         else if (DUAL) { GI_CHAIN_WAIT(2); } else { GI_CHAIN_WAIT(4); }
         since_epi = __builtin_amdgcn_readfirstlane(since_epi + 1);
-        if (!DUAL && !CH_DBG(1)) dma_tile(s + 3);
+        if (!DUAL) dma_tile(s + 3);
         const int slot = s & (RING - 1);
         const bool active = swid * 32 < __builtin_amdgcn_readfirstlane(lN);
-        if (active && !CH_DBG(2)) read_frags(slot, kt);
+        if (active) read_frags(slot, kt);
         if (DUAL) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the fragments are in registers: the slot is free
-            if (!CH_DBG(1)) dma_tile(s + 2);
+            dma_tile(s + 2);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (active && !CH_DBG(4)) mma();
+        if (active) mma();
         __builtin_amdgcn_sched_barrier(0);
         kt = __builtin_amdgcn_readfirstlane(kt + 1);
         if (kt == __builtin_amdgcn_readfirstlane(nk)) {       // layer done
-            if (CH_DBG(32)) {                              // (lab: no epilogue at all)
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                __syncthreads();
-            } else
             epilogue(l);
             since_epi = 0;
             l = __builtin_amdgcn_readfirstlane(l + 1);
@@ -1392,11 +1360,6 @@ extern "C" int gi_mlp_chain(const gi_chain_params* chains, int nchains, void* st
             image_bytes += (long long)chains[c].ngroups * chain_tiles(chains[c]) * CH_TILE * 4;
         big = image_bytes > (4LL << 20) && 1.15 * gi_cdiv(blocks(2 * CH_ROWS), ncu) < 0.9 * rounds;
     }
-    {   // (measurement aid) GI_CHAIN_BWD64=1: 64-row blocks for the dZ chains of the message passes only — half the
-        // workgroups, so half the CUs stay free for the weight-gradient queue that runs beside every backward chain
-        static const bool bwd64 = getenv("GI_CHAIN_BWD64") && atoi(getenv("GI_CHAIN_BWD64"));
-        if (bwd64 && rows64 < 0 && chains[0].backward && blocks(CH_ROWS) >= ncu / 2) big = true;
-    }
     if (g_chain_cfg.tile_rows > 0) {                        // tests / measurements: force a height
         h = std::min(std::max(g_chain_cfg.tile_rows, CH_ROWS), CH_ROWS + CH_XMAX);
         big = false;
@@ -1437,13 +1400,7 @@ extern "C" int gi_mlp_chain(const gi_chain_params* chains, int nchains, void* st
     a.nchains = nchains;
     if (total == 0) return 0;
     a.trace = g_chain_cfg.trace;                            // per-workgroup timestamps (tools/trace_chain.py)
-    {
-        static const bool xcd = !(getenv("GI_CHAIN_XCD") && atoi(getenv("GI_CHAIN_XCD")) == 0);
-        a.remap = (xcd && !bounded && total >= 16) ? 1 : 0;
-#ifdef GI_CHAIN_X2_LAB      // (make EXTRA=-DGI_CHAIN_X2_LAB: the breakdowns of profiles/r05/x2_chain_breakdown.txt, x2r_chain_breakdown.txt; results WRONG with a mask)
-        a.dbg = getenv("GI_DBG_X2") ? atoi(getenv("GI_DBG_X2")) : 0;
-#endif
-    }
+    a.remap = (!bounded && total >= 16) ? 1 : 0;
     hipStream_t st = (hipStream_t)stream;
     GiProfScope prof(st, GI_PROF_GEMM | (x2 ? GI_PROF_PIPE_X2 : 0), flops);
     const dim3 grid(bounded ? std::min(total, ncu) : total), block(512);
@@ -1453,14 +1410,9 @@ extern "C" int gi_mlp_chain(const gi_chain_params* chains, int nchains, void* st
     // chain workgroups owning their CU).  One weight tile of look-ahead less costs nothing measurable alone;
     // the step gains 1.6 % (headline 2.312 / 2.332 -> 2.277 / 2.295 ms, ZINC shape 5.044 -> 4.957, ChEMBL shape
     // 3.854 -> 3.813; profiles/r03/chain_ring_ab.txt).  gi_mlp_chain_config(ring = 3): the three-slot ring.
-    // (measurement aid GI_CHAIN_RING3_SMALL=<n>: launches of at most n row blocks — the pass-0 rows: a dozen workgroups,
-    // pure weight-stream latency, nothing else wants the CUs' LDS — take the three-slot ring: one more tile in flight)
-    static const int ring3_small = getenv("GI_CHAIN_RING3_SMALL") ? atoi(getenv("GI_CHAIN_RING3_SMALL")) : 0;
-    const bool ring2 = !big && g_chain_cfg.ring != 3 && !(total <= ring3_small);
+    const bool ring2 = !big && g_chain_cfg.ring != 3;
     if (x2r) {
-        // more row blocks than CUs: two workgroups per CU (GI_CHAIN_X2R_DUAL=0 / 1: never / always — measurements)
-        static const int dual_env = getenv("GI_CHAIN_X2R_DUAL") ? atoi(getenv("GI_CHAIN_X2R_DUAL")) : -1;
-        const bool dual = dual_env >= 0 ? dual_env != 0 : total > ncu;
+        const bool dual = total > ncu;                     // more row blocks than CUs: two workgroups per CU
         const dim3 gridx(bounded ? std::min(total, dual ? 2 * ncu : ncu) : total);
         if (chains[0].backward) {
             if (dual) hipLaunchKernelGGL((gi_chain_x2r_kernel<true, true>), gridx, block, 0, st, a);

@@ -13,17 +13,10 @@
 // 2.04e-7, mean signed error -6.4e-9; with the first-order correction of rounds 2-5 — the product's rounding error and
 // the low part of log2(e) folded back in, three more instructions — 1.93e-7 and -7.0e-9: the same).  Round 6 dropped the
 // correction: 60 -> 48 cycles per value in every forward epilogue of the path, headline step -0.75 %
-// (profiles/r06/ab_head_selu_bare_exp.txt).  -DGI_EXP_CORRECTED brings it back.  (libm expf costs ~25 VALU instructions.)
+// (profiles/r06/ab_head_selu_bare_exp.txt; the corrected form is in the git history).  (libm expf costs ~25 VALU instructions.)
 __device__ __forceinline__ float gi_exp_nonpos(float x) {
     const float l2e_hi = 1.44269502162933349609375f;
-#ifdef GI_EXP_CORRECTED
-    const float l2e_lo = 1.925963033500011e-8f;
-    const float t = x * l2e_hi;
-    const float r = fmaf(x, l2e_hi, -t) + x * l2e_lo;          // (exact product - t) + low part
-    return __builtin_amdgcn_exp2f(t) * fmaf(r, 0.693147182464599609375f, 1.f);
-#else
     return __builtin_amdgcn_exp2f(x * l2e_hi);
-#endif
 }
 // SELU as torch.nn.SELU (gnn/modules.py:126,164): scale * (x > 0 ? x : alpha * (exp(x) - 1)) —
 // the same exp(x) - 1 form ATen's CPU/GPU elu kernels evaluate.
@@ -78,21 +71,6 @@ extern "C" int gi_b3p_enable(int on);
 // GI_GEMM_LOG line of a launch (gi_gemm.hip); cls: two characters, "00" forward / "01" dgrad / "11" wgrad layouts,
 // "b0" / "b1" the bf16x3 launches of the forward / dgrad
 void gi_gemm_log_launch(const char* cls, const gi_gemm_params* probs, int n, int blocks, double flops);
-
-// ---- bias-gradient column of weight-gradient slabs, computed on its own (gi_ops.hip) ---------------------------------
-// A weight-gradient GEMM [dW | db] = dZ^T [X | 1] carries the bias gradient as an extra "ones" column: n_in + 1 output
-// columns.  When n_in is a multiple of the 64-wide tile that one column costs a whole extra column of tiles (129 -> 3
-// tiles instead of 2: the GRU projections, every stack's first layer at H = 128).  Such problems run as plain
-// n_out x n_in GEMMs and this launch writes column `col` of their slabs: slab s of a problem gets the column sums of dZ
-// over the s-th of `nsplit` equal row chunks (fixed order: deterministic), so the slab reduction finds db as before.
-struct GiBiasSlab {
-    const float* dZ; int lddz;           // [rows, n_out] row-major
-    const int* grp_off; int g;           // rows [grp_off[g], grp_off[g + 1]) on the device, or NULL: rows [0, rows)
-    int rows, n_out;
-    float* slab; long long stride;       // slab s at slab + s * stride, [n_out, ld]
-    int ld, col, nsplit;
-};
-int gi_bias_slabs(const GiBiasSlab* descs, int n, hipStream_t st);
 
 // ---- pass-0 row cache (gi_graph.p0_cache, gi_compact.hip): lookup before the pass-0 stack launch (words[0] =
 // hit flag, rows copied into m0 / e0 on a hit), insert after it (no-op on a hit).  nfam = 1 (message rows) or

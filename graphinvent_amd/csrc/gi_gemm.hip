@@ -723,12 +723,9 @@ static int launch_tiles(GemmBatch& b, double flops, hipStream_t st) {
         if ((b.p[i].flags & ~GI_GEMM_SPLITK) != own_epilogue(am, bm)) epi = 0;
     if (want_remap(b.total))
         for (int i = 0; i < b.n; ++i) b.p[i].flags |= 32;
-    {   // GI_WGRAD_SLAB_ORDER=0: split-K launches keep the per-slab order (measurement aid)
-        static const bool slab = !(getenv("GI_WGRAD_SLAB_ORDER") && atoi(getenv("GI_WGRAD_SLAB_ORDER")) == 0);
-        if (slab && b.total >= 64)
-            for (int i = 0; i < b.n; ++i)
-                if ((b.p[i].flags & GI_GEMM_SPLITK) && !b.p[i].m_dev) b.p[i].flags |= 2048;
-    }
+    if (b.total >= 64)                                  // split-K launches: slab-per-XCD tile order
+        for (int i = 0; i < b.n; ++i)
+            if ((b.p[i].flags & GI_GEMM_SPLITK) && !b.p[i].m_dev) b.p[i].flags |= 2048;
     int grid = b.total;
     // Bounded launches (rows counted on the device, m_dev): the grid would be sized for the BOUND and its surplus
     // workgroups, though they exit at once, are dispatched at the tail of the launch at the dispatcher's rate

@@ -511,8 +511,6 @@ bool gi_b3p_eligible(const gi_gemm_params* probs, int n) {
     // quantises badly below ~2.5 tiles per CU (measured at the headline batch, 348 tiles: 75 us against 70 us for the
     // three-workgroups-per-CU kernel of round 3; at 26 000 rows, 1 224 tiles: 225 against 244 us)
     if (!probs[0].a_major && tiles < 640 && !getenv("GI_B3P_ALL")) return false;
-    static const bool grouped_to_b3v = getenv("GI_B3V_GROUPED") && atoi(getenv("GI_B3V_GROUPED"));   // (measurement aid)
-    if (probs[0].a_major && probs[0].ngroups && grouped_to_b3v) return false;
     for (int i = 0; i < n; ++i) {
         const gi_gemm_params& p = probs[i];
         if (!(p.flags & GI_GEMM_BF3) || (p.flags & GI_GEMM_BF3A)) return false;
@@ -582,14 +580,11 @@ int gi_b3p_launch(const gi_gemm_params* probs, int n, void* stream) {
     bool bounded = false;
     for (int i = 0; i < k; ++i) bounded |= b.p[i].m_dev != nullptr;
     b.remap = (total >= 512 && !bounded && !am) ? 1 : 0;
-    {   // Weight-gradient launches (split-K slabs): consecutive tile ids are the column / row tiles of ONE slab, i.e. the
-        // workgroups that read the SAME rows of both operands — dealt round-robin to the 8 XCDs each of them pulls its
-        // 128 + 256 columns of those rows through a different L2 (2.5-3.1 x the operand bytes per launch through the
-        // fabric, profiles/r04).  With the bijective remap one XCD walks consecutive ids: a slab's tiles share an L2.
-        // GI_B3P_WGRAD_REMAP=0: dispatch order.
-        static const bool wremap = !(getenv("GI_B3P_WGRAD_REMAP") && atoi(getenv("GI_B3P_WGRAD_REMAP")) == 0);
-        if (am && wremap && !bounded && total >= 16) b.remap = 1;
-    }
+    // Weight-gradient launches (split-K slabs): consecutive tile ids are the column / row tiles of ONE slab, i.e. the
+    // workgroups that read the SAME rows of both operands — dealt round-robin to the 8 XCDs each of them pulls its
+    // 128 + 256 columns of those rows through a different L2 (2.5-3.1 x the operand bytes per launch through the
+    // fabric, profiles/r04).  With the bijective remap one XCD walks consecutive ids: a slab's tiles share an L2.
+    if (am && !bounded && total >= 16) b.remap = 1;
     hipStream_t st = (hipStream_t)stream;
     typedef void (*kern_t)(const GpBatch);
     kern_t fn;
@@ -621,10 +616,9 @@ int gi_b3p_launch(const gi_gemm_params* probs, int n, void* stream) {
         int dev = 0, cus = 0;
         (void)hipGetDevice(&dev);
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        const char* e = getenv("GI_B3P_STREAM");                  // 0: one workgroup per tile (measurement aid)
-        g_b3p_stream_cus = (e && atoi(e) == 0) ? 0 : cus;
+        g_b3p_stream_cus = cus;
     }
-    if (g_b3p_stream_cus > 0 && grid > g_b3p_stream_cus && !bounded) grid = g_b3p_stream_cus;
+    if (grid > g_b3p_stream_cus && !bounded) grid = g_b3p_stream_cus;
     hipLaunchKernelGGL(fn, dim3(grid), dim3(512), lds_bytes, st, b);
     return gi_launch_status();
 }

@@ -205,8 +205,7 @@ __global__ __launch_bounds__(512) void gru_fused_fwd_kernel(const GruArgs a) {
 
 // Can the fused kernel take this update?  (otherwise: the two-projection GEMM launch + gi_gru_gates_fwd)
 bool gi_gru_fused_ok(int H, int M, int lda, int ldh, int ldg) {
-    const bool on = !(getenv("GI_GRU_FUSED") && atoi(getenv("GI_GRU_FUSED")) == 0);     // (read per call: a test switches it mid-process)
-    return on && H >= 4 && M >= 4 && (H & 3) == 0 && (M & 3) == 0 && (lda & 3) == 0 && (ldh & 3) == 0 && ldh >= H &&
+    return H >= 4 && M >= 4 && (H & 3) == 0 && (M & 3) == 0 && (lda & 3) == 0 && (ldh & 3) == 0 && ldh >= H &&
            lda >= M && ldg >= 3 * H;
 }
 
@@ -221,18 +220,9 @@ int gi_gru_fused_fwd(const float* agg, int lda, const float* hx, int ldh, const 
     GruArgs a{agg, lda, hx, ldh, Wih, Whh, bih, bhh, gi, gh, ldg, hx_new, seg_off, rows, rows_dev, H, M};
     hipStream_t st = (hipStream_t)stream;
     GiProfScope prof(st, GI_PROF_GEMM, 2.0 * (double)rows * 3.0 * H * ((double)M + H));
-    // ONE workgroup per CU: the kernel is MFMA-bound with one wave per SIMD (four waves = four SIMDs), and the dispatcher
-    // packs two 37-KB workgroups onto one CU while others idle (measured: 35 us per launch as dispatched, see below) —
-    // unused dynamic LDS makes a second workgroup not fit.
-    static const int pad = getenv("GI_GRU_PAD_LDS") ? atoi(getenv("GI_GRU_PAD_LDS")) : 0;
-    static bool attr = false;
-    const int dyn = pad ? 48 * 1024 : 0;
-    if (pad && !attr) {
-        if (hipFuncSetAttribute((const void*)gru_fused_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, dyn) != hipSuccess)
-            return (int)hipGetLastError();
-        attr = true;
-    }
-    hipLaunchKernelGGL(gru_fused_fwd_kernel, dim3(gi_cdiv(rows, GU_TM), gi_cdiv(H, GU_TN)), dim3(512), dyn, st, a);
+    // (static LDS only: padding the launch with unused dynamic LDS to force one workgroup per CU was measured and not
+    // adopted, tools/experiments/README.md "Retired switches")
+    hipLaunchKernelGGL(gru_fused_fwd_kernel, dim3(gi_cdiv(rows, GU_TM), gi_cdiv(H, GU_TN)), dim3(512), 0, st, a);
     return gi_launch_status();
 }
 

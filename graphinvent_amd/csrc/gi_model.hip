@@ -182,17 +182,10 @@ bool bf3_enabled() {
 // 16-bit-pipe launches (GI_BF3, GI_X2) — the dZ chains of the BACKWARD only.  The forward keeps the fp32 chain: its
 // rows are bit-independent of one another, which the pass-0 row cache, the equality of blocking and host-sync-free
 // forwards and of forwards with and without a tape rely on (the fp16x2 chain scales activations per 64-row block, so a
-// row's last bits depend on its block).  GI_CHAIN_X2=0: the fp32-MFMA chain in the backward too.
-static bool chain_x2_enabled(bool call_x2) {
-    static const int v = getenv("GI_CHAIN_X2") ? atoi(getenv("GI_CHAIN_X2")) : 1;
-    return v != 0 && call_x2 && x2_enabled() && bf3_enabled();
-}
+// row's last bits depend on its block).
 // ... and, round 5, the FORWARD chains through the row-independent kernel (gi_chain_x2r_kernel: every row scaled by
-// itself, so the properties listed above hold bit for bit — tests/test_kernels_gpu.py).  GI_CHAIN_FWD_X2=0: fp32.
-static bool chain_fwd_x2_enabled(bool call_x2) {
-    static const int v = getenv("GI_CHAIN_FWD_X2") ? atoi(getenv("GI_CHAIN_FWD_X2")) : 1;
-    return v != 0 && chain_x2_enabled(call_x2);
-}
+// itself, so the properties listed above hold bit for bit — tests/test_kernels_gpu.py).
+static bool chain_x2_enabled(bool call_x2) { return call_x2 && x2_enabled() && bf3_enabled(); }
 bool bf3_wide(const Mlp& q, int l) { return q.fan_in(l) >= BF3_MIN_WIDTH && q.fan_out(l) >= BF3_MIN_WIDTH; }
 bool bf3_layer_ok(const Mlp& q, int l) { return bf3_enabled() && bf3_wide(q, l); }
 
@@ -363,7 +356,7 @@ void wcache_layout(const Model& m, Wc& c) {
 }
 
 // ---- wgrad slab plan ----------------------------------------------------------------------------
-struct SlabEntry { long long off, stride; int nsplit, calls, done, n_out, n_in, ld, tn, bidx, launched, reduced, bf3, single_last, sep, x2all; };   // x2all: fp16x2 launch when the call has (or can make) the operands' amax cells (plan_slabs)   // sep: bias column by gi_bias_slabs, reduced with the last batch   // single_last: the last call wrote ONE slab (the pass-0 rows, defer_wgrad)
+struct SlabEntry { long long off, stride; int nsplit, calls, done, n_out, n_in, ld, bidx, launched, reduced, bf3, single_last, x2all; };   // x2all: fp16x2 launch from the operands' published amax cells (plan_slabs)   // single_last: the last call wrote ONE slab (the pass-0 rows, defer_wgrad)
 struct SlabPlan {
     SlabEntry e[160];
     long long total;
@@ -396,99 +389,50 @@ int bf3_wgrad_nsplit(int red_rows, int decide_rows, int slab_rows = 0) {
 // largest magnitude of their operands (the stacks' activations and dZ, written by the chain kernels): the fp16x2 chain
 // kernels now publish them (gi_chain_layer.out_amax, gi_chain_params.x_amax) whenever BOTH directions of a stack run
 // on those kernels — 410 us of the 594-us weight-gradient queue that bounds the backward of the message passes
-// (profiles/r05) were these problems on the fp32 MFMA.  And every OTHER weight gradient too (wgrad_x2_all_possible):
-// operands without a publishing producer get their cell from gi_absmax (Run::AmaxPool).
+// (profiles/r05) were these problems on the fp32 MFMA.  Operands of round-4-rule problems without a publishing producer
+// (a wide first / last layer) get their cell from gi_absmax (Run::AmaxPool): fp16x2 instead of the spilling bf16x3
+// instantiation.  (Every other weight gradient on the 16-bit pipe too measured slower: tools/experiments/README.md.)
 // Their launches are a few dozen workgroups each (250 x 251 outputs = two 128 x 256 tiles per slab), i.e. latency-bound:
-// SHORT slabs (GI_MSG_SLAB_ROWS, default below) trade slab traffic for workgroups.  GI_MSG_WGRAD_X2=0 / GI_WGRAD_X2_ALL=0:
-// as before.
-constexpr int X2ALL_MIN_WIDTH = 32, X2ALL_MIN_ROWS = 512;
-// GI_P0_GRU_MAIN (default 1): pass 0's GRU weight gradients run in the main queue's last launch (gi_ggnn_backward_phase)
-bool p0_gru_on_main() {
-    static const int v = getenv("GI_P0_GRU_MAIN") ? atoi(getenv("GI_P0_GRU_MAIN")) : 1;
-    return v != 0;
-}
-int msg_slab_rows() {
-    static const int v = getenv("GI_MSG_SLAB_ROWS") ? std::max(64, atoi(getenv("GI_MSG_SLAB_ROWS"))) : 460;
-    return v;
-}
-int x2all_slab_rows(int decide_rows) { return decide_rows >= BF3_MIN_ROWS ? msg_slab_rows() : BF3_WGRAD_SHORT_SLAB_ROWS; }
-bool msg_wgrad_x2_possible(const Model& m, bool call_x2);
-// MEASURED (round 6, profiles/r06/ab_wgrad_x2_all.txt) AND NOT THE DEFAULT: with every weight gradient on the 16-bit pipe the
-// headline step is 2.02 ms against 1.886 (the 128 x 128-tile kernel; 2.04-2.06 through the pipelined one): a launch
-// of either kernel is >= 30 us whatever its size (per workgroup ~2 us per 32-deep k tile: the fp32 -> 2 x fp16 split is
-// VALU work the small problems cannot hide), and the operands' gi_absmax passes add 15-40 us per hand-over, while the
-// fp32 kernel runs the same small problems as 1 500 light workgroups.  What IS on by default: the stacks' hidden layers
-// through the chain kernels' cells (msg_wgrad_x2_possible, -0.8 %), and the pool for round-4-rule problems that lack a
-// producer's cell (a wide first / last layer: fp16x2 instead of the spilling bf16x3 instantiation).
-bool wgrad_x2_all_enabled() {
-    static const int v = getenv("GI_WGRAD_X2_ALL") ? atoi(getenv("GI_WGRAD_X2_ALL")) : 0;
-    return v != 0;
-}
+// SHORT slabs trade slab traffic for workgroups.
+constexpr int X2ALL_MIN_WIDTH = 32, X2ALL_MIN_ROWS = 512, MSG_SLAB_ROWS = 460;
+int x2all_slab_rows(int decide_rows) { return decide_rows >= BF3_MIN_ROWS ? MSG_SLAB_ROWS : BF3_WGRAD_SHORT_SLAB_ROWS; }
 bool wgrad_x2_pool_possible(const Model& m, bool call_x2) {
     return !m.d.dropout && call_x2 && x2_enabled() && bf3_enabled() && gi_b3p_enable(-1);
 }
-bool wgrad_x2_all_possible(const Model& m, bool call_x2) { return wgrad_x2_all_enabled() && wgrad_x2_pool_possible(m, call_x2); }
 bool msg_wgrad_x2_possible(const Model& m, bool call_x2) {
-    static const int v = getenv("GI_MSG_WGRAD_X2") ? atoi(getenv("GI_MSG_WGRAD_X2")) : 1;
-    return v != 0 && !m.mnn && !m.d.dropout && m.d.passes > 0 && chain_fwd_x2_enabled(call_x2) && gi_b3p_enable(-1) &&
+    return !m.mnn && !m.d.dropout && m.d.passes > 0 && chain_x2_enabled(call_x2) && gi_b3p_enable(-1) &&
            chain_fits(m.msg[0], m.d.H) && (m.d.kind != GI_KIND_ATTGGNN || chain_fits(m.eatt[0], m.d.H));
 }
 
-// The bias gradient as its own launch (GiBiasSlab, gi_common.h) when the "ones" column would start a new column of
-// 64-wide tiles: n_in % 64 == 0 (GRU projections and first layers at H = 128: 129 columns = 3 tiles for 2 tiles' worth
-// of work).  fp32-MFMA weight gradients only (the 16-bit-pipe kernel's 256-wide tiles hold 501 columns either way).
-// The bias columns of ALL such problems of a backward are written by ONE launch (two in the two-call backward) on the
-// weight-gradient queue, and their parameters are reduced with the last batch.
-// MEASURED AND NOT ADOPTED (default off; GI_WGRAD_BIAS=1 switches it on; tools/experiments/README.md): the tiles it
-// removes are worth ~60 us of weight-gradient kernel time per step, but one bias launch per hand-over (five per step,
-// ~10 us each beside the GEMMs) lost 30 us (1.955 against 1.923 ms), and the single launch ties (1.952-1.961 against
-// 1.945-1.964 ms; ZINC shape 4.06-4.09 against 4.09-4.11): more, smaller split-K slabs to write and reduce eat the rest.
-bool wgrad_sep_bias(int n_in) {
-    static const bool on = getenv("GI_WGRAD_BIAS") && atoi(getenv("GI_WGRAD_BIAS")) != 0;
-    return on && n_in >= 64 && (n_in & 63) == 0;
-}
-
-void wgrad_shape(int n_out, int n_in, int red_rows, double share, int& tn, int& nsplit) {
-    // 64x64 output tiles; 128x128 tiles for the big square weight gradients (a quarter of the slabs)
-    // measured slower: 2.73 against 2.64 ms per step (tools/experiments/README.md)
-    // (measurement aids, re-run in round 5: GI_WGRAD_TN=2 -> 128 x 128 tiles for problems of at least 192 x 192,
-    // GI_WGRAD_WGS=<n> -> workgroups per problem)
-    static const int env_tn = getenv("GI_WGRAD_TN") ? atoi(getenv("GI_WGRAD_TN")) : 1;
-    static const int env_wgs = getenv("GI_WGRAD_WGS") ? atoi(getenv("GI_WGRAD_WGS")) : 0;
-    tn = (env_tn == 2 && n_out >= 192 && n_in >= 192) ? 2 : 1;
-    if (env_tn == 12) tn = 12;                          // 64 x 128 tiles (tm = 1, tn = 2) for every problem
-    const int tiles = tn == 12 ? gi_cdiv(n_out, 64) * gi_cdiv(wgrad_sep_bias(n_in) ? n_in : n_in + 1, 128)
-                               : gi_cdiv(n_out, 64 * tn) * gi_cdiv(wgrad_sep_bias(n_in) ? n_in : n_in + 1, 64 * tn);
+// fp32-MFMA weight gradients: 64x64 output tiles (128x128 tiles for the big square problems measured slower: 2.73
+// against 2.64 ms per step, tools/experiments/README.md), split into slabs for ~192 workgroups per problem
+int wgrad_nsplit(int n_out, int n_in, int red_rows, double share) {
+    const int tiles = gi_cdiv(n_out, 64) * gi_cdiv(n_in + 1, 64);
     const int kt = gi_cdiv(std::max(red_rows, 1), 32);
     // workgroups per problem, measured in round 2: 96 -> 2.44-2.51 ms per step, 128 -> 2.39-2.40,
     // 192 -> 2.34-2.35, 256 -> 2.37, 384 -> 2.40-2.41
-    const double wgs = env_wgs > 0 ? (double)env_wgs : 192.0;
-    const int want = (int)(wgs * share / tiles + 0.5);
-    nsplit = std::min(std::max(want, 1), std::max(1, kt / 2));
+    const int want = (int)(192.0 * share / tiles + 0.5);
+    return std::min(std::max(want, 1), std::max(1, kt / 2));
 }
 
 void plan_slabs(const Model& m, int S, int E, const int* Et, SlabPlan& sp) {   // E, Et: message rows
     const gi_ggnn_dims& d = m.d;
     memset(&sp, 0, sizeof(sp));
     long long o = 0;
-    int maxEt = 0;
-    for (int t = 0; t < d.Fe; ++t) maxEt = std::max(maxEt, Et ? Et[t] : E);
-    // x2all (round 6): a problem the round-4 rule leaves on the fp32 MFMA becomes an fp16x2 launch of gi_b3p_kernel when
-    // the call can give both operands an amax cell (defer_wgrad; without them it runs on the fp32 MFMA with THIS plan's
-    // slab count).  Such launches are a few dozen 128 x 256-tile workgroups, i.e. latency-bound: SHORT slabs.
-    const bool allx = wgrad_x2_all_possible(m, x2_enabled());
+    // x2all (round 6): a hidden layer of a message / energy stack that the round-4 rule leaves on the fp32 MFMA becomes
+    // an fp16x2 launch of gi_b3p_kernel from the cells the fp16x2 chains publish (defer_wgrad).  Such launches are a few
+    // dozen 128 x 256-tile workgroups, i.e. latency-bound: SHORT slabs.
     auto add = [&](int widx, int bidx, int n_out, int n_in, int red, int calls, double share, bool bf3 = false,
-                   int decide_rows = -1, bool gathered = false, bool chain_cells = false) {
+                   int decide_rows = -1, bool chain_cells = false) {
         SlabEntry& e = sp.e[widx];
         e.bidx = bidx; e.launched = 0; e.reduced = 0;
         e.n_out = n_out; e.n_in = n_in; e.ld = gi_r4(n_in + 1); e.calls = calls; e.done = 0;
-        wgrad_shape(n_out, n_in, red, share, e.tn, e.nsplit);
+        e.nsplit = wgrad_nsplit(n_out, n_in, red, share);
         if (decide_rows < 0) decide_rows = red;
         e.bf3 = bf3 && !d.dropout && bf3_wgrad_ok(n_out, n_in, decide_rows);
         if (e.bf3) e.nsplit = bf3_wgrad_nsplit(red, decide_rows);
         e.x2all = 0;
-        if ((allx || chain_cells) && !e.bf3 && n_out >= X2ALL_MIN_WIDTH && n_in >= X2ALL_MIN_WIDTH && decide_rows >= X2ALL_MIN_ROWS &&
-            (!gathered || (allx && msg_wgrad_x2_possible(m, x2_enabled())))) {
+        if (chain_cells && !e.bf3 && n_out >= X2ALL_MIN_WIDTH && n_in >= X2ALL_MIN_WIDTH && decide_rows >= X2ALL_MIN_ROWS) {
             e.x2all = 1;
             e.nsplit = bf3_wgrad_nsplit(red, decide_rows, x2all_slab_rows(decide_rows));
         }
@@ -501,14 +445,12 @@ void plan_slabs(const Model& m, int S, int E, const int* Et, SlabPlan& sp) {   /
     auto add_mlp = [&](const Mlp& q, int red, int calls, double share = 1.0, bool bf3 = false, int decide_rows = -1,
                        bool stack = false) {
         for (int l = 0; l < q.layers(); ++l)
-            add(q.w(l), q.b(l), q.fan_out(l), q.fan_in(l), red, calls, share, bf3, decide_rows, stack && l == 0,
-                stack && l > 0 && msg_cells);
+            add(q.w(l), q.b(l), q.fan_out(l), q.fan_in(l), red, calls, share, bf3, decide_rows, stack && l > 0 && msg_cells);
     };
     const int R = S + 1;
     for (int t = 0; t < (m.mnn ? 0 : d.Fe); ++t) {   // (MNN: its message weight's gradient has slabs of its own, Ws.mslab)
         const int et = Et ? Et[t] : E / d.Fe;
-        static const int force_msg = getenv("GI_B3W_MSG") ? atoi(getenv("GI_B3W_MSG")) : -1;   // (measurement aid)
-        const bool m3 = force_msg >= 0 ? force_msg != 0 : E >= BF3_WGRAD_SMALL_MIN;
+        const bool m3 = E >= BF3_WGRAD_SMALL_MIN;
         add_mlp(m.msg[t], et, d.passes, E > 0 ? 1.5 * (double)et / E : 1.0, m3, E, true);
         if (d.kind == GI_KIND_ATTGGNN)
             add_mlp(m.eatt[t], et, d.passes, E > 0 ? 1.5 * (double)et / E : 1.0, m3, E, true);
@@ -518,8 +460,7 @@ void plan_slabs(const Model& m, int S, int E, const int* Et, SlabPlan& sp) {   /
     if (m.gather()) { add_mlp(m.att, R, 1, 1.0, true); add_mlp(m.emb, R, 1, 1.0, true); }
     add_mlp(m.add1, R, 1, 1.0, true);
     add_mlp(m.conn1, R, 1, 1.0, true);
-    static const int force_g = getenv("GI_B3W_G") ? atoi(getenv("GI_B3W_G")) : -1;             // (measurement aid)
-    const bool g3 = force_g >= 0 ? force_g != 0 : d.B >= BF3_WGRAD_SMALL_MIN / 4;
+    const bool g3 = d.B >= BF3_WGRAD_SMALL_MIN / 4;
     add_mlp(m.add2, d.B, 1, 1.0, g3); add_mlp(m.conn2, d.B, 1, 1.0, g3); add_mlp(m.term2, d.B, 1, 1.0, g3);
     sp.total = o;
 }
@@ -681,23 +622,11 @@ bool chain_fits(const Mlp& q, int dx_cols);
 void chain_fwd_params(gi_chain_params& c, const Run& r, float* ws, const Mlp* mlps, const Grp& g,
                       const float* X, int ldx, const int* idx, int rows, const long long* acts,
                       int ldh, float* final_dst, int ld_final);
-// Pass 0 has a few hundred distinct message rows (one per atom kind and bond type): its chain launch is a dozen
-// workgroups that each stream their bond type's whole ~1 MB weight image, 57 us forward and 125 us backward on the
-// critical path for next to no arithmetic (profiles/r04/x2/critical_path_amax_cells.txt).  Layer by layer the same rows
-// are 5 (4) grouped launches of a dozen 64 x 64 tiles: measured a tie in the forward (50 us), and in the backward the
-// four dgrad launches end 30-40 us before the chain would (they run beside pass 1's weight gradients either way).
-// GI_P0_LAYERWISE: bit 0 forward, bit 1 backward.  Default 0: with the pass-0 weight gradients in one slab the chain won the A/B at all three shapes (profiles/r04/p0).
-bool p0_layerwise(const Run& r, const Grp& g, int rows, bool backward) {
-    static const int v = getenv("GI_P0_LAYERWISE") ? atoi(getenv("GI_P0_LAYERWISE")) : 0;     // bit 0: forward, bit 1: backward
-    return (v & (backward ? 2 : 1)) && g.dim_slot == 2 && !r.dims && rows <= 2048;
-}
-
 void mlp_forward(Run& r, float* ws, const Mlp* mlps, const Grp& g, const float* X, int ldx,
                  const int* a_idx, int rows, const long long* acts, int ldh, float* final_dst,
                  int ld_final) {
     const int L = mlps[0].layers();
-    if (g.n && r.ok() && rows > 0 && r.img_f[mlps == r.eatt0 ? 1 : 0] && ldx >= gi_r4(mlps[0].in) &&
-        !p0_layerwise(r, g, rows, false)) {
+    if (g.n && r.ok() && rows > 0 && r.img_f[mlps == r.eatt0 ? 1 : 0] && ldx >= gi_r4(mlps[0].in)) {
         gi_chain_params c;                      // the whole stack in one resident-activation launch
         chain_fwd_params(c, r, ws, mlps, g, X, ldx, a_idx, rows, acts, ldh, final_dst, ld_final);
         r.chk(gi_mlp_chain(&c, 1, r.st));
@@ -765,12 +694,9 @@ struct Deferred {
     gi_gemm_params p[96];
     int widx[96][GI_MAX_GROUPS];     // weight indices each problem's slabs belong to
     int nw[96];
-    unsigned char sep_bias[96];      // the problem's bias-gradient column is written by gi_bias_slabs, not by a ones column
     unsigned char want_amax[96];     // fp16x2 problem whose a_amax (bit 0) / b_amax (bit 1) cell comes from the pool at launch time
-    GiBiasSlab bias[160];            // ... collected over the whole backward, launched once (flush_bias)
-    int nbias = 0;
     int n = 0;
-    gi_gemm_params& next() { gemm_defaults(p[n]); nw[n] = 0; sep_bias[n] = 0; want_amax[n] = 0; return p[n++]; }
+    gi_gemm_params& next() { gemm_defaults(p[n]); nw[n] = 0; want_amax[n] = 0; return p[n++]; }
 };
 
 void flush_batch(Run& r, Batch& b, bool wgrad) {
@@ -853,10 +779,10 @@ void add_dgrad(Batch& b, Run& r, int widx, int n_out, int n_in, int ncols, const
 void flush_deferred(Run& r, Deferred& q);
 void kick_deferred(Run& r, Deferred& q, SideStream* side, bool all);
 // queued weight-gradient problems that make up one hand-over to the side stream (one launch)
-inline int wgrad_kick_n() {
-    static const int n = [] { const char* e = getenv("GI_KICK_N"); const int v = e ? atoi(e) : 8; return (v >= 1 && v <= 8) ? v : 8; }();   // (measurement aid)
-    return n;
-}
+constexpr int WGRAD_KICK_N = 8;
+// node rows up to which no weight-gradient launch goes to the side stream beside the node-level dgrad launches
+// (Run::hold_kicks; measured in gi_ggnn_backward_phase)
+constexpr int HOLD_KICKS_MAX_ROWS = 9000;
 
 gi_reduce_desc reduce_desc(const SlabEntry& e, float* slabs, float* const* grads, int widx) {
     gi_reduce_desc q;
@@ -878,7 +804,7 @@ void defer_wgrad(Run& r, Deferred& q, SlabPlan& sp, float* slabs, const int* wid
     p.ones_col = e0.n_in;
     p.flags = GI_GEMM_SPLITK;
     p.nsplit = e0.nsplit; p.c_split_stride = e0.stride;
-    p.tm = e0.tn == 12 ? 1 : e0.tn; p.tn = e0.tn == 12 ? 2 : e0.tn;     // 1x1 (64x64 tiles) or 2x2 (128x128), see wgrad_shape
+    p.tm = 1; p.tn = 1;                            // 64x64 tiles (wgrad_nsplit)
     // The pass-0 rows (a few dozen per bond type, the stack's last call): ONE slab instead of the plan's nsplit — split
     // nine ways the launch was 2 200 workgroups that mostly store zeros, 50 us + their share of the final reduction
     // behind the last dZ chain with nothing left to overlap (profiles/r04/x2/critical_path_amax_cells.txt)
@@ -887,8 +813,8 @@ void defer_wgrad(Run& r, Deferred& q, SlabPlan& sp, float* slabs, const int* wid
     //   bf3   (the round-4 rule: node-level hidden layers, message / graph-level stacks of big batches): 16-bit pipe;
     //         fp16x2 when both operands have an amax cell — the producers' (node-level layers, the fp16x2 chains) or,
     //         round 6, one from the pool (Run::AmaxPool: gi_absmax in front of the launch) — else bf16x3;
-    //   x2all (round 6: everything else that is big enough): fp16x2 under the same condition, else the fp32 MFMA with
-    //         the plan's slab count.
+    //   x2all (round 6: the message / energy stacks' hidden layers): fp16x2 from the chains' cells, else the fp32 MFMA
+    //         with the plan's slab count.
     // A gathered B (the first layer of a message stack reads h[u_src]) needs published cells: the pool's gi_absmax
     // would measure rows the launch does not read.
     if ((e0.bf3 || e0.x2all) && !one_slab) {
@@ -897,28 +823,18 @@ void defer_wgrad(Run& r, Deferred& q, SlabPlan& sp, float* slabs, const int* wid
         if (!g.n && !(ca && cb))
             if (const Run::Bf3* e = r.bf3_layer(r.P[widx[0]], rows))
                 if (e->amax) { if (e->dz_ok) ca = e->amax + 2 * GI_AMAX_WORDS; if (e->in_ok) cb = e->amax + GI_AMAX_WORDS; }
-        const bool pool = r.wgrad_x2 && !b_idx && (e0.bf3 || wgrad_x2_all_enabled());
+        const bool pool = r.wgrad_x2 && !b_idx && e0.bf3;
         if ((ca && cb) || pool) {
             if (!b_idx || e0.x2all) {
                 p.flags |= GI_GEMM_BF3 | GI_GEMM_X2;
                 p.a_amax = ca; p.b_amax = cb;
                 q.want_amax[q.n - 1] = (ca ? 0 : 1) | (cb ? 0 : 2);
-                // which kernel: the pipelined 128 x 256 one (one workgroup per CU, ~30 us per launch whatever its size)
-                // for the big node-level problems, 128 x 128 tiles / 256 threads / 32 KB for the many small ones
-                // (GI_WGRAD_T128: 0 never, 1 the round-6 set, 2 every fp16x2 weight gradient)
-                static const int t128 = getenv("GI_WGRAD_T128") ? atoi(getenv("GI_WGRAD_T128")) : 0;
-                if (t128 == 2 || (t128 == 1 && !e0.bf3)) p.flags |= GI_GEMM_T128;
             }
         } else if (e0.bf3 && !b_idx) {
             p.flags |= GI_GEMM_BF3;
         }
     }
     const int slot = q.n - 1;
-    if (!(p.flags & GI_GEMM_BF3) && !one_slab && wgrad_sep_bias(e0.n_in)) {   // plain n_out x n_in problem; db by gi_bias_slabs
-        p.N = e0.n_in; p.ones_col = -1;                                  // (the pass-0 rows: a few dozen, one slab, keep the column)
-        q.sep_bias[slot] = 1;
-        for (int t = 0; t < (g.n ? g.n : 1); ++t) sp.e[widx[t]].sep = 1;
-    }
     if (g.n) {
         p.ngroups = g.n; p.grp_off = g.off;
         for (int t = 0; t < g.n; ++t) {
@@ -936,19 +852,7 @@ void defer_wgrad(Run& r, Deferred& q, SlabPlan& sp, float* slabs, const int* wid
         q.widx[slot][0] = widx[0];
         q.nw[slot] = 1;
     }
-    if (r.side && q.n >= wgrad_kick_n() && !r.hold_kicks) kick_deferred(r, q, r.side, false);
-}
-
-// one launch per tile class among (up to) 8 consecutive queued problems
-void launch_wgrad_batch(Run& r, const gi_gemm_params* p, int n, hipStream_t st) {
-    gi_gemm_params a[8], b[8];
-    int na = 0, nb = 0;
-    for (int i = 0; i < n; ++i) {
-        if (p[i].tm == 1) a[na++] = p[i];
-        else b[nb++] = p[i];
-    }
-    if (na && r.ok()) r.chk(gi_gemm_batch(a, na, st));
-    if (nb && r.ok()) r.chk(gi_gemm_batch(b, nb, st));
+    if (r.side && q.n >= WGRAD_KICK_N && !r.hold_kicks) kick_deferred(r, q, r.side, false);
 }
 
 // The amax cells the queued fp16x2 problems still lack (Deferred::want_amax): one cell of the pool per distinct operand
@@ -1003,33 +907,19 @@ void resolve_pool_amax(Run& r, gi_gemm_params* p, const unsigned char* want, int
 
 // consecutive queued problems, up to 8 per launch; the bf16x3 ones (one workgroup per CU, equal tiles) are packed
 // separately, biggest first, into launches of about one round of the device
-void launch_wgrad_batches(Run& r, Deferred& dq, const gi_gemm_params* p_in, const unsigned char* sep, int n, hipStream_t st) {
+void launch_wgrad_batches(Run& r, Deferred& dq, int n, hipStream_t st) {
     gi_gemm_params p[96];
-    for (int i = 0; i < n; ++i) p[i] = p_in[i];
+    for (int i = 0; i < n; ++i) p[i] = dq.p[i];
     resolve_pool_amax(r, p, dq.want_amax, n, st);
-    // b3[0]: bf16x3; fp16x2: b3[1 + 2 (128 x 128-tile kernel) + 1 (gathered B)] (a launch is ONE kernel instantiation)
-    gi_gemm_params rest[96], b3[5][96];
-    int nr = 0, n3[5] = {0, 0, 0, 0, 0};
-    GiBiasSlab* const bias = dq.bias;
-    int& nbias = dq.nbias;
+    // b3[0]: bf16x3; fp16x2: b3[1 + 1 (gathered B)] (a launch is ONE kernel instantiation)
+    gi_gemm_params rest[96], b3[3][96];
+    int nr = 0, n3[3] = {0, 0, 0};
     for (int i = 0; i < n; ++i) {
         if (p[i].flags & GI_GEMM_BF3) {
-            const int x = (p[i].flags & GI_GEMM_X2) ? 1 + ((p[i].flags & GI_GEMM_T128) ? 2 : 0) + (p[i].b_idx ? 1 : 0) : 0;
+            const int x = (p[i].flags & GI_GEMM_X2) ? 1 + (p[i].b_idx ? 1 : 0) : 0;
             b3[x][n3[x]++] = p[i];
         }
         else rest[nr++] = p[i];
-        if (sep && sep[i]) {                                      // bias-gradient column of this problem's slabs
-            const gi_gemm_params& q = p[i];
-            const int ng = q.ngroups ? q.ngroups : 1;
-            for (int g = 0; g < ng; ++g) {
-                if (nbias == 160) { r.chk(gi_bias_slabs(bias, nbias, st)); nbias = 0; }      // (very deep configurations only)
-                GiBiasSlab& b = bias[nbias++];
-                b.dZ = q.A; b.lddz = q.lda; b.grp_off = q.ngroups ? q.grp_off : nullptr; b.g = g;
-                b.rows = q.K; b.n_out = q.M;
-                b.slab = q.ngroups ? q.Cg[g] : q.C; b.stride = q.c_split_stride;
-                b.ld = q.ldc; b.col = q.N; b.nsplit = q.ngroups ? q.gsplit[g] : q.nsplit;
-            }
-        }
     }
     auto tiles = [](const gi_gemm_params& q) {
         int zs = q.nsplit;
@@ -1042,30 +932,22 @@ void launch_wgrad_batches(Run& r, Deferred& dq, const gi_gemm_params* p_in, cons
         if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c <= 0) c = 256;
         return c;
     }();
-    for (int x = 4; x >= 0; --x) {
+    for (int x = 2; x >= 0; --x) {
         gi_gemm_params* q = b3[x];
         for (int i = 1; i < n3[x]; ++i)                           // stable insertion sort, most tiles first
             for (int j = i; j > 0 && tiles(q[j]) > tiles(q[j - 1]); --j) std::swap(q[j], q[j - 1]);
-        const int cap = x >= 3 ? 1 << 30 : cus;                   // (the 128 x 128 kernel: several workgroups per CU, any size)
         for (int base = 0; base < n3[x] && r.ok();) {
             int k = 0, t = 0;
-            while (base + k < n3[x] && k < 8 && (k == 0 || t + tiles(q[base + k]) <= cap)) { t += tiles(q[base + k]); ++k; }
+            while (base + k < n3[x] && k < 8 && (k == 0 || t + tiles(q[base + k]) <= cus)) { t += tiles(q[base + k]); ++k; }
             r.chk(gi_gemm_batch(q + base, k, st));
             base += k;
         }
     }
-    for (int base = 0; base < nr && r.ok(); base += 8) launch_wgrad_batch(r, rest + base, std::min(8, nr - base), st);
-}
-
-// the bias-gradient columns of every problem launched so far without a ones column: one launch, on a stream that is
-// ordered behind their dZ (the stream of their weight-gradient GEMMs)
-void flush_bias(Run& r, Deferred& q, hipStream_t st) {
-    if (q.nbias && r.ok()) r.chk(gi_bias_slabs(q.bias, q.nbias, st));
-    q.nbias = 0;
+    for (int base = 0; base < nr && r.ok(); base += 8) r.chk(gi_gemm_batch(rest + base, std::min(8, nr - base), st));   // (64x64 tiles)
 }
 
 void flush_deferred(Run& r, Deferred& q) {
-    launch_wgrad_batches(r, q, q.p, q.sep_bias, q.n, r.st);
+    launch_wgrad_batches(r, q, q.n, r.st);
     q.n = 0;
 }
 
@@ -1100,13 +982,12 @@ struct SideStream {
 // launch every complete batch of 8 queued problems (all of them when `all`) on the side stream
 void kick_deferred(Run& r, Deferred& q, SideStream* side, bool all) {
     if (!side || !r.ok()) return;
-    const int kn = wgrad_kick_n();
-    const int n = all ? q.n : (q.n / kn) * kn;
+    const int n = all ? q.n : (q.n / WGRAD_KICK_N) * WGRAD_KICK_N;
     if (n == 0) return;
     hipEvent_t ready = side->next();
     r.chk((int)hipEventRecord(ready, r.st));
     r.chk((int)hipStreamWaitEvent(side->st, ready, 0));
-    launch_wgrad_batches(r, q, q.p, q.sep_bias, n, side->st);
+    launch_wgrad_batches(r, q, n, side->st);
     // parameters whose last slab has just been queued: reduce them right behind, on the side stream
     // too, so that only the final pass's gradients are left for the end of the backward
     gi_reduce_desc descs[96 * GI_MAX_GROUPS > 160 ? 160 : 96 * GI_MAX_GROUPS];
@@ -1114,7 +995,7 @@ void kick_deferred(Run& r, Deferred& q, SideStream* side, bool all) {
     for (int i = 0; i < n; ++i)
         for (int k = 0; k < q.nw[i]; ++k) {
             SlabEntry& e = r.sp->e[q.widx[i][k]];
-            if (++e.launched == e.calls && !e.reduced && !e.sep && nd < 160) {   // (sep: bias column still to come)
+            if (++e.launched == e.calls && !e.reduced && nd < 160) {
                 e.reduced = 1;
                 descs[nd++] = reduce_desc(e, r.slabs, r.grads, q.widx[i][k]);
             }
@@ -1123,7 +1004,6 @@ void kick_deferred(Run& r, Deferred& q, SideStream* side, bool all) {
     for (int i = n; i < q.n; ++i) {
         q.p[i - n] = q.p[i];
         q.nw[i - n] = q.nw[i];
-        q.sep_bias[i - n] = q.sep_bias[i];
         q.want_amax[i - n] = q.want_amax[i];
         for (int k = 0; k < q.nw[i]; ++k) q.widx[i - n][k] = q.widx[i][k];
     }
@@ -1223,7 +1103,7 @@ void msg_backward(Run& r, float* ws, SlabPlan& sp, float* slabs, Deferred& dq, c
                   float* dX, int lddx, int dx_cols, const SegIn* seg = nullptr) {
     const int L = mlps[0].layers();
     if (g.n && r.ok() && rows > 0 && r.img_b[mlps == r.eatt0 ? 1 : 0] && dx_cols == mlps[0].in &&
-        ldz >= gi_r4(mlps[0].out) && !p0_layerwise(r, g, rows, true)) {
+        ldz >= gi_r4(mlps[0].out)) {
         gi_chain_params c;                      // the whole dZ chain in one launch, then the wgrads
         seg_launch(r, seg, rows, mlps[0].out, const_cast<float*>(Zlast), ldz);
         if (chain_bwd_params(c, r, ws, mlps, g, Zlast, ldz, rows, acts, dzs, ldh, dX, lddx, dx_cols))
@@ -1254,15 +1134,10 @@ void msg_backward(Run& r, float* ws, SlabPlan& sp, float* slabs, Deferred& dq, c
 
 // ---- resident-activation chains (gi_chain.hip) ---------------------------------------------------
 // The per-bond-type message / energy stacks run as ONE launch per direction when every layer fits
-// the chain kernel (<= GI_CHAIN_MAXL layers, widths 4..GI_CHAIN_MAXW); GI_CHAIN=0 or wider stacks
-// take the layer-by-layer GEMM path above (same arithmetic, more launches).
-bool chain_enabled() {
-    static const bool v = !(getenv("GI_CHAIN") && atoi(getenv("GI_CHAIN")) == 0);
-    return v;
-}
-
+// the chain kernel (<= GI_CHAIN_MAXL layers, widths 4..GI_CHAIN_MAXW); wider stacks take the
+// layer-by-layer GEMM path above (same arithmetic, more launches).
 bool chain_fits(const Mlp& q, int dx_cols) {
-    if (!chain_enabled() || q.layers() > GI_CHAIN_MAXL) return false;
+    if (q.layers() > GI_CHAIN_MAXL) return false;
     for (int l = 0; l < q.layers(); ++l)
         if (q.fan_in(l) < 4 || q.fan_in(l) > GI_CHAIN_MAXW || q.fan_out(l) < 4 ||
             q.fan_out(l) > GI_CHAIN_MAXW)
@@ -1352,11 +1227,6 @@ int chain_bwd_params(gi_chain_params& c, const Run& r, float* ws, const Mlp* mlp
     c.image_stride = r.img_b_stride[mlps == r.eatt0 ? 1 : 0];
     c.X = Zlast; c.ldx = ldz; c.x_idx = nullptr; c.backward = 1;
     c.x2_wamax = r.chain_amax[mlps == r.eatt0 ? 1 : 0];
-    {   // (measurement aid) GI_CHAIN_BWD_X2R=1: the dZ chains through the row-independent kernel too (measured: +0.6 % at
-        // the headline batch, -0.7 % ZINC shape, +1.4 % ChEMBL shape; for the pass-0 rows only: ties — profiles/r05/ab)
-        static const bool bwd_x2r = getenv("GI_CHAIN_BWD_X2R") && atoi(getenv("GI_CHAIN_BWD_X2R"));
-        if (bwd_x2r && c.x2_wamax) c.x2_rows32 = 1;
-    }
     chain_groups(c, g, rows);
     float* const cells = (c.x2_wamax && g.dim_slot != 2) ? r.msg_cells[mlps == r.eatt0 ? 1 : 0] : nullptr;
     c.x_amax = msg_cell(cells, 1, L - 1);                   // Zlast = dZ of the last layer
@@ -1527,7 +1397,6 @@ extern "C" int gi_side_stream_create(void** out) {
     hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
     if (e != hipSuccess) return (int)e;
     hipStream_t st = nullptr;
-    if (getenv("GI_SIDE_PRIO") && atoi(getenv("GI_SIDE_PRIO")) == 0) least = (least + greatest) / 2;   // (measurement aid: not the lowest)
     e = hipStreamCreateWithPriority(&st, hipStreamNonBlocking, least);
     if (e != hipSuccess) return (int)e;
     *out = (void*)st;
@@ -1933,8 +1802,7 @@ static int mnn_backward(const Model& m, const float* const* params, const gi_gra
                        w.ldA, dh, w.ldH, d.H, false};
             jobs[1] = {&m.conn1, hxP, w.ldhx, R, w.conn1_act, w.ldM1, nullptr, 0, w.conn1_dz,
                        ws + w.conn1o, w.ldC, dhb, w.ldH, d.H, false};
-            static const int hold_env = getenv("GI_HOLD_KICKS") ? atoi(getenv("GI_HOLD_KICKS")) : -1;
-            r.hold_kicks = hold_env >= 0 ? hold_env != 0 : R <= 9000;
+            r.hold_kicks = R <= HOLD_KICKS_MAX_ROWS;
             mlp_jobs_backward(r, ws, sp, slabs, dq, jobs, 2);
             r.hold_kicks = false;
             if (r.side) kick_deferred(r, dq, r.side, false);
@@ -1948,7 +1816,6 @@ static int mnn_backward(const Model& m, const float* const* params, const gi_gra
         hipStream_t rst = r.side ? r.side->st : r.st;
         if (r.side) kick_deferred(r, dq, r.side, true);
         else flush_deferred(r, dq);
-        flush_bias(r, dq, rst);
         gi_reduce_desc descs[160];
         int nd = 0;
         readout_params([&](int widx) {
@@ -2012,11 +1879,9 @@ static int mnn_backward(const Model& m, const float* const* params, const gi_gra
     }
     if (r.side) {
         kick_deferred(r, dq, r.side, true);
-        flush_bias(r, dq, r.side->st);
         join_side(r, r.side);
     } else {
         flush_deferred(r, dq);
-        flush_bias(r, dq, r.st);
     }
     gi_reduce_desc descs[160];
     int nd = 0;
@@ -2101,7 +1966,7 @@ extern "C" int gi_ggnn_forward_ex(const gi_ggnn_dims* dp, const float* const* pa
     float* guard_cells[2] = {nullptr, nullptr};     // the forward chains' max |W| cells packed by this call
     for (int k = 0; k < (attn ? 2 : 1); ++k) {
         if (w.img_f_n[k] <= 0) continue;
-        const bool fx = !r.drop && chain_fwd_x2_enabled(r.x2);      // the row-independent fp16x2 chain, not the fp32 one
+        const bool fx = !r.drop && chain_x2_enabled(r.x2);      // the row-independent fp16x2 chain, not the fp32 one
         const bool cached = fx && wcache && wc.img_fx[k] >= 0;
         if (!chains_run && !(cached && !r.wc_valid)) continue;
         if (fx) {
@@ -2264,7 +2129,7 @@ extern "C" int gi_ggnn_forward_ex(const gi_ggnn_dims* dp, const float* const* pa
                                    ws + w.hx[p + 1], seg_off, R, r.dims, d.H, d.M, r.st));
             continue;
         }
-        // ... or (GI_GRU_FUSED=0, widths that are not multiples of 4): both input projections in one launch, then the gate kernel
+        // ... or (widths that are not multiples of 4): both input projections in one launch, then the gate kernel
         {
             Batch b;
             add_fwd(b, r, params[m.gru_wih], params[m.gru_bih], d.M, 3 * d.H, ws + w.agg[p], w.ldM, R,
@@ -2409,7 +2274,7 @@ extern "C" int gi_ggnn_backward_phase(const gi_ggnn_dims* dp, const float* const
     SlabPlan sp;
     plan_slabs(m, S, U, Ut, sp);
     Grp bytype0{d.Fe, gfix + L.type_off0, w.D0};
-    bytype0.dim_slot = 2;                                  // (marks the pass-0 rows: p0_layerwise)
+    bytype0.dim_slot = 2;                                  // (marks the pass-0 rows)
     Run r{(hipStream_t)stream, params, 0};
     r.drop = d.dropout != 0; r.seed = d.drop_seed; r.fshift = w.fshift;
     r.skinny = ws + w.skinny; r.skinny_floats = w.skinny_floats;
@@ -2521,9 +2386,7 @@ extern "C" int gi_ggnn_backward_phase(const gi_ggnn_dims* dp, const float* const
         // Round 5, with the backward bound by the weight-gradient queue: holding still wins at the headline batch
         // (7.3 k node rows: 1.935 against 1.944 ms) and loses from ~10 k rows on (B = 2000: 3.35 -> 3.24 ms, ZINC shape
         // 4.05 -> 4.00, ChEMBL shape 3.24 -> 3.21, B = 4000 a tie; profiles/r05/ab/ab_hold_kicks.txt).
-        // GI_HOLD_KICKS = 0 / 1 forces either.
-        static const int hold_env = getenv("GI_HOLD_KICKS") ? atoi(getenv("GI_HOLD_KICKS")) : -1;
-        r.hold_kicks = hold_env >= 0 ? hold_env != 0 : R <= 9000;
+        r.hold_kicks = R <= HOLD_KICKS_MAX_ROWS;
         mlp_jobs_backward(r, ws, sp, slabs, dq, jobs, 4);
         r.hold_kicks = false;
         if (r.side) kick_deferred(r, dq, r.side, false);
@@ -2534,8 +2397,7 @@ extern "C" int gi_ggnn_backward_phase(const gi_ggnn_dims* dp, const float* const
         // queued (side stream if there is one) so that the caller can start exchanging the gradients
         // of these parameters while the message passes are still being differentiated
         if (r.side) {
-            kick_deferred(r, dq, r.side, true);          // also reduces every finished parameter ...
-            flush_bias(r, dq, r.side->st);               // ... but those whose bias column comes from its own launch: now
+            kick_deferred(r, dq, r.side, true);          // also reduces every finished parameter
             gi_reduce_desc descs[160];
             int nd = 0;
             readout_params([&](int widx) {
@@ -2546,7 +2408,6 @@ extern "C" int gi_ggnn_backward_phase(const gi_ggnn_dims* dp, const float* const
             if (nd && r.ok()) r.chk(gi_reduce_slabs(descs, nd, r.side->st));
         } else {
             flush_deferred(r, dq);
-            flush_bias(r, dq, r.st);
             gi_reduce_desc descs[160];
             int nd = 0;
             readout_params([&](int widx) {
@@ -2594,10 +2455,10 @@ extern "C" int gi_ggnn_backward_phase(const gi_ggnn_dims* dp, const float* const
         }
         float* dagg = ws + w.dagg[p];
         // Pass 0 of the class-row path: the main queue has ~100 us of short launches left, the weight-gradient queue
-        // everything deferred so far.  GI_P0_GRU_MAIN (default 1): hand that over NOW and keep pass 0's own GRU weight
-        // gradients for the main queue's last launch (with the pass-0 message stack's), so that both queues end together.
-        if (p == 0 && w.D0 > 0 && r.side && p0_gru_on_main() && !r.p0_on_main) {
-            kick_deferred(r, dq, r.side, true); flush_bias(r, dq, r.side->st); r.hold_kicks = r.p0_on_main = true;
+        // everything deferred so far: hand that over NOW and keep pass 0's own GRU weight gradients for the main queue's
+        // last launch (with the pass-0 message stack's), so that both queues end together.
+        if (p == 0 && w.D0 > 0 && r.side) {
+            kick_deferred(r, dq, r.side, true); r.hold_kicks = r.p0_on_main = true;
         }
         {
             const int wih = m.gru_wih, whh = m.gru_whh;
@@ -2623,7 +2484,6 @@ extern "C" int gi_ggnn_backward_phase(const gi_ggnn_dims* dp, const float* const
                 {m.eatt, w.aact[p], w.adz[p], w.ldEa, ws + w.een[p], w.ldM,
                  p > 0 ? ws + w.dxa : nullptr}};
             if (p0) {   // per class row: sum over its (hundreds of) edge slots, both stacks in one launch
-                if (r.side && !r.p0_on_main) { kick_deferred(r, dq, r.side, true); flush_bias(r, dq, r.side->st); r.hold_kicks = r.p0_on_main = true; }
                 r.chk(gi_class_sum_dselu(ws + w.tmp_emb, ws + w.tmp_en, w.ldM, gp->cls_edges,
                                          gp->cls_off, w.D0, d.M, ws + w.m[p], ws + w.een[p], w.ldM,
                                          r.st));
@@ -2647,7 +2507,6 @@ extern "C" int gi_ggnn_backward_phase(const gi_ggnn_dims* dp, const float* const
         } else if (p == 0 && w.D0 > 0) {
             // pass 0: d m0 = selu'(m0) * (cmat^T . d agg): split-K over the R rows, slabs summed with
             // the SELU backward folded in; then the MLP backward on the D0 class rows (no d h needed)
-            if (r.side && !r.p0_on_main) { kick_deferred(r, dq, r.side, true); flush_bias(r, dq, r.side->st); r.hold_kicks = r.p0_on_main = true; }   // nothing queued waits for the pass-0 chain
             gi_gemm_params q;
             gemm_defaults(q);
             q.A = gp->cmat; q.lda = gp->ldc0; q.a_major = 1;
@@ -2692,15 +2551,12 @@ extern "C" int gi_ggnn_backward_phase(const gi_ggnn_dims* dp, const float* const
     // ---- all weight-gradient GEMMs, 8 problems per launch, then slabs -> parameter gradients -------
     if (r.side && r.p0_on_main) {
         flush_deferred(r, dq);            // a dozen workgroups, right behind their chain: no hand-over to wait for
-        flush_bias(r, dq, r.st);          // (nothing: the pass-0 problems keep their ones column)
         join_side(r, r.side);
     } else if (r.side) {
         kick_deferred(r, dq, r.side, true);
-        flush_bias(r, dq, r.side->st);
         join_side(r, r.side);
     } else {
         flush_deferred(r, dq);
-        flush_bias(r, dq, r.st);
     }
     gi_reduce_desc descs[160];            // whatever has not been reduced on the side stream yet
     int nd = 0;

@@ -140,7 +140,7 @@ def ggnn_forward_raw(consts, nodes, edges, params, kind: int = _L.KIND_GGNN, dro
         gs.x2_guard, gs.x2_guard_host = guard[0].data_ptr(), guard[1]
         graph.x2_guard = guard[0]                           # (the backward counts its dZ rows there too)
     flags = _L.RUN_NO_X2 if no_x2 else 0
-    side = _side_stream(dev) if (PREPACK_SIDE and not drop) else 0
+    side = _side_stream(dev) if not drop else 0
     if want_backward and not drop:
         flags |= _L.RUN_PREPACK_BWD
     if wcache is not None and not drop and not want_backward:
@@ -207,10 +207,6 @@ _SIDE_STREAMS = {}
 _SIDE_STREAM_OBJS = {}
 #: False keeps the whole backward on one stream (bench.py's one_stream measurement; no env knob)
 WGRAD_SIDE_STREAM = True
-#: False (environment GI_PREPACK=0): the forward packs nothing ahead and enqueues the weights' amax pass on its own
-#: stream — the round-4 schedule (A/B aid)
-import os as _os_env
-PREPACK_SIDE = _os_env.environ.get("GI_PREPACK", "1") != "0"
 
 
 def _side_stream_obj(device: torch.device, handle: int):
@@ -498,8 +494,7 @@ class _FusedMPNN(torch.nn.Module):
 
     def _cache_key(self, params):
         # every run-time switch the derivation reads: bf3_prepare writes the max |W| cells only with fp16x2 AND the
-        # pipelined kernel (gi_b3p_enable), the chains' weight guard runs only with the guard on.  GI_CHAIN_X2 and
-        # GI_CHAIN_FWD_X2 are read once from the environment and fixed for the life of the process.
+        # pipelined kernel (gi_b3p_enable), the chains' weight guard runs only with the guard on.
         lib = _L.load()
         return (_L.WEIGHTS_EPOCH[0], id(params), tuple((_ops._version(p), p.data_ptr()) for p in params),
                 self._x2_off(), bool(self.x2_guard), lib.gi_bf3_enable(-1), lib.gi_x2_enable(-1),

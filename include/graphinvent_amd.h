@@ -19,54 +19,21 @@
  *   - no exceptions cross the ABI; one process per GPU, calls come from one host thread at a time.
  *     Process-wide state is limited to: the optional per-launch timing log (gi_prof_*), a pool of
  *     timing-disabled hipEvents used to order the backward's two streams, the test / measurement hooks
- *     gi_gemm_config and gi_mlp_chain_config, and switches read once from the environment:
- *       GI_FUSE=<mask>          launch-count reductions (gi_fuse_flags, default 15)
- *       GI_CHAIN=0              per-bond-type stacks layer by layer through gi_gemm instead of gi_mlp_chain
+ *     gi_gemm_config and gi_mlp_chain_config, and eight switches read from the environment:
  *       GI_BF3=0                every GEMM and chain on the fp32 MFMA (default 1: the node-level readout layers >= 192
  *                               wide and the message stacks' chains, forward and dZ, run as splits on the 16-bit MFMA
  *                               pipe, GI_GEMM_BF3 — same result to ~3e-7; gi_bf3_enable)
  *       GI_X2=0                 those launches as three bf16 planes (six products) instead of two scaled fp16 planes
  *                               (three products, GI_GEMM_X2; gi_x2_enable); also puts the chains back on fp32
- *       GI_CHAIN_X2=0           only the dZ chains back on the fp32 chain kernel (gi_chain_params.x2_wamax unused)
- *       GI_CHAIN_FWD_X2=0       only the FORWARD chains back on the fp32 chain kernel (default: the row-independent
- *                               fp16x2 kernel, gi_chain_params.x2_rows32)
- *       GI_WGRAD_X2_ALL=1       (round 6; measured slower, off by default) EVERY weight gradient of at least 32 x 32 outputs
- *                               over >= 512 rows as an fp16x2 launch; operands nobody publishes a maximum of get their amax
- *                               cell from gi_absmax in front of the launch.  Default: the round-4 set + the message / energy
- *                               stacks' hidden layers (cells published by the fp16x2 chain kernels)
- *                               GI_WGRAD_T128=0 / 1 / 2: none (default) / the round-6 set / all fp16x2 weight gradients on the
- *                               128 x 128-tile kernel of gi_gemm_b3v.hip (GI_GEMM_T128) instead of the pipelined 128 x 256 one
- *       GI_MSG_WGRAD_X2=0       the fp16x2 chain kernels' amax cells are not used for the message / energy stacks' weight
- *                               gradients (their first, gathered layer then stays on the fp32 MFMA);
- *                               GI_MSG_SLAB_ROWS=<n>: reduction rows per split-K slab of the new launches (default 460)
- *       GI_GRU_PAD_LDS=0        (measurement aid) the fused GRU launch without the unused dynamic LDS that keeps it at one
- *                               workgroup per CU
- *       GI_GRU_FUSED=0          the forward's GRU update as a two-projection GEMM launch + the gate kernel (default, round 6:
- *                               one fused launch, csrc/gi_gru.hip)
- *       GI_CHAIN_PACK_FUSED=0   the fp16x2 chain image as memset + gi_absmax + pack launches (default, round 6: one launch that
- *                               also writes the max |W| cells)
- *       GI_P0_GRU_MAIN=0        pass 0's GRU weight gradients go to the weight-gradient queue with everything else (default,
- *                               round 6: they ride in the main queue's last launch, so that both queues end together)
- *       GI_GEMM_LOG=<file>      one line per GEMM launch (tools/gemm_launch_report.py)
- *     and measurement aids that pick between kernels / schedules that compute the same thing (the A/B files under
- *     profiles/r04 name them): GI_B3P, GI_B3V, GI_B3P_ALL, GI_B3P_STREAM, GI_B3V_GROUPED (which 16-bit-pipe kernel),
- *     GI_B3W_MSG, GI_B3W_G (message-stack / graph-level weight gradients on the 16-bit pipe below their size
- *     thresholds), GI_P0_LAYERWISE (pass 0 without the chain kernel), GI_CHAIN_BWD64 (64-row fp32 chain blocks in
- *     the backward), GI_CHAIN_XCD (0: the chain kernels' row blocks in dispatch order instead of the XCD-aware one),
- *     GI_CHAIN_X2R_DUAL (0 / 1: the row-independent fp16x2 chain never / always as two workgroups per CU; default: when a
- *     launch has more row blocks than CUs), GI_CHAIN_BWD_X2R (1: the dZ chains through that kernel too),
- *     GI_WGRAD_BIAS (1: weight gradients whose input width is a multiple of 64 get their bias gradient from a separate
- *     launch instead of a "ones" column that costs a column of tiles — measured a tie, off by default), GI_WGRAD_TN /
- *     GI_WGRAD_WGS (tile class / workgroups per problem of the fp32-MFMA weight gradients), GI_SEGSUM_U (outputs per
- *     thread of the aggregation kernel: 1, 2 or 4), GI_HOLD_KICKS (0 / 1: weight-gradient launches beside the
- *     node-level dgrad launches always / never; default: held back up to 9 000 node rows), GI_KICK_N (weight-gradient problems per hand-over to the second
- *     queue, 1..8), GI_SIDE_PRIO (0: gi_side_stream_create with a middle instead of the lowest priority), GI_CHAIN_RING3_SMALL (chain launches
- *     of at most that many row blocks on the three-slot weight ring), GI_DBG_X2 (only in a library built with -DGI_CHAIN_X2_LAB; results WRONG: parts of the fp16x2 chain kernel switched
- *     off for timing),
- *     GI_B3V_X2_FWD (1: the fp16x2 forward / dgrad launches of the node-level stacks on the 32-deep-tile kernel of gi_gemm_b3v.hip),
- *     GI_B3P_WGRAD_REMAP / GI_WGRAD_SLAB_ORDER
- *     (0: the 16-bit-pipe / fp32 weight-gradient tiles in dispatch order / per-slab order instead of slab-per-XCD); graphinvent_amd/gnn/mpnn.py reads GI_PREPACK (0: gi_ggnn_forward_ex without a side stream and without
- *     GI_RUN_PREPACK_BWD: the round-4 schedule).
+ *       GI_FUSE=<mask>          launch-count reductions (gi_fuse_flags, default 15)
+ *       GI_B3P=0, GI_B3V=0      initial values of gi_b3p_enable / gi_b3v_enable (default 1)
+ *       GI_B3P_ALL=1            forward / dgrad launches on the software-pipelined kernel whatever their tile count
+ *                               (default: from 2.5 tiles per CU on; gi_b3p_enable)
+ *       GI_CHAIN_PACK_FUSED=0   the fp16x2 chain image as memset + gi_absmax + pack launches instead of one launch that
+ *                               also writes the max |W| cells (read per call: the test of the fused launch compares both)
+ *       GI_GEMM_LOG=<file>      one line per GEMM launch (tools/gemm_launch_report.py); output only
+ *     Variants that were measured and not adopted are in the git history, not behind switches
+ *     (tools/experiments/README.md, "Retired switches").
  */
 #ifndef GRAPHINVENT_AMD_H
 #define GRAPHINVENT_AMD_H
@@ -239,7 +206,8 @@ int gi_host_flag_destroy(int* host);
                               matrix or the `planes` output of a producing launch); no a_idx */
 #define GI_GEMM_T128  2048 /* with GI_GEMM_BF3 | GI_GEMM_X2, weight-gradient layout: prefer the 128 x 128-tile kernel (256 threads,
                               32 KB of LDS, several workgroups per CU: gi_gemm_b3v.hip) to the software-pipelined
-                              128 x 256-tile one (one 512-thread workgroup per CU) — launches of many small problems */
+                              128 x 256-tile one (one 512-thread workgroup per CU) — launches of many small problems.
+                              Callers' choice: gi_ggnn_backward never sets it */
 #define GI_GEMM_X2    1024 /* with GI_GEMM_BF3 and plain fp32 operands: split every operand into TWO scaled fp16 values
                               instead of three bf16 (csrc/gi_x2.h): three f16 MFMA products per fp32 product instead of
                               six, the same ~3e-7 distance from the fp64 product.  Needs the largest magnitude of both
@@ -395,7 +363,7 @@ typedef struct {
                                  GI_GEMM_BF3B_F32 launches: a transposed copy of a weight, 4 bytes per element through L2
                                  instead of 6); fits the same buffer */
 } gi_bf3_pack_desc;
-/* Which kernel runs a GI_GEMM_BF3 launch whose operands are plain fp32 (measurement aids; on = 1 / 0 sets, on < 0
+/* Which kernel runs a GI_GEMM_BF3 launch whose operands are plain fp32 (test hooks; on = 1 / 0 sets, on < 0
  * queries; both return the previous setting; environment GI_B3P / GI_B3V set the initial values, default 1):
  *   gi_b3p_enable: the software-pipelined 128 x 256 kernel (gi_gemm_b3p.hip) — weight-gradient launches
  *                  (a_major + b_major + split-K slabs; autograd of gnn/modules.py:166-170) always, forward / dgrad
