@@ -1219,7 +1219,8 @@ __global__ __launch_bounds__(512, DUAL ? 4 : 1) void gi_chain_x2r_kernel(const C
 }
 
 int validate_chain(const gi_chain_params& p) {
-    if (p.nlayers < 1 || p.nlayers > GI_CHAIN_MAXL || !p.X || p.rows < 0) return GI_EINVAL;
+    if (p.nlayers > GI_CHAIN_MAXL) return GI_ELIMIT;   // (callers run such a stack layer by layer)
+    if (p.nlayers < 1 || !p.X || p.rows < 0) return GI_EINVAL;
     if (p.ngroups < 1 || p.ngroups > GI_MAX_GROUPS) return GI_EINVAL;
     if (p.ngroups > 1 && !p.grp_off) return GI_EINVAL;
     if (p.ldx < ((p.layer[0].K + 3) & ~3)) return GI_EINVAL;   // 16-byte reads end inside the row
@@ -1242,8 +1243,8 @@ int validate_chain(const gi_chain_params& p) {
 
 extern "C" long long gi_mlp_chain_image_floats(const gi_chain_params* p) {
     if (!p) return GI_EINVAL;
-    if (p->nlayers < 1 || p->nlayers > GI_CHAIN_MAXL || p->ngroups < 1 || p->ngroups > GI_MAX_GROUPS)
-        return GI_EINVAL;
+    if (p->nlayers > GI_CHAIN_MAXL) return GI_ELIMIT;
+    if (p->nlayers < 1 || p->ngroups < 1 || p->ngroups > GI_MAX_GROUPS) return GI_EINVAL;
     return (long long)p->ngroups * chain_tiles(*p) * CH_TILE;
 }
 
@@ -1252,8 +1253,8 @@ extern "C" int gi_mlp_chain_pack(const gi_chain_params* chains, int nchains, voi
     if (!chains || nchains < 1 || nchains > 2) return GI_EINVAL;
     for (int c = 0; c < nchains; ++c) {
         const gi_chain_params& p = chains[c];
-        if (p.nlayers < 1 || p.nlayers > GI_CHAIN_MAXL || p.ngroups < 1 || p.ngroups > GI_MAX_GROUPS)
-            return GI_EINVAL;
+        if (p.nlayers > GI_CHAIN_MAXL) return GI_ELIMIT;
+        if (p.nlayers < 1 || p.ngroups < 1 || p.ngroups > GI_MAX_GROUPS) return GI_EINVAL;
         for (int l = 0; l < p.nlayers; ++l) {
             const gi_chain_layer& q = p.layer[l];
             if (q.K < 4 || q.N < 4 || q.K > GI_CHAIN_MAXW || q.N > GI_CHAIN_MAXW) return GI_ELIMIT;

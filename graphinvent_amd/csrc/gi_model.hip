@@ -27,6 +27,9 @@ namespace {
 
 constexpr int MAXL = 12;   // max Linear layers per MLP (depth + 1)
 constexpr int MAXP = 16;   // max message passes
+// parameter tensors of the largest model build_model accepts: AttentionGGNN with GI_MAX_GROUPS bond types and every
+// stack MAXL layers deep (message + energy stacks per bond type, the GRU's four, seven readout / gather stacks)
+constexpr int MAXPARAMS = 2 * MAXL * (2 * GI_MAX_GROUPS + 7) + 4;
 
 struct Mlp {
     int base, in, hidden, depth, out;
@@ -358,7 +361,7 @@ void wcache_layout(const Model& m, Wc& c) {
 // ---- wgrad slab plan ----------------------------------------------------------------------------
 struct SlabEntry { long long off, stride; int nsplit, calls, done, n_out, n_in, ld, bidx, launched, reduced, bf3, single_last, x2all; };   // x2all: fp16x2 launch from the operands' published amax cells (plan_slabs)   // single_last: the last call wrote ONE slab (the pass-0 rows, defer_wgrad)
 struct SlabPlan {
-    SlabEntry e[160];
+    SlabEntry e[MAXPARAMS];
     long long total;
 };
 
@@ -990,12 +993,12 @@ void kick_deferred(Run& r, Deferred& q, SideStream* side, bool all) {
     launch_wgrad_batches(r, q, n, side->st);
     // parameters whose last slab has just been queued: reduce them right behind, on the side stream
     // too, so that only the final pass's gradients are left for the end of the backward
-    gi_reduce_desc descs[96 * GI_MAX_GROUPS > 160 ? 160 : 96 * GI_MAX_GROUPS];
+    gi_reduce_desc descs[96 * GI_MAX_GROUPS > MAXPARAMS ? MAXPARAMS : 96 * GI_MAX_GROUPS];
     int nd = 0;
     for (int i = 0; i < n; ++i)
         for (int k = 0; k < q.nw[i]; ++k) {
             SlabEntry& e = r.sp->e[q.widx[i][k]];
-            if (++e.launched == e.calls && !e.reduced && nd < 160) {
+            if (++e.launched == e.calls && !e.reduced && nd < (int)(sizeof(descs) / sizeof(descs[0]))) {
                 e.reduced = 1;
                 descs[nd++] = reduce_desc(e, r.slabs, r.grads, q.widx[i][k]);
             }
@@ -1547,7 +1550,7 @@ extern "C" long long gi_ggnn_slab_floats(const gi_ggnn_dims* d, int S, int U, co
     if (build_model(d, m) || S < 0 || E < 0) return GI_EINVAL;
     static_assert(sizeof(SlabPlan) < (1 << 16), "plan size");
     SlabPlan sp;
-    if (m.nparams > 160) return GI_ELIMIT;
+    if (m.nparams > MAXPARAMS) return GI_ELIMIT;
     plan_slabs(m, S, E, Et, sp);
     return sp.total;
 }
@@ -1816,7 +1819,7 @@ static int mnn_backward(const Model& m, const float* const* params, const gi_gra
         hipStream_t rst = r.side ? r.side->st : r.st;
         if (r.side) kick_deferred(r, dq, r.side, true);
         else flush_deferred(r, dq);
-        gi_reduce_desc descs[160];
+        gi_reduce_desc descs[MAXPARAMS];
         int nd = 0;
         readout_params([&](int widx) {
             if (sp.e[widx].reduced) return;
@@ -1883,7 +1886,7 @@ static int mnn_backward(const Model& m, const float* const* params, const gi_gra
     } else {
         flush_deferred(r, dq);
     }
-    gi_reduce_desc descs[160];
+    gi_reduce_desc descs[MAXPARAMS];
     int nd = 0;
     auto add_desc = [&](int widx) {
         SlabEntry& e = sp.e[widx];
@@ -2258,7 +2261,7 @@ extern "C" int gi_ggnn_backward_phase(const gi_ggnn_dims* dp, const float* const
         return GI_EINVAL;
     if (E > 0 && (!u_src || !in_perm || !mu_off || !mu_dst || !mu_slot || !out_perm || U == 0))
         return GI_EINVAL;
-    if (m.nparams > 160) return GI_ELIMIT;
+    if (m.nparams > MAXPARAMS) return GI_ELIMIT;
     if (gp->wcache) return GI_EINVAL;     // (a forward that used the weights cache left no max |W| cells in ws)
     const gi_ggnn_dims& d = m.d;
     gi_compact_layout_t L;
@@ -2398,7 +2401,7 @@ extern "C" int gi_ggnn_backward_phase(const gi_ggnn_dims* dp, const float* const
         // of these parameters while the message passes are still being differentiated
         if (r.side) {
             kick_deferred(r, dq, r.side, true);          // also reduces every finished parameter
-            gi_reduce_desc descs[160];
+            gi_reduce_desc descs[MAXPARAMS];
             int nd = 0;
             readout_params([&](int widx) {
                 if (sp.e[widx].reduced) return;
@@ -2408,7 +2411,7 @@ extern "C" int gi_ggnn_backward_phase(const gi_ggnn_dims* dp, const float* const
             if (nd && r.ok()) r.chk(gi_reduce_slabs(descs, nd, r.side->st));
         } else {
             flush_deferred(r, dq);
-            gi_reduce_desc descs[160];
+            gi_reduce_desc descs[MAXPARAMS];
             int nd = 0;
             readout_params([&](int widx) {
                 sp.e[widx].reduced = 1;
@@ -2558,7 +2561,7 @@ extern "C" int gi_ggnn_backward_phase(const gi_ggnn_dims* dp, const float* const
     } else {
         flush_deferred(r, dq);
     }
-    gi_reduce_desc descs[160];            // whatever has not been reduced on the side stream yet
+    gi_reduce_desc descs[MAXPARAMS];            // whatever has not been reduced on the side stream yet
     int nd = 0;
     auto add_desc = [&](int widx, int) {
         SlabEntry& e = sp.e[widx];

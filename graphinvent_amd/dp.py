@@ -100,8 +100,12 @@ class DataParallel:
         if bucket is None:
             return None
         base = bucket.untyped_storage().data_ptr()
+        # (a parameter without a gradient — the message stacks and GRU of a model with 0 message passes — keeps its
+        # segment of the bucket, zeros, in the exchange; its .grad stays None)
+        if all(p.grad is None for p in self.params):
+            return None
         for p in self.params:
-            if p.grad is None or p.grad.untyped_storage().data_ptr() != base:
+            if p.grad is not None and p.grad.untyped_storage().data_ptr() != base:
                 return None
         return bucket
 
@@ -153,7 +157,9 @@ class DataParallel:
                 dist.all_reduce(bucket, op=dist.ReduceOp.SUM, group=self.group)
             bucket.mul_(1.0 / self.world_size)
             return
-        grads = [p.grad for p in self.params]
+        grads = [p.grad for p in self.params if p.grad is not None]
+        if not grads:
+            return
         flat = torch.cat([g.reshape(-1) for g in grads])
         dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=self.group)
         flat.mul_(1.0 / self.world_size)

@@ -59,6 +59,29 @@ def _dims_from_constants(c, B: int, kind: int = _L.KIND_GGNN) -> "_L.GgnnDims":
     return d
 
 
+def _check_limits(c, kind: int) -> None:
+    """The compiled-in limits of the HIP model (``gi_ggnn_num_params``), checked when the model is built: the
+    reference accepts any value, and past a limit the forward could only report a parameter-table mismatch."""
+    if kind == _L.KIND_MNN:
+        depths = ("mlp1_depth", "mlp2_depth")
+    else:
+        depths = ("msg_depth", "att_depth") if kind == _L.KIND_ATTGGNN else ("enn_depth",)
+        depths += ("gather_att_depth", "gather_emb_depth", "mlp1_depth", "mlp2_depth")
+    limits = [(k, 0, _L.MODEL_MAX_DEPTH) for k in depths] + [("message_passes", 0, _L.MODEL_MAX_PASSES),
+                                                               ("max_n_nodes", 1, _L.GI_MAX_NODES),
+                                                               ("n_edge_features", 1, _L.GI_MAX_GROUPS)]
+    for key, lo, hi in limits:
+        v = getattr(c, key)
+        if not lo <= v <= hi:
+            raise ValueError(f"{key} = {v}: the HIP model supports {key} from {lo} to {hi}")
+
+
+def _unused_without_passes(c, dims) -> int:
+    """How many leading parameters (message stacks / message weights, GRU) a model with 0 message passes never
+    reads: the reference leaves their ``.grad`` None."""
+    return _L.load().gi_ggnn_first_readout_param(C.byref(dims)) if c.message_passes == 0 else 0
+
+
 def _ptr_table(tensors) -> "C.Array":
     return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
@@ -117,7 +140,10 @@ def ggnn_forward_raw(consts, nodes, edges, params, kind: int = _L.KIND_GGNN, dro
     dims = _dims_from_constants(consts, B, kind)
     if drop:
         _set_dropout(dims, consts, kind, dropout_seed)
-    if lib.gi_ggnn_num_params(C.byref(dims)) != len(params):
+    n_params = lib.gi_ggnn_num_params(C.byref(dims))
+    if n_params < 0:
+        _L.check(int(n_params), "model dimensions (gi_ggnn_num_params)")
+    if n_params != len(params):
         raise RuntimeError("parameter table does not match the model dimensions")
     for p in params:
         if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
@@ -169,7 +195,10 @@ def _forward_bounded(lib, consts, nodes, edges, params, kind, bounds, p0_cache=N
     B, N = nodes.shape[0], nodes.shape[1]
     attn = kind == _L.KIND_ATTGGNN
     dims = _dims_from_constants(consts, B, kind)
-    if lib.gi_ggnn_num_params(C.byref(dims)) != len(params):
+    n_params = lib.gi_ggnn_num_params(C.byref(dims))
+    if n_params < 0:
+        _L.check(int(n_params), "model dimensions (gi_ggnn_num_params)")
+    if n_params != len(params):
         raise RuntimeError("parameter table does not match the model dimensions")
     e_bound, d0_bound = bounds
     dev = nodes.device
@@ -332,7 +361,8 @@ class _GGNNFunction(torch.autograd.Function):
         # hooks on them) while a collective would still be reducing the bucket in place
         grads, gflat = ggnn_backward_raw(tape, out, d_out, params, None)
         ctx.owner._grad_bucket = gflat          # the flat bucket graphinvent_amd.dp all-reduces
-        return (None, None, None, *grads)
+        unused = _unused_without_passes(ctx.owner.constants, tape[0])
+        return (None, None, None, *([None] * unused), *grads[unused:])
 
 
 class _GGNNDirect(torch.autograd.Function):
@@ -671,14 +701,16 @@ class _FusedMPNN(torch.nn.Module):
                                "all-reduce of the first one is reducing the gradient bucket in place; "
                                "use DataParallel(overlap=False) for multiple backwards per step")
         grads, gflat = ggnn_backward_raw(tape, out, d_out, params, hook, bucket)
+        # (0 message passes: the parameters the forward never read keep their .grad, None or not, like autograd's)
+        unused = _unused_without_passes(self.constants, tape[0])
         with torch.no_grad():
             if fresh:
-                for p, g in zip(params, grads):
+                for p, g in zip(params[unused:], grads[unused:]):
                     if p.requires_grad:
                         p.grad = g
                 self._grad_bucket = gflat    # the flat bucket graphinvent_amd.dp all-reduces
             else:                            # gradient accumulation across backward calls
-                for p, g in zip(params, grads):
+                for p, g in zip(params[unused:], grads[unused:]):
                     if p.requires_grad:
                         if p.grad is None:
                             p.grad = g
@@ -719,6 +751,7 @@ class GGNN(_FusedMPNN):
         self.message_size = c.message_size
         self.message_passes = c.message_passes
         self.constants = c
+        _check_limits(c, self._KIND)
 
         # registration order of gnn/mpnn.py:238-282 (fixes state_dict order and RNG consumption)
         self.msg_nns = torch.nn.ModuleList()
@@ -746,6 +779,7 @@ class AttentionGGNN(_FusedMPNN):
         self.message_size = c.message_size
         self.message_passes = c.message_passes
         self.constants = c
+        _check_limits(c, self._KIND)
 
         # both ModuleLists are registered first (state_dict: every msg_nns.* before att_nns.*), the
         # MLPs are constructed interleaved (RNG order msg_0, att_0, msg_1, ...): gnn/mpnn.py:316-335
@@ -778,6 +812,7 @@ class MNN(_FusedMPNN):
         self.message_size = c.message_size
         self.message_passes = c.message_passes
         self.constants = c
+        _check_limits(c, self._KIND)
 
         # registration order and RNG consumption of gnn/mpnn.py:21-53: message_weights (uninitialised), GRUCell,
         # GlobalReadout (graph_emb_size = hidden_node_features), then reset_parameters draws message_weights

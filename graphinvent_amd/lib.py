@@ -23,6 +23,7 @@ CSRC = os.path.join(_HERE, "csrc")
 
 GI_MAX_GROUPS = 8
 GI_MAX_NODES = 128
+MODEL_MAX_DEPTH, MODEL_MAX_PASSES = 11, 16    # stack depth (MAXL - 1) and message passes (MAXP) of csrc/gi_model.hip
 EPI_BIAS, EPI_SELU, EPI_DSELU, EPI_ACCUM, GEMM_SPLITK = 1, 2, 4, 8, 16
 EPI_MULACT = 64
 GEMM_BF3A, GEMM_BF3B_F32 = 256, 512       # with GEMM_BF3: A is an image too / B is the plain fp32 matrix

@@ -815,6 +815,8 @@ typedef struct gi_ggnn_dims {
 int gi_side_stream_create(void** stream);
 int gi_side_stream_destroy(void* stream);
 
+/* Number of parameter tensors of the model, or GI_ELIMIT past a compiled-in limit: every stack depth 0..11 (at most 12
+ * Linear layers), 0..16 message passes, N <= GI_MAX_NODES, Fe <= GI_MAX_GROUPS. */
 int gi_ggnn_num_params(const gi_ggnn_dims* d);
 /* S active slots, E directed edges, U message rows, D0 pass-0 rows (counts[0], [1], [3], [20]) */
 long long gi_ggnn_workspace_floats(const gi_ggnn_dims* d, int S, int E, int U, int D0);

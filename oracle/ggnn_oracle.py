@@ -407,14 +407,15 @@ def forward_backward(P, cfg, nodes, edges, target, model: str = "GGNN", upstream
     """One forward + loss + backward; returns (logits, loss, grads-by-key).  Train-step order of
     Workflow.py:785-796 up to (not including) the optimizer.  upstream != None: the gradients are J^T . upstream — the
     backward operator applied to a GIVEN d loss / d logits instead of this evaluation's own (tests: the backward's
-    arithmetic apart from the conditioning of softmax - target on a fitted model)."""
+    arithmetic apart from the conditioning of softmax - target on a fitted model).  A parameter the forward never
+    reads (message stacks and GRU at message_passes = 0) gets None, as the reference's ``.grad`` stays None."""
     leaves = OrderedDict((k, v.detach().clone().requires_grad_(True)) for k, v in P.items())
     out = FORWARDS[model](leaves, cfg, nodes, edges)
     loss = kl_loss(out, target)
     if upstream is not None:
-        grads = torch.autograd.grad(out, list(leaves.values()), grad_outputs=upstream.to(out.dtype))
+        grads = torch.autograd.grad(out, list(leaves.values()), grad_outputs=upstream.to(out.dtype), allow_unused=True)
     else:
-        grads = torch.autograd.grad(loss, list(leaves.values()))
+        grads = torch.autograd.grad(loss, list(leaves.values()), allow_unused=True)
     return out.detach(), loss.detach(), OrderedDict(zip(leaves.keys(), grads))
 
 

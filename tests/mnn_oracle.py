@@ -130,9 +130,10 @@ def typed_sums(h: np.ndarray, in_perm: np.ndarray, u_src: np.ndarray, u_type: np
 
 
 def forward_backward(P, cfg, nodes, edges, target):
-    """One forward + KL loss + backward; returns (logits, loss, grads-by-key)."""
+    """One forward + KL loss + backward; returns (logits, loss, grads-by-key), None for a parameter the forward never
+    reads (message_weights and GRU at message_passes = 0), as the reference's ``.grad`` stays None."""
     leaves = OrderedDict((k, v.detach().clone().requires_grad_(True)) for k, v in P.items())
     out = mnn_forward(leaves, cfg, nodes, edges)
     loss = O.kl_loss(out, target)
-    grads = torch.autograd.grad(loss, list(leaves.values()))
+    grads = torch.autograd.grad(loss, list(leaves.values()), allow_unused=True)
     return out.detach(), loss.detach(), OrderedDict(zip(leaves.keys(), grads))

@@ -125,3 +125,53 @@ def test_pending_early_exchange_with_replaced_gradients_fails_loudly(tmp_path):
     mp.spawn(_worker_replaced_grads, args=(2, port, str(tmp_path)), nprocs=2, join=True)
     for r in (0, 1):
         assert "no longer views" in torch.load(tmp_path / f"e{r}.pt")["msg"]
+
+
+def _worker_zero_passes(rank, world, port, out_dir, overlap):
+    """A model with 0 message passes: its message stacks and GRU get no gradient (.grad None, as in the reference);
+    their segments of the flat bucket (zeros) still travel with the exchange."""
+    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
+    from graphinvent_amd import dp, synthetic
+    from graphinvent_amd.gnn import mpnn
+    from graphinvent_amd.loss import apd_kl_loss
+    from graphinvent_amd.optim import FusedAdam
+    from oracle import ggnn_oracle as O
+    torch.cuda.set_device(0)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    cfg = O.make_config(device="cuda", message_passes=0)
+    model = mpnn.GGNN(O.as_constants(cfg))
+    model.load_state_dict(O.init_params(cfg, seed=10 + rank))
+    model = model.cuda().train()
+    n8, e8, a8 = synthetic.make_batch(64, **synthetic.SHAPES["gdb13"], seed=3 + rank)
+    nodes, edges, tgt = (torch.from_numpy(x).float().cuda() for x in (n8, e8, a8))
+    opt = FusedAdam(model.parameters(), lr=1e-3, weight_decay=1e-2)
+    tr = dp.DataParallel(model, opt, loss_fn=apd_kl_loss, overlap=overlap)
+    tr.broadcast_parameters(src=0)
+    before = [p.detach().clone() for p in model.parameters()]
+    tr.step(nodes, edges, tgt)
+    torch.save(dict(before=[b.cpu() for b in before], params=[p.detach().cpu() for p in model.parameters()],
+                    no_grad=[p.grad is None for p in model.parameters()],
+                    bucket=model._grad_bucket.cpu() if model._grad_bucket is not None else None,
+                    zero_copy=tr.last_bucket_zero_copy, overlapped=tr.last_overlapped),
+               os.path.join(out_dir, f"z{rank}.pt"))
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("overlap", [True, False])
+def test_zero_passes_data_parallel_step(tmp_path, overlap):
+    from graphinvent_amd.gnn import mpnn
+    from oracle import ggnn_oracle as O
+    port = _free_port()
+    mp.spawn(_worker_zero_passes, args=(2, port, str(tmp_path), overlap), nprocs=2, join=True)
+    r0, r1 = (torch.load(tmp_path / f"z{r}.pt") for r in (0, 1))
+    names = list(O.param_shapes(O.make_config(message_passes=0)))
+    unused = [k.startswith(("msg_nns.", "gru.")) for k in names]
+    assert r0["no_grad"] == unused == r1["no_grad"]                   # .grad None exactly for those
+    assert r0["zero_copy"] and r1["zero_copy"] and r0["overlapped"] == overlap
+    offs, _ = mpnn.grad_bucket_layout(r0["params"])
+    for k, u, o, p in zip(names, unused, offs, r0["params"]):
+        if u:                                                          # their bucket segments: zeros
+            assert not bool(r0["bucket"][o:o + p.numel()].any()), k
+    for u, b, a, c in zip(unused, r0["before"], r0["params"], r1["params"]):
+        assert torch.equal(a, c)                                       # ranks stay bit-identical
+        assert torch.equal(a, b) == u                                  # Adam (weight decay) moves only the used ones

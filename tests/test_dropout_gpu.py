@@ -81,10 +81,18 @@ DROPS = dict(enn_dropout_p=0.1, gather_att_dropout_p=0.15, gather_emb_dropout_p=
              mlp1_dropout_p=0.2, mlp2_dropout_p=0.1)
 
 
-@pytest.mark.parametrize("name", ["GGNN", "AttGGNN"])
+#: GGNN variants whose dropout sites shift: stacks 0 / 1 deep (a stack's only layer is also its last), one pass
+VARIANTS = {"GGNN_depth01": dict(enn_depth=0, gather_att_depth=1, gather_emb_depth=0, mlp1_depth=1, mlp2_depth=0),
+            "GGNN_passes1": dict(message_passes=1)}
+
+
+@pytest.mark.parametrize("name", ["GGNN", "AttGGNN"] + list(VARIANTS))
 def test_training_mode_matches_the_oracle_fed_the_same_masks(name):
     if name == "GGNN":
         cfg, cls = O.make_config(**TINY, **DROPS), mpnn.GGNN
+    elif name in VARIANTS:
+        cfg, cls = O.make_config(**dict(TINY, **VARIANTS[name]), **DROPS), mpnn.GGNN
+        name = "GGNN"
     else:
         drops = dict(DROPS, msg_dropout_p=0.1, att_dropout_p=0.2)
         drops.pop("enn_dropout_p")

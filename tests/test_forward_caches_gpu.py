@@ -264,13 +264,23 @@ def _variant(name):
             return torch.from_numpy(n8).float().to(DEV), torch.from_numpy(e8).float().to(DEV)
         # up to 12 x 3 x 4 feature classes per bond type: above ops.default_bounds' 64, within GI_P0_MAX_CLASSES
         return "GGNN", cfg, implicit, (4 * 1000 * 13, 256 * 3)
+    if name == "depth0":                     # every stack one Linear: pass-0 class rows produce the messages directly
+        return "GGNN", O.shaped_config(*g, enn_depth=0, gather_att_depth=0, gather_emb_depth=0, mlp1_depth=0,
+                                       mlp2_depth=0), plain, None
+    if name == "passes1":                    # pass 0 is the only pass: the table's rows are the whole message stage
+        return "GGNN", O.shaped_config(*g, message_passes=1), plain, None
+    if name == "chain_maxl":                 # 8-layer message stacks (GI_CHAIN_MAXL): the largest chain image
+        return "GGNN", O.shaped_config(*g, enn_depth=7), plain, None
+    if name == "chain_over":                 # 9 layers: chain-ineligible by depth, layer by layer, no chain image
+        return "GGNN", O.shaped_config(*g, enn_depth=8), plain, None
     if name == "narrow_readout":             # every node-level layer below BF3_MIN_WIDTH: no 16-bit-pipe launch
         return "GGNN", O.shaped_config(*g, gather_att_hidden_dim=160, gather_emb_hidden_dim=160,
                                        mlp1_hidden_dim=160, mlp2_hidden_dim=160), plain, None
     raise KeyError(name)
 
 
-@pytest.mark.parametrize("name", ["mnn", "wide_enn", "wide_h", "implicit_h", "narrow_readout"])
+@pytest.mark.parametrize("name", ["mnn", "wide_enn", "wide_h", "implicit_h", "narrow_readout", "depth0", "passes1",
+                                  "chain_maxl", "chain_over"])
 @pytest.mark.parametrize("sync_free", [False, True])
 def test_model_variants(name, sync_free):
     kind, cfg, make, bounds = _variant(name)

@@ -663,6 +663,7 @@ def _chain_case(sizes, off, seed, two=False, x2=False, in_scale=1.0, rows32=Fals
     ((16, 24, 24, 12), [0, 5, 7, 8]),                           # tiny config
     ((37, 256, 7, 130), [0, 64]),                               # one group, awkward widths, depth 2
     ((128, 100), [0, 31, 95]),                                  # single layer
+    ((100,) + (250,) * 7 + (100,), [0, 33, 33, 131]),          # 8 layers = GI_CHAIN_MAXL, ragged, empty group
 ])
 def test_mlp_chain_forward_and_dz_chain(sizes, off):
     _chain_case(sizes, off, seed=sum(sizes))
@@ -680,6 +681,7 @@ def test_mlp_chain_two_chains_one_launch():
     ((16, 24, 24, 12), [0, 5, 7, 8]),                           # tiny config
     ((37, 256, 7, 130), [0, 64]),                               # one group, awkward widths, exactly one block
     ((128, 100), [0, 31, 95]),                                  # single layer
+    ((100,) + (250,) * 7 + (100,), [0, 33, 33, 131]),          # 8 layers = GI_CHAIN_MAXL, ragged, empty group
 ])
 def test_mlp_chain_fp16x2_forward_and_dz_chain(sizes, off, in_scale):
     """The fp16x2 chain (gi_chain_params.x2_wamax; csrc/gi_x2.h): 64-row blocks, weights as two scaled fp16 planes
@@ -699,6 +701,7 @@ def test_mlp_chain_fp16x2_forward_and_dz_chain(sizes, off, in_scale):
     ((16, 24, 24, 12), [0, 5, 7, 8]),                           # tiny config
     ((37, 256, 7, 130), [0, 64]),                               # one group, awkward widths
     ((128, 100), [0, 31, 95]),                                  # single layer
+    ((100,) + (250,) * 7 + (100,), [0, 33, 33, 131]),          # 8 layers = GI_CHAIN_MAXL, ragged, empty group
 ])
 def test_mlp_chain_fp16x2_row_independent_variant(sizes, off, in_scale):
     """gi_chain_params.x2_rows32 (round 5): 32-row blocks, every ROW scaled by its own power of two, the product formed
@@ -802,6 +805,7 @@ def test_mlp_chain_fp16x2_rows32_is_bitwise_row_independent():
     ((128, 250, 250, 250, 250, 128), [0, 600, 600, 777]),
     ((100, 250, 250, 100), [0, 33, 34, 131]),
     ((37, 256, 7, 130), [0, 70]),
+    ((100,) + (250,) * 7 + (100,), [0, 33, 33, 131]),          # 8 layers = GI_CHAIN_MAXL, ragged, empty group
 ])
 def test_mlp_chain_taller_row_blocks(chain_cfg, tile_rows, sizes, off):
     """Row blocks of 32 + x rows (x <= 4 extra rows computed on the VALU; what the launcher picks when
@@ -817,6 +821,7 @@ def test_mlp_chain_taller_row_blocks(chain_cfg, tile_rows, sizes, off):
     ((100, 250, 250, 100), [0, 33, 34, 131]),
     ((100, 250, 250, 250, 250, 100), [0, 1000, 1001, 2500]),
     ((37, 256, 7, 130), [0, 70]),
+    ((100,) + (250,) * 7 + (100,), [0, 33, 33, 131]),          # 8 layers = GI_CHAIN_MAXL, ragged, empty group
 ])
 def test_mlp_chain_64_row_blocks(chain_cfg, sizes, off):
     """The <2, 2> variant (64 rows per workgroup, two weight tiles in LDS; what the launcher picks for
@@ -832,6 +837,7 @@ def test_mlp_chain_64_row_blocks(chain_cfg, sizes, off):
     ((128, 250, 250, 250, 250, 128), [0, 600, 600, 777]),
     ((100, 250, 250, 100), [0, 33, 34, 131]),
     ((37, 256, 7, 130), [0, 70]),
+    ((100,) + (250,) * 7 + (100,), [0, 33, 33, 131]),          # 8 layers = GI_CHAIN_MAXL, ragged, empty group
 ])
 def test_mlp_chain_three_slot_ring(chain_cfg, tile_rows, sizes, off):
     """gi_chain_kernel<BWD, 1, 3>: 32-row blocks with the three-slot weight ring (146 KB of LDS) — the default

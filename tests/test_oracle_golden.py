@@ -110,15 +110,38 @@ def test_attggnn_oracle_matches_reference(golden_dir):
         assert rel(v.numpy(), g["grad." + k]) < 2e-5, k
 
 
-SHAPE_GOLDENS = ("golden_zinc", "golden_att_gdb13", "golden_att_chembl", "golden_aromatic")
+#: tests/golden/make_golden_depths.py: stack depths 0, 1, mixed, 7 / 8 (the chain kernels' layer limit and one past it)
+#: and 0, 1, 5 message passes, for GGNN, AttentionGGNN and MNN
+DEPTH_GOLDENS = ("golden_depth0", "golden_depth1", "golden_depth_mixed", "golden_enn7_passes5", "golden_passes1",
+                 "golden_passes0", "golden_att_msg0_att8_passes1", "golden_att_msg7_att0", "golden_att_passes0",
+                 "golden_mnn_passes0", "golden_mnn_passes1", "golden_mnn_depth0")
+SHAPE_GOLDENS = ("golden_zinc", "golden_att_gdb13", "golden_att_chembl", "golden_aromatic") + DEPTH_GOLDENS
 
 
 def load_shape_golden(golden_dir, name):
-    """(cfg, params, arrays, model kind) of a fixture written by tests/golden/make_golden_shapes.py."""
+    """(cfg, params, arrays, model kind) of a fixture written by tests/golden/make_golden_shapes.py or
+    make_golden_depths.py (model kind "GGNN", "AttGGNN" or "MNN")."""
     g = np.load(os.path.join(golden_dir, name + ".npz"))
-    cfg = O.make_config(**{k[4:]: int(g[k]) for k in g.files if k.startswith("cfg.")})
     kind = str(g["model"])
+    stored = {k[4:]: int(g[k]) for k in g.files if k.startswith("cfg.")}
+    if kind == "MNN":
+        from tests import mnn_oracle as MO
+        cfg = MO.tiny_config(**stored)
+        return cfg, MO.init_params(cfg, seed=int(g["seed"])), g, kind
+    cfg = O.make_config(**stored)
     return cfg, O.init_params(cfg, seed=int(g["seed"]), model=kind), g, kind
+
+
+def no_grad_names(g) -> set:
+    """The parameters whose .grad the reference left None (fixtures of make_golden_depths.py)."""
+    return set(str(k) for k in g["nograd"]) if "nograd" in g.files else set()
+
+
+def oracle_forward_backward(kind, P, cfg, nodes, edges, tgt):
+    if kind == "MNN":
+        from tests import mnn_oracle as MO
+        return MO.forward_backward(P, cfg, nodes, edges, tgt)
+    return O.forward_backward(P, cfg, nodes, edges, tgt, model=kind)
 
 
 @pytest.mark.parametrize("name", SHAPE_GOLDENS)
@@ -133,13 +156,16 @@ def test_other_shapes_and_variants_match_reference(golden_dir, name):
     so every tensor must agree with the oracle at 1e-4 in at least one of the two precisions."""
     cfg, P, g, kind = load_shape_golden(golden_dir, name)
     nodes, edges, tgt = (torch.from_numpy(g[k]).float() for k in ("nodes", "edges", "apds"))
-    out, loss, grads = O.forward_backward(P, cfg, nodes, edges, tgt, model=kind)
+    out, loss, grads = oracle_forward_backward(kind, P, cfg, nodes, edges, tgt)
     assert out.shape == g["logits"].shape
     assert rel(out.numpy(), g["logits"]) < 5e-6
     assert abs(float(loss) - float(g["loss"])) < 1e-6 * abs(float(g["loss"]))
+    # None exactly where the reference's .grad is None (0 message passes), a digest for every other parameter
+    assert set(k for k, v in grads.items() if v is None) == no_grad_names(g)
+    grads = {k: v for k, v in grads.items() if v is not None}
     assert set("gdigest." + k for k in grads) == set(k for k in g.files if k.startswith("gdigest."))
     P64 = {k: v.double() for k, v in P.items()}
-    _, _, grads64 = O.forward_backward(P64, cfg, nodes.double(), edges.double(), tgt.double(), model=kind)
+    _, _, grads64 = oracle_forward_backward(kind, P64, cfg, nodes.double(), edges.double(), tgt.double())
 
     def err(v, ref):
         d = digest(v)
