@@ -57,6 +57,8 @@ int gi_gru_fused_fwd(const float* agg, int lda, const float* hx, int ldh, const 
 
 // gi_gemm_batch hands launches whose problems all carry GI_GEMM_BF3 to gi_gemm_bf3.hip
 int gi_gemm_bf3_launch(const gi_gemm_params* probs, int n, void* stream);
+// ... and fp16x2 launches of plain fp32 operands with the forward / dgrad epilogue (epi 1 / 2) to gi_gemm_x2n.hip
+int gi_x2n_launch(const gi_gemm_params* probs, int n, int epi, void* stream);
 // ... and gi_gemm_bf3_launch those with plain fp32 operands (no images, no gathers) to gi_gemm_b3v.hip: forward,
 // dgrad (W as stored, b_major) and weight-gradient (a_major + b_major, split-K slabs) layouts on 32-deep k tiles
 bool gi_b3v_eligible(const gi_gemm_params* probs, int n);

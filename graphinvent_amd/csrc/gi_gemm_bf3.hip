@@ -517,6 +517,12 @@ int gi_gemm_bf3_launch(const gi_gemm_params* probs, int n, void* stream) {
         // measured on the node-level hidden-layer launch (684 tiles): 76.7 -> 73.0 us forward, 84.0 -> 82.1 dgrad
         b.remap = (total >= 512 && !bounded) ? 1 : 0;       // (bounded: the order would be over the bound's tiles)
     }
+    if (x2 && (epi == 1 || epi == 2)) {
+        // forward / dgrad epilogues: the column-split kernel (gi_gemm_x2n.hip), the same results bit for bit;
+        // GI_X2N=0 (read per launch: a test compares both) keeps them here
+        const char* e = getenv("GI_X2N");
+        if (!(e && atoi(e) == 0)) return gi_x2n_launch(probs, n, epi, stream);
+    }
     hipStream_t st = (hipStream_t)stream;
     GiProfScope prof(st, GI_PROF_GEMM | (x2 ? GI_PROF_PIPE_X2 : GI_PROF_PIPE_BF3), flops);
     gi_gemm_log_launch(x2 ? ((b.p[0].flags & GI_EPI_BIAS) ? "x0" : "x1") : ((b.p[0].flags & GI_EPI_BIAS) ? "b0" : "b1"), b.p, k,

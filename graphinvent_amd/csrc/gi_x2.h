@@ -55,12 +55,16 @@ __device__ __forceinline__ float gx_amax_read(const float* cell) {
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
     return m;
 }
-// largest |v| over the lanes of a wave -> one atomic max on the bit pattern (all values >= 0) of the wave's slot
-__device__ __forceinline__ void gx_amax_publish(float m, float* cell) {
+// largest |v| over the lanes of a wave -> one atomic max on the bit pattern (all values >= 0) of slot `s` of the cell
+__device__ __forceinline__ void gx_amax_publish_slot(float m, float* cell, int s) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    float* slot = cell + ((blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) & (GX_AMAX_SLOTS - 1)) * GX_AMAX_STRIDE;
+    float* slot = cell + s * GX_AMAX_STRIDE;
     // look first: a stale value only costs a redundant atomic (the maximum is monotonic)
     if ((threadIdx.x & 63) == 0 && m > *reinterpret_cast<volatile float*>(slot))
         atomicMax(reinterpret_cast<unsigned*>(slot), __builtin_bit_cast(unsigned, m));
+}
+// ... into the wave's own slot
+__device__ __forceinline__ void gx_amax_publish(float m, float* cell) {
+    gx_amax_publish_slot(m, cell, (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) & (GX_AMAX_SLOTS - 1));
 }

@@ -31,6 +31,8 @@
  *                               (default: from 2.5 tiles per CU on; gi_b3p_enable)
  *       GI_CHAIN_PACK_FUSED=0   the fp16x2 chain image as memset + gi_absmax + pack launches instead of one launch that
  *                               also writes the max |W| cells (read per call: the test of the fused launch compares both)
+ *       GI_X2N=0                fp16x2 forward / dgrad launches on gi_gemm_bf3_kernel instead of the column-split kernel
+ *                               (the same results bit for bit; read per launch: its test compares both)
  *       GI_GEMM_LOG=<file>      one line per GEMM launch (tools/gemm_launch_report.py); output only
  *     Variants that were measured and not adopted are in the git history, not behind switches
  *     (tools/experiments/README.md, "Retired switches").
