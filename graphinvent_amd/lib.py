@@ -138,6 +138,16 @@ class DropoutParams(C.Structure):                       # gi_dropout_params
                 ("a", C.c_float), ("b_keep", C.c_float), ("b_drop", C.c_float)]
 
 
+ROUTE_COUNTS = 4                                        # GI_ROUTE_COUNTS
+(ROUTE_ERR_VALUE, ROUTE_ERR_ONEHOT, ROUTE_ERR_ASYMMETRIC, ROUTE_ERR_MULTI_BOND, ROUTE_ERR_CONNECT, ROUTE_ERR_PADDING,
+ ROUTE_ERR_EMPTY) = 1, 2, 4, 8, 16, 32, 64               # GI_ROUTE_ERR_*
+
+
+class RouteDims(C.Structure):
+    """gi_route_dims"""
+    _fields_ = [(n, ci) for n in ("M", "N", "Fn", "Fe", "n_seg")] + [("seg", ci * 4), ("apd_width", ci)]
+
+
 # name -> (restype, argtypes); every symbol include/graphinvent_amd.h declares
 SIGNATURES = {
     "gi_abi_version": (ci, []),
@@ -239,6 +249,11 @@ SIGNATURES = {
     "gi_expand_slots2": (ci, [vp, ci, ci, vp, ci, vp, ci, ci, vp, ci, vp, ci, ci, vp]),
     "gi_compress_slots2_f": (ci, [vp, ci, ci, vp, ci, vp, ci, vp, ci, ci, vp, ci, vp, ci, vp, ci, ci, ci,
                                   cll, vp]),
+    "gi_route_plan_ws_bytes": (cll, [C.POINTER(RouteDims)]),
+    "gi_route_rows_ws_bytes": (cll, [ci, ci]),
+    "gi_route_plan": (ci, [C.POINTER(RouteDims), vp, vp, vp, vp, vp, vp, vp]),
+    "gi_route_expand": (ci, [C.POINTER(RouteDims), vp, vp, vp, vp, ci, C.c_ulonglong, vp, vp, vp, ci, vp, vp, vp]),
+    "gi_route_merge": (ci, [C.POINTER(RouteDims), vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]),
 }
 FUSE_GATES_V4, FUSE_DH_SCATTER, FUSE_TIER2_DSELU, FUSE_SLOTS = 1, 2, 4, 8  # GI_FUSE_*
 

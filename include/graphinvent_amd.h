@@ -890,6 +890,63 @@ int gi_ggnn_backward_phase(const gi_ggnn_dims* d, const float* const* params, co
                            void* side_stream, int phase);
 int gi_ggnn_first_readout_param(const gi_ggnn_dims* d);
 
+/* ------------------------------------------------------------------------------------------
+ * Decoding routes (gi_route.hip): from M whole molecules to the training rows the reference's preprocessing writes,
+ * `PreprocessingGraph.get_decoding_route_state(k)` for k = 0 .. n_edges + 1 (MolecularGraph.py:691-732: k = 0 the
+ * whole molecule with APD = terminate, k >= 1 the APD before the k-th `truncate_graph` and the graph after it), and
+ * the merge of byte-identical subgraphs `DataProcesser.get_subgraphs` intends (DataProcesser.py:204-231).
+ *
+ * nodes [M, N, Fn] and edges [M, N, N, Fe] are int8, 0 / 1, nodes in the reference's order (every node i > 0 has a
+ * lower neighbour), zero padded; a node's feature row is one-hot in each of the n_seg consecutive segments of sizes
+ * seg[] (atom type, formal charge, then implicit Hs and chirality when configured; util.py:26-47), which are the
+ * middle dimensions of dim_f_add = [N, seg.., Fe]; apd_width = N prod(seg) Fe + N Fe + 1 (GI_EINVAL otherwise).
+ * Limits: N <= GI_MAX_NODES, Fe <= GI_MAX_GROUPS (GI_ELIMIT).
+ *
+ * counts[GI_ROUTE_COUNTS] int32 (device): [0] OR of the error bits of all molecules, [1] rows of the call (the sum of
+ * the route lengths), [2] rows after the merge.  A molecule that violates the contract gets route length 0 and its
+ * GI_ROUTE_ERR_* bits in mol_err[m]; it contributes no rows, nothing faults and nothing is written out of bounds.
+ *
+ *   gi_route_plan    zeroes counts; lengths[M] = n_edges + 2 (0 if invalid), mol_err[M], counts[0..1]; the per-pair
+ *                    deletion steps and row offsets stay in plan_ws (gi_route_plan_ws_bytes).
+ *   gi_route_expand  rows [0, min(counts[1], rows_cap)) in molecule-major, step-minor order: out_nodes
+ *                    [rows_cap, N, Fn] and out_edges [rows_cap, N, N, Fe] int8; out_apd [rows_cap, apd_width] one-hot,
+ *                    GI_DTYPE_I8 or GI_DTYPE_F32 (NULL: not written); row_mol / row_step [rows_cap] int32 (-1 past the
+ *                    real rows, whose outputs are zero).  Every out_* buffer is written in whole aligned 16-byte
+ *                    pieces: it must be 16-byte aligned and its size rounded up to 16 bytes.  Also leaves each row's
+ *                    hot APD index and 64-bit content hash (AND hash_mask — ~0 in production; tests force collisions
+ *                    with fewer bits) in rows_ws (gi_route_rows_ws_bytes(rows_cap, merge)).
+ *   gi_route_merge   after gi_route_expand with the same rows_ws (allocated with merge = 1) and rows_cap, on its
+ *                    out_nodes / out_edges / row_mol / row_step: rows with identical bytes become one row at the place
+ *                    of their first occurrence, order kept; out_apd = the sum of their one-hot APDs (GI_DTYPE_I8 only
+ *                    for M <= 127, a sum may reach M); out_row_mol / out_row_step name the first occurrence;
+ *                    counts[2] = rows kept.  Same buffer sizes as gi_route_expand; rows past counts[2] are zero in
+ *                    out_nodes / out_edges / out_apd.  Rows are grouped by hash and confirmed by a byte compare; the
+ *                    result does not depend on launch timing (the sums are integer). */
+#define GI_ROUTE_COUNTS 4
+#define GI_ROUTE_ERR_VALUE 1        /* an entry of nodes or edges is not 0 / 1 */
+#define GI_ROUTE_ERR_ONEHOT 2       /* a node's feature row is not one-hot in every segment */
+#define GI_ROUTE_ERR_ASYMMETRIC 4   /* edges[i, j] != edges[j, i] */
+#define GI_ROUTE_ERR_MULTI_BOND 8   /* several bond types on one pair */
+#define GI_ROUTE_ERR_CONNECT 16     /* a node i > 0 without a neighbour of lower index */
+#define GI_ROUTE_ERR_PADDING 32     /* nodes are not a zero-padded prefix, or a bond touches padding or the diagonal */
+#define GI_ROUTE_ERR_EMPTY 64       /* no node at all */
+typedef struct {
+    int M, N, Fn, Fe;
+    int n_seg, seg[4];
+    int apd_width;
+} gi_route_dims;
+long long gi_route_plan_ws_bytes(const gi_route_dims* d);
+long long gi_route_rows_ws_bytes(int rows_cap, int merge);
+int gi_route_plan(const gi_route_dims* d, const signed char* nodes, const signed char* edges, void* plan_ws,
+                  int* lengths, int* mol_err, int* counts, void* stream);
+int gi_route_expand(const gi_route_dims* d, const signed char* nodes, const void* plan_ws, void* rows_ws,
+                    const int* counts, int rows_cap, unsigned long long hash_mask, signed char* out_nodes,
+                    signed char* out_edges, void* out_apd, int apd_dtype, int* row_mol, int* row_step, void* stream);
+int gi_route_merge(const gi_route_dims* d, void* rows_ws, int* counts, int rows_cap, const signed char* in_nodes,
+                   const signed char* in_edges, const int* in_row_mol, const int* in_row_step,
+                   signed char* out_nodes, signed char* out_edges, void* out_apd, int apd_dtype, int* out_row_mol,
+                   int* out_row_step, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
