@@ -2,10 +2,14 @@
 shipped preprocessed data (the committed .npz conversion of data/pre-training/gdb13_1K-debug/train.h5; the rows
 whose f_term entry is set) are the dataset, and their decoding routes are expanded on the device per batch:
 
-    int8 molecules (pinned host memory) -> RouteLoader (gi_route.hip: plan, expand, merge) -> gnn.mpnn.GGNN(constants)
-    -> apd_kl_loss -> FusedAdam
+    int8 molecules (pinned host memory) -> RouteLoader (gi_reorder.hip: a fresh node order; gi_route.hip: plan, expand,
+    merge) -> gnn.mpnn.GGNN(constants) -> apd_kl_loss -> FusedAdam
 
-    python examples/train_routes.py [--epochs 30] [--batch 64] [--model GGNN|AttGGNN] [--no-merge]
+    python examples/train_routes.py [--epochs 30] [--batch 64] [--model GGNN|AttGGNN] [--no-merge] [--reorder bfs|dfs]
+
+`--reorder` draws a new breadth- or depth-first node order for every molecule in every epoch on the device (route
+augmentation: the reference fixes one order per molecule at preprocessing time); without it the molecules are expanded
+in the order they are stored in.
 
 A user with only a preprocessed .h5 recovers the molecules the same way (`routes.molecules_from_rows` on the arrays
 of `loader.read_hdf_int8`); one with a `PreprocessingGraph` pipeline stores `get_graph_state()` of every molecule
@@ -26,7 +30,7 @@ from graphinvent_amd.loss import apd_kl_loss                      # noqa: E402
 from graphinvent_amd.optim import FusedAdam                       # noqa: E402
 
 
-def train(epochs=30, batch=64, model_name="GGNN", merge=True, seed=0, verbose=True):
+def train(epochs=30, batch=64, model_name="GGNN", merge=True, seed=0, verbose=True, reorder=None):
     d = np.load(os.path.join(ROOT, "tests", "golden", "gdb13_1K-debug_train.npz"))
     nodes, edges = routes.molecules_from_rows(d["nodes"], d["edges"], d["APDs"], unique=True)
     N, Fn = nodes.shape[1:]
@@ -36,7 +40,7 @@ def train(epochs=30, batch=64, model_name="GGNN", merge=True, seed=0, verbose=Tr
     cls = mpnn.GGNN if model_name == "GGNN" else mpnn.AttentionGGNN
     model = cls(constants_for(nodes, edges, d["APDs"])).to("cuda").train()
     opt = FusedAdam(model.parameters(), lr=1e-4)                  # defaults.py:120 init_lr
-    loader = routes.RouteLoader(nodes, edges, dim_f_add, dim_f_conn, batch, seed=seed, merge=merge)
+    loader = routes.RouteLoader(nodes, edges, dim_f_add, dim_f_conn, batch, seed=seed, merge=merge, reorder=reorder)
     steps = 0
     for epoch in range(epochs):                                   # the batch count varies with the epoch's order
         loader.set_epoch(epoch)
@@ -64,5 +68,6 @@ if __name__ == "__main__":
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--model", default="GGNN", choices=["GGNN", "AttGGNN"])
     ap.add_argument("--no-merge", action="store_true")
+    ap.add_argument("--reorder", default=None, choices=["bfs", "dfs"])
     a = ap.parse_args()
-    train(a.epochs, a.batch, a.model, not a.no_merge)
+    train(a.epochs, a.batch, a.model, not a.no_merge, reorder=a.reorder)

@@ -141,6 +141,8 @@ class DropoutParams(C.Structure):                       # gi_dropout_params
 ROUTE_COUNTS = 4                                        # GI_ROUTE_COUNTS
 (ROUTE_ERR_VALUE, ROUTE_ERR_ONEHOT, ROUTE_ERR_ASYMMETRIC, ROUTE_ERR_MULTI_BOND, ROUTE_ERR_CONNECT, ROUTE_ERR_PADDING,
  ROUTE_ERR_EMPTY) = 1, 2, 4, 8, 16, 32, 64               # GI_ROUTE_ERR_*
+ROUTE_ERR_RANK = 128                                    # GI_ROUTE_ERR_RANK (gi_route_reorder only)
+ROUTE_BFS, ROUTE_DFS = 0, 1                             # GI_ROUTE_BFS, GI_ROUTE_DFS
 
 
 class RouteDims(C.Structure):
@@ -254,6 +256,7 @@ SIGNATURES = {
     "gi_route_plan": (ci, [C.POINTER(RouteDims), vp, vp, vp, vp, vp, vp, vp]),
     "gi_route_expand": (ci, [C.POINTER(RouteDims), vp, vp, vp, vp, ci, C.c_ulonglong, vp, vp, vp, ci, vp, vp, vp]),
     "gi_route_merge": (ci, [C.POINTER(RouteDims), vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]),
+    "gi_route_reorder": (ci, [ci, ci, ci, ci, vp, vp, vp, C.c_ulonglong, C.c_ulonglong, vp, ci, vp, vp, vp, vp, vp]),
 }
 FUSE_GATES_V4, FUSE_DH_SCATTER, FUSE_TIER2_DSELU, FUSE_SLOTS = 1, 2, 4, 8  # GI_FUSE_*
 

@@ -10,8 +10,14 @@ and ``RouteLoader`` feeds a training loop from int8 molecules in pinned host mem
 A molecule is what ``PreprocessingGraph`` holds after ``node_remap`` and ``pad_graph_representation``
 (MolecularGraph.py:435-461, 616-633): ``nodes[N, Fn]`` and ``edges[N, N, Fe]``, int8, 0 / 1, nodes in the
 reference's (BFS / DFS) order so that every node i > 0 has a neighbour of lower index, zero padded; every node row
-one-hot per feature segment, ``edges`` symmetric with at most one bond type per pair.  SMILES parsing and the node
-ordering stay with RDKit and the reference; everything after them is here.
+one-hot per feature segment, ``edges`` symmetric with at most one bond type per pair.
+
+``reorder`` is ``node_remap`` itself, minus the source of the ranking: from a node ranking (given, or drawn on the
+device per molecule and epoch) it runs the reference's breadth- or depth-first search and ``reorder_nodes`` with the
+HIP kernel of ``csrc/gi_reorder.hip``, so molecules in ANY node order become valid input of ``expand``, and
+``RouteLoader(reorder=...)`` trains on a different decoding route of every molecule in every epoch — the reference
+draws one order per molecule at preprocessing time and keeps it.  Only SMILES parsing and RDKit's canonical ranking
+(``use_canon``; pass it as ``rank``) stay outside; everything after them is here.
 """
 from __future__ import annotations
 
@@ -34,8 +40,16 @@ ERROR_MESSAGES = {
 }
 
 
+#: bits only ``reorder`` sets, next to those of ERROR_MESSAGES it shares (there ROUTE_ERR_CONNECT means: not connected)
+REORDER_ERROR_MESSAGES = {
+    L.ROUTE_ERR_RANK: "a row of rank is not a permutation of 0 .. n_nodes - 1",
+}
+_ROUTES = {"bfs": L.ROUTE_BFS, "dfs": L.ROUTE_DFS}
+
+
 def describe_errors(bits: int) -> str:
-    return "; ".join(msg for bit, msg in ERROR_MESSAGES.items() if bits & bit)
+    return "; ".join(msg for table in (ERROR_MESSAGES, REORDER_ERROR_MESSAGES) for bit, msg in table.items()
+                     if bits & bit)
 
 
 def _as_numpy(x) -> np.ndarray:
@@ -269,6 +283,90 @@ def expand(nodes: torch.Tensor, edges: torch.Tensor, dim_f_add: Sequence[int], d
     return _finish(p, counts, int(n_rows), strict=invalid == "raise")
 
 
+def _enqueue_reorder(nodes: torch.Tensor, edges: torch.Tensor, route: str, rank: Optional[torch.Tensor], seed: int,
+                     epoch: int, mol_ids: Optional[torch.Tensor], want_order: bool):
+    """gi_route_reorder on the current stream of the inputs' device, with no host wait:
+    (nodes', edges', order or None, mol_err).  `rank` int32 [M, N] and `mol_ids` int64 [M] are on that device."""
+    lib, dev = L.load(), nodes.device
+    M, N, Fn = nodes.shape
+    Fe = edges.shape[3]
+    out_n, out_e = torch.empty_like(nodes), torch.empty_like(edges)
+    order = torch.empty((M, N), dtype=torch.int32, device=dev) if want_order else None
+    mol_err = torch.empty(M, dtype=torch.int32, device=dev)
+    L.check(lib.gi_route_reorder(M, N, Fn, Fe, nodes.data_ptr(), edges.data_ptr(),
+                                 None if rank is None else rank.data_ptr(), int(seed) & (2 ** 64 - 1),
+                                 int(epoch) & (2 ** 64 - 1), None if mol_ids is None else mol_ids.data_ptr(),
+                                 _ROUTES[route], out_n.data_ptr(), out_e.data_ptr(),
+                                 None if order is None else order.data_ptr(), mol_err.data_ptr(),
+                                 torch.cuda.current_stream(dev).cuda_stream), "gi_route_reorder")
+    return out_n, out_e, order, mol_err
+
+
+def reorder(nodes: torch.Tensor, edges: torch.Tensor, *, route: str = "bfs", rank=None, seed: int = 0,
+            epoch: int = 0, mol_ids=None, return_order: bool = False, invalid: str = "raise"):
+    """``PreprocessingGraph.node_remap`` (MolecularGraph.py:435-461) for ``M`` molecules in one launch, on the inputs'
+    device and the current stream: returns ``(nodes', edges')`` with ``nodes' = nodes[order]`` and ``edges' =
+    edges[order][:, order]``, zero padded (``reorder_nodes``, ``pad_graph_representation``), where ``order`` is the
+    reference's breadth- (``route="bfs"``) or depth-first (``"dfs"``) search from node ``rank[0]`` (the reference
+    passes ``atom_ranking[0]``, a rank VALUE, as the start index; so does this).  The input nodes may be in any
+    order; the output satisfies ``expand``'s contract.  ``return_order=True`` appends ``order`` (int32 ``[M, N]``: the
+    input index of every output node, -1 past the molecule's nodes).
+
+    ``rank`` (``[M, N]`` integers, tensor or array; the first ``n`` entries of a row count): a permutation of
+    ``0 .. n-1`` per molecule, higher = more important — the reference's ``atom_ranking``, e.g. RDKit's canonical
+    ranking.  ``rank=None`` draws it on the device, so nothing but the molecules crosses PCIe, as a pure function of
+    ``(seed, epoch, mol_ids[m], node)`` (``mol_ids`` defaults to ``0 .. M-1``; give the molecules' indices in the
+    dataset and a molecule's order in an epoch does not depend on batching, shuffling or the rank it lands on).
+
+    ``"dfs"`` equals the reference's ``depth_first_search`` node for node.  ``"bfs"`` emits every level in ascending
+    input index.  Its level sets are the reference's, but the reference appends a level as a Python ``set``
+    (MolecularGraph.py:374), in CPython's hash-table order: that is ascending index while all ids are below the
+    table size (8 slots for up to 4 elements), so the two agree for molecules of up to 8 nodes and differ inside
+    levels for part of the larger ones.  CPython's probing sequence is NOT reproduced; every order produced is a
+    valid BFS order.  As in the reference the ranking reaches a BFS through the start node only: ``"bfs"`` has at
+    most ``n`` distinct orders per molecule, ``"dfs"`` many more.
+
+    A molecule with an entry other than 0 / 1, nodes that are not a zero-padded prefix, asymmetric edges, no node,
+    several connected components (the reference's loops never return on those) or a ``rank`` row that is not a
+    permutation raises ``ValueError`` naming the rule, after ONE read-back of the error words.  ``invalid="skip"``
+    reads nothing back: such molecules are copied through unchanged (``order`` = identity) and the per-molecule
+    error bits (int32 ``[M]``, ``lib.ROUTE_ERR_*``) are appended to the result.
+    """
+    if invalid not in ("raise", "skip"):
+        raise ValueError("invalid must be 'raise' or 'skip'")
+    if route not in _ROUTES:
+        raise ValueError("route must be 'bfs' or 'dfs'")
+    nodes, edges = _check_inputs(nodes, edges)
+    M, N, _ = nodes.shape
+    if N > L.GI_MAX_NODES:
+        raise ValueError(f"max_n_nodes = {N} exceeds the kernels' limit GI_MAX_NODES = {L.GI_MAX_NODES}")
+    if edges.shape[3] > L.GI_MAX_GROUPS:
+        raise ValueError(f"n_edge_features = {edges.shape[3]} exceeds the kernels' limit GI_MAX_GROUPS = "
+                         f"{L.GI_MAX_GROUPS}")
+    dev = nodes.device
+    if rank is not None:
+        rank = torch.as_tensor(rank)
+        if tuple(rank.shape) != (M, N) or rank.dtype.is_floating_point:
+            raise ValueError(f"rank must be integers of shape [M, N] = {[M, N]}, got {tuple(rank.shape)}")
+        rank = rank.to(device=dev, dtype=torch.int32).contiguous()
+    if mol_ids is not None:
+        mol_ids = torch.as_tensor(mol_ids)
+        if tuple(mol_ids.shape) != (M,) or mol_ids.dtype.is_floating_point:
+            raise ValueError(f"mol_ids must be {M} integers, got shape {tuple(mol_ids.shape)}")
+        mol_ids = mol_ids.to(device=dev, dtype=torch.int64).contiguous()
+    with torch.cuda.device(dev):
+        out_n, out_e, order, mol_err = _enqueue_reorder(nodes, edges, route, rank, seed, epoch, mol_ids, return_order)
+        if invalid == "raise" and M:
+            bits = int(np.bitwise_or.reduce(mol_err.cpu().numpy()))        # the read-back
+            if bits:
+                what = describe_errors(bits & ~L.ROUTE_ERR_CONNECT)
+                if bits & L.ROUTE_ERR_CONNECT:
+                    what = "; ".join(filter(None, [what, "a molecule is not connected"]))
+                raise ValueError("invalid molecule(s) in the batch: " + what)
+    out = (out_n, out_e) + ((order,) if return_order else ())
+    return out + ((mol_err,) if invalid == "skip" else ())
+
+
 def plan_batches(lengths: np.ndarray, batch_size: int, rank: int = 0, world_size: int = 1, seed: int = 0,
                  epoch: int = 0, shuffle: bool = True):
     """The molecule indices of every batch of an epoch on one rank (host arithmetic; see ``RouteLoader``)."""
@@ -309,13 +407,22 @@ class RouteLoader:
     * Pipelining: the copy and expansion of batch k + 2 are enqueued on the loader's side stream, and batch k + 1's
       merged row count is read back there and its compaction counts handed to ``ops.prefetch_compact``, while step k
       runs.  The consumer's stream only ever waits for an event of the side stream, never for the host.
+    * ``reorder="bfs"`` / ``"dfs"`` (default ``None``: the molecules as stored): every batch goes through ``reorder``
+      on the side stream between the copy and the expansion, with the ranking drawn on the device from the loader's
+      ``seed``, the epoch and the molecule's index in the dataset.  Each epoch then trains on a different decoding
+      route of every molecule, the same whatever the rank, world size or batch size, and the stored molecules may
+      be in any node order.  Route lengths depend on the bond count only, so batches and row counts are unchanged;
+      a molecule the reorder refuses (say, a disconnected one) is passed on unchanged and reported by the expansion.
     """
 
     def __init__(self, nodes, edges, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], batch_size: int,
                  rank: int = 0, world_size: int = 1, seed: int = 0, shuffle: bool = True,
-                 device: Optional[str] = "cuda", merge: bool = True, prefetch_compact: bool = True):
+                 device: Optional[str] = "cuda", merge: bool = True, prefetch_compact: bool = True,
+                 reorder: Optional[str] = None):
         if not 0 <= rank < world_size:
             raise ValueError("rank out of range")
+        if reorder is not None and reorder not in _ROUTES:
+            raise ValueError("reorder must be None, 'bfs' or 'dfs'")
         n, e = _as_numpy(nodes), _as_numpy(edges)
         if n.dtype != np.int8 or e.dtype != np.int8:
             raise TypeError("molecules are int8 arrays (the dtype of the preprocessed HDF)")
@@ -330,7 +437,7 @@ class RouteLoader:
         self.dims = _route_dims(0, n.shape[1], n.shape[2], e.shape[3], dim_f_add, dim_f_conn)
         self._dim_f_add, self._dim_f_conn = list(dim_f_add), list(dim_f_conn)
         self.batch_size, self.rank, self.world, self.seed, self.shuffle = int(batch_size), rank, world_size, seed, shuffle
-        self.merge, self.prefetch_compact = merge, prefetch_compact
+        self.merge, self.prefetch_compact, self.reorder = merge, prefetch_compact, reorder
         self.epoch = 0
         self._nodes = torch.from_numpy(np.ascontiguousarray(n)).pin_memory()
         self._edges = torch.from_numpy(np.ascontiguousarray(e)).pin_memory()
@@ -360,8 +467,9 @@ class RouteLoader:
         return [idx.copy() for idx, _ in self._epoch_plan()]
 
     # ---- pipeline stages ----------------------------------------------------------------------------------
-    def _launch(self, idx: np.ndarray, rows: int, slot: int):
-        """Gather the molecules into a pinned staging slot; copy, plan, expand and merge on the side stream."""
+    def _launch(self, idx: np.ndarray, rows: int, slot: int, epoch: int = 0):
+        """Gather the molecules into a pinned staging slot; copy, (reorder,) plan, expand and merge on the side
+        stream."""
         k = idx.shape[0]
         if self._stage is None:
             cap = max(self.batch_size // 2, 1)                # a route has at least 2 rows
@@ -369,6 +477,9 @@ class RouteLoader:
             self._stage = [(mk(self._nodes), mk(self._edges)) for _ in range(3)]
             self._counts_host = [torch.empty(L.ROUTE_COUNTS, dtype=torch.int32).pin_memory() for _ in range(3)]
             self.pinned_bytes += sum(a.numel() + b.numel() for a, b in self._stage)
+            if self.reorder is not None:                      # the batch's dataset indices: the kernel's mol_ids
+                self._stage_ids = [torch.empty(cap, dtype=torch.int64).pin_memory() for _ in range(3)]
+                self.pinned_bytes += 3 * cap * 8
         sn, se = self._stage[slot]
         np.take(self._nodes.numpy().reshape(self.n_molecules, -1), idx, axis=0,
                 out=sn.numpy().reshape(sn.shape[0], -1)[:k])
@@ -378,6 +489,11 @@ class RouteLoader:
         with torch.cuda.device(self.device), torch.cuda.stream(self._stream):
             dn = sn[:k].to(self.device, non_blocking=True)
             de = se[:k].to(self.device, non_blocking=True)
+            if self.reorder is not None:
+                ids = self._stage_ids[slot]
+                ids.numpy()[:k] = idx
+                dn, de, _, _ = _enqueue_reorder(dn, de, self.reorder, None, self.seed, epoch,
+                                                ids[:k].to(self.device, non_blocking=True), False)
             p = _enqueue(dn, de, d, self.merge, rows)
             host = self._counts_host[slot]
             host.copy_(p.counts, non_blocking=True)
@@ -408,11 +524,11 @@ class RouteLoader:
         return out
 
     def __iter__(self) -> Iterator[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
-        batches = self._epoch_plan()
+        batches, epoch = self._epoch_plan(), self.epoch
         cur = torch.cuda.current_stream(self.device)
         launched, ready = None, None
         for i, (idx, rows) in enumerate(batches):
-            nxt = self._launch(idx, rows, i % 3)
+            nxt = self._launch(idx, rows, i % 3, epoch)
             if launched is not None:
                 fin = self._finalise(launched)
                 if ready is not None:

@@ -947,6 +947,35 @@ int gi_route_merge(const gi_route_dims* d, void* rows_ws, int* counts, int rows_
                    signed char* out_nodes, signed char* out_edges, void* out_apd, int apd_dtype, int* out_row_mol,
                    int* out_row_step, void* stream);
 
+/* Node reordering (gi_reorder.hip): what `PreprocessingGraph.node_remap` (MolecularGraph.py:435-461) does once it has
+ * a node ranking, for M molecules in one launch: a breadth- or depth-first search (:328-433) from node rank[0], then
+ * `reorder_nodes` and `pad_graph_representation` (:592-633).  nodes [M, N, Fn] / edges [M, N, N, Fe] as above, except
+ * that the nodes may be in ANY order; out_nodes / out_edges (same shapes, not the inputs) hold nodes[order] and
+ * edges[order][:, order], zero padded, which satisfy gi_route_plan's order rule.  No alignment or padding is asked of
+ * any buffer.
+ *
+ * rank [M, N] int32 (device): the first n entries of a row are a permutation of 0 .. n-1, higher = more important
+ * (the reference's `atom_ranking`); NULL draws it on the device from (seed, epoch, id), id = mol_ids[m] (int64,
+ * device) or m when mol_ids is NULL: s = mix64(mix64(seed) + epoch), key_i = mix64(s ^ (id << 8 | i)) with the
+ * splitmix64 step mix64 and 64-bit wrap-around, rank_i = the number of j < n with (key_j, j) < (key_i, i).
+ *
+ * GI_ROUTE_DFS is the reference's loop, node for node.  GI_ROUTE_BFS emits every level in ascending input index: the
+ * level SETS are the reference's, whose order inside a level is CPython's set iteration order (equal to this one for
+ * molecules of up to 8 nodes, not in general beyond).  The ranking reaches a BFS through the start node only.
+ *
+ * order [M, N] int32 (NULL: not written): the input index of every output node, -1 past the molecule's n nodes.
+ * mol_err [M]: 0, or the GI_ROUTE_ERR_* bits of a molecule the kernel refuses — an entry not 0 / 1 (VALUE), nodes
+ * not a zero-padded prefix or a bond on padding or the diagonal (PADDING), asymmetric edges, no node (EMPTY), not
+ * connected (CONNECT), `rank` not a permutation (RANK).  Such a molecule is copied through unchanged, order = the
+ * identity; every loop is bounded by the dims, nothing faults and nothing is written out of bounds. */
+#define GI_ROUTE_ERR_RANK 128       /* a given rank row is not a permutation of 0 .. n-1 */
+#define GI_ROUTE_BFS 0
+#define GI_ROUTE_DFS 1
+int gi_route_reorder(int M, int N, int Fn, int Fe, const signed char* nodes, const signed char* edges,
+                     const int* rank, unsigned long long seed, unsigned long long epoch, const long long* mol_ids,
+                     int mode, signed char* out_nodes, signed char* out_edges, int* order, int* mol_err,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
