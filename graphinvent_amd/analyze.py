@@ -1,0 +1,313 @@
+"""
+Read-out of generated molecules on the device: the tensor bookkeeping of ``Analyzer.get_molecular_properties``
+(Analyzer.py:311-599) and of ``GraphGenerator.graph_to_graph`` / ``GraphGeneratorRL.graph_to_graph``
+(GraphGenerator.py:659-804, GraphGeneratorRL.py:725-), which the reference does molecule by molecule from Python:
+``int(torch.sum(edges[node, :, bond]))`` for every molecule, node and bond type, a ``torch.nonzero`` per node and per
+graph and ``.item()`` on every bond index, i.e. one device-to-host synchronisation per atom and per bond.
+
+``molecular_properties(nodes, edges, n_nodes, groups, ...)`` is one launch (``gi_mol_properties``) over the generator's
+own tensors and returns the dictionary entries of ``get_molecular_properties`` that need no RDKit, as fp32 tensors on
+the device with the reference's shapes and values.  ``fraction_unique``, ``fraction_valid`` and
+``fraction_valid_properly_terminated`` are NOT produced: they come from RDKit's sanitisation and SMILES, and the
+caller merges them into the dictionary.
+
+``decode(nodes, edges, n_nodes, groups)`` is one launch (``gi_mol_decode``) that writes what ``_graph_to_mol`` reads
+out of the tensors: per atom the index inside each one-hot segment, per graph the bond triples in
+``torch.nonzero``'s order, and a status word for what the reference would misread or raise on.  ``.host()`` brings all
+of it to the host with one copy and one synchronisation; ``records`` maps the indices through the constants' tables
+into the arguments of ``Chem.Atom`` / ``AddBond``.  Building ``rdkit.Chem.RWMol`` objects stays in the caller.
+
+Counts are summed as integers on the device and converted once (the exact integer as fp32, then one fp32 division):
+bit for bit the reference's values while every count is below 2**24.  Beyond that the reference's own fp32
+accumulation (``hist[i] += 1``) stops being exact, e.g. it stays at 16777216 for ever; the counts here stay exact
+integers (rounded once to fp32), which is deliberately not the reference's result.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Iterator, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import lib as L
+from .generator import _host_sync_allowed
+
+#: status bits of ``decode`` (``lib.MOL_*``), with what the reference does in that case
+STATUS_MESSAGES = {
+    L.MOL_ONEHOT: "a node row below n_nodes does not have exactly one set entry per segment (the reference reads "
+                  "the wrong entries or raises IndexError)",
+    L.MOL_BOND_PAST_N: "a bond touches a node >= n_nodes (the reference raises KeyError in node_to_idx)",
+    L.MOL_OVERFLOW: "more than max_bonds bonds (only the first max_bonds are written; n_bonds holds the true count)",
+    L.MOL_VALUE: "an entry is neither 0 nor 1",
+    L.MOL_MULTI_BOND: "a pair of atoms carries several bond types (RDKit's AddBond refuses the second)",
+}
+
+
+def describe_status(bits: int) -> str:
+    return "; ".join(msg for bit, msg in STATUS_MESSAGES.items() if bits & bit) or "well-formed"
+
+
+def _check_inputs(what: str, nodes, edges, n_nodes, groups: Sequence[int], need_n_nodes: bool):
+    """-> (G, N, Fn, Fe, dtype code, n_nodes (or None), its byte width, groups as ints)."""
+    for name, x in (("nodes", nodes), ("edges", edges)):
+        if not isinstance(x, torch.Tensor):
+            raise TypeError(f"{what}: {name} must be a torch tensor, got {type(x).__name__}")
+        if not x.is_cuda:
+            raise RuntimeError(f"{what} needs CUDA (ROCm) tensors ({name} is on {x.device}): the MI355X HIP path has "
+                               "no CPU fallback")
+    if nodes.dim() != 3 or edges.dim() != 4:
+        raise ValueError(f"{what}: nodes must be [G, N, Fn] and edges [G, N, N, Fe]")
+    G, N, Fn = nodes.shape
+    Fe = edges.shape[3]
+    if tuple(edges.shape) != (G, N, N, Fe):
+        raise ValueError(f"{what}: edges {tuple(edges.shape)} does not match nodes {tuple(nodes.shape)}")
+    if nodes.dtype != edges.dtype or nodes.dtype not in (torch.float32, torch.int8):
+        raise TypeError(f"{what}: nodes and edges must both be float32 or both int8, got {nodes.dtype} / {edges.dtype}")
+    if edges.device != nodes.device:
+        raise ValueError(f"{what}: edges is on {edges.device}, nodes on {nodes.device}")
+    if not nodes.is_contiguous() or not edges.is_contiguous():
+        raise ValueError(f"{what}: nodes and edges must be contiguous (they are read in place, once)")
+    groups = [int(g) for g in groups]
+    if not 2 <= len(groups) <= 4 or min(groups) < 1 or sum(groups) != Fn:
+        raise ValueError(f"{what}: groups {groups} must be 2 to 4 positive segment sizes (atom type, formal charge, "
+                         f"[implicit H], [chirality]) that sum to Fn = {Fn}")
+    if N < 1 or Fn < 1 or Fe < 1 or N > L.GI_MAX_NODES or Fe > L.GI_MAX_GROUPS or Fn > L.ANALYZE_MAX_FN:
+        raise ValueError(f"{what}: needs 1 <= N <= {L.GI_MAX_NODES}, 1 <= Fe <= {L.GI_MAX_GROUPS}, 1 <= Fn <= "
+                         f"{L.ANALYZE_MAX_FN}; got N {N}, Fn {Fn}, Fe {Fe}")
+    nn_bytes = 1
+    if n_nodes is None:
+        if need_n_nodes:
+            raise ValueError(f"{what}: n_nodes is required")
+    else:
+        if not isinstance(n_nodes, torch.Tensor):
+            raise TypeError(f"{what}: n_nodes must be a torch tensor")
+        if not n_nodes.is_cuda or n_nodes.device != nodes.device:
+            raise RuntimeError(f"{what}: n_nodes must be a CUDA tensor on {nodes.device} (no CPU fallback)")
+        if tuple(n_nodes.shape) != (G,):
+            raise ValueError(f"{what}: n_nodes has shape {tuple(n_nodes.shape)}, expected ({G},)")
+        if n_nodes.dtype not in (torch.int8, torch.int32, torch.int64):
+            raise TypeError(f"{what}: n_nodes must be int8 (what build_graphs leaves), int32 or int64, got "
+                            f"{n_nodes.dtype}")
+        if not n_nodes.is_contiguous():
+            raise ValueError(f"{what}: n_nodes must be contiguous")
+        nn_bytes = n_nodes.element_size()
+    dtype = L.DTYPE_I8 if nodes.dtype == torch.int8 else L.DTYPE_F32
+    return G, N, Fn, Fe, dtype, n_nodes, nn_bytes, groups
+
+
+def molecular_properties(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Optional[torch.Tensor],
+                         groups: Sequence[int], *, termination: Optional[torch.Tensor] = None,
+                         epoch_key: Optional[str] = None, max_n_nodes: Optional[int] = None,
+                         n_imp_H: int = 0, n_chirality: int = 0, use_imp_H: Optional[bool] = None,
+                         use_chirality: Optional[bool] = None) -> dict:
+    """The entries of ``Analyzer.get_molecular_properties`` (Analyzer.py:311-599) that need no RDKit, in one launch.
+
+    ``nodes`` [G, N, Fn] / ``edges`` [G, N, N, Fe]: contiguous device tensors, both fp32 or both int8 (e.g. a
+    generator's ``generated_nodes`` / ``generated_edges``, or the int8 molecule arrays of ``routes.RouteLoader`` for
+    ``evaluate_training_set``).  ``n_nodes`` [G] int8 / int32 / int64; ``None`` derives it as the number of non-zero
+    node rows (the model's node mask).  ``groups``: the sizes of the one-hot segments of a node row in the
+    reference's order — atom type, formal charge, [implicit H], [chirality] — i.e. the differences of
+    ``util.get_feature_vector_indices()``.  With three groups, ``use_imp_H`` / ``use_chirality`` say which optional
+    segment the third one is (default: implicit H unless ``use_chirality`` is set alone).  An absent segment is the
+    reference's ``[0] * n`` list of length ``n_imp_H`` / ``n_chirality``.  ``max_n_nodes`` (default N) sizes
+    ``n_nodes_hist``.  ``termination`` [G] (int8 or float) adds ``fraction_properly_terminated``.
+
+    Returns ``{name: value}``, or ``{(epoch_key, name): value}`` when ``epoch_key`` is given, for ``n_nodes_hist``
+    [max_n_nodes + 1], ``avg_n_nodes``, ``atom_type_hist``, ``formal_charge_hist``, ``numh_hist``,
+    ``chirality_hist``, ``n_edges_hist`` [10], ``avg_n_edges``, ``edge_feature_hist`` [Fe] and (with
+    ``termination``) ``fraction_properly_terminated``: fp32 tensors on the device (views of one buffer), quirks
+    included — a node of degree 0 is counted in the LAST bin of ``n_edges_hist``, the column sums run over all N
+    rows, ``edge_feature_hist`` halves the whole plane's sum.  Nothing is read back and nothing synchronises.
+
+    NOT produced: ``fraction_unique``, ``fraction_valid``, ``fraction_valid_properly_terminated``.  They come from
+    RDKit; merge them into the dictionary in the caller.  Values are the reference's bit for bit while every count
+    is below 2**24 (see the module docstring for what happens beyond).  G = 0 returns zeros without a launch (the
+    reference raises)."""
+    what = "molecular_properties"
+    G, N, Fn, Fe, dtype, n_nodes, nn_bytes, groups = _check_inputs(what, nodes, edges, n_nodes, groups, False)
+    H = (N if max_n_nodes is None else int(max_n_nodes)) + 1
+    if not 1 <= H <= L.ANALYZE_MAX_HIST + 1:
+        raise ValueError(f"{what}: max_n_nodes must be in [0, {L.ANALYZE_MAX_HIST}]")
+    if len(groups) == 3:
+        if use_imp_H is None and use_chirality is None:
+            use_imp_H, use_chirality = True, False
+        elif use_imp_H is None:
+            use_imp_H = not use_chirality
+        elif use_chirality is None:
+            use_chirality = not use_imp_H
+        if bool(use_imp_H) == bool(use_chirality):
+            raise ValueError(f"{what}: three groups hold exactly one of implicit H and chirality")
+    else:
+        use_imp_H = use_chirality = len(groups) == 4
+    term_dtype = L.DTYPE_I8
+    if termination is not None:
+        if not isinstance(termination, torch.Tensor) or not termination.is_cuda or termination.device != nodes.device:
+            raise RuntimeError(f"{what}: termination must be a CUDA tensor on {nodes.device} (no CPU fallback)")
+        if tuple(termination.shape) != (G,):
+            raise ValueError(f"{what}: termination has shape {tuple(termination.shape)}, expected ({G},)")
+        if termination.dtype != torch.int8:
+            termination = termination.float()
+            term_dtype = L.DTYPE_F32
+        termination = termination.contiguous()
+    dev = nodes.device
+    nb = H + Fn + L.ANALYZE_EDGE_BINS + Fe
+    out = torch.zeros(nb + 3, dtype=torch.float32, device=dev)
+    if G > 0:
+        totals = torch.zeros(nb + 2, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            L.check(L.load().gi_mol_properties(
+                G, N, Fn, Fe, nodes.data_ptr(), edges.data_ptr(), dtype,
+                None if n_nodes is None else n_nodes.data_ptr(), nn_bytes,
+                None if termination is None else termination.data_ptr(), term_dtype, H - 1, totals.data_ptr(),
+                out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "gi_mol_properties")
+    col = out[H:H + Fn]
+    off = np.cumsum([0] + groups).tolist()
+    seg = [col[off[k]:off[k + 1]] for k in range(len(groups))]
+    third = seg[2] if len(groups) >= 3 else None
+    props = {
+        "n_nodes_hist": out[:H],
+        "avg_n_nodes": out[nb],
+        "atom_type_hist": seg[0],
+        "formal_charge_hist": seg[1],
+        "n_edges_hist": out[H + Fn:H + Fn + L.ANALYZE_EDGE_BINS],
+        "avg_n_edges": out[nb + 1],
+        "edge_feature_hist": out[H + Fn + L.ANALYZE_EDGE_BINS:nb],
+        "numh_hist": third if use_imp_H else [0] * int(n_imp_H),
+        "chirality_hist": seg[-1] if use_chirality else [0] * int(n_chirality),
+    }
+    if termination is not None:
+        props["fraction_properly_terminated"] = out[nb + 2]
+    if epoch_key is not None:
+        props = {(epoch_key, k): v for k, v in props.items()}
+    return props
+
+
+class DecodedMolecules:
+    """What ``decode`` wrote, on the device: ``atoms`` [G, N, S] int8, ``bonds`` [G, max_bonds, 3] int16, ``n_bonds``
+    [G] int32 and ``status`` [G] int32, views of one byte buffer so that ``host()`` needs one copy."""
+
+    def __init__(self, buf: torch.Tensor, G: int, N: int, S: int, max_bonds: int):
+        self._buf, self._host, self._pinned = buf, None, None
+        self.G, self.N, self.S, self.max_bonds = G, N, S, max_bonds
+        self.atoms, self.bonds, self.n_bonds, self.status = self._views(buf, torch)
+
+    @staticmethod
+    def nbytes(G: int, N: int, S: int, max_bonds: int) -> int:
+        return 8 * G + 6 * G * max_bonds + G * N * S        # status | n_bonds | bonds | atoms: each aligned to itself
+
+    def _views(self, buf, xp):
+        G, N, S, mb = self.G, self.N, self.S, self.max_bonds
+        o_n, o_b, o_a = 4 * G, 8 * G, 8 * G + 6 * G * mb
+        status, n_bonds = buf[:o_n].view(xp.int32), buf[o_n:o_b].view(xp.int32)
+        bonds, atoms = buf[o_b:o_a].view(xp.int16).reshape(G, mb, 3), buf[o_a:].view(xp.int8).reshape(G, N, S)
+        return atoms, bonds, n_bonds, status
+
+    def host(self):
+        """-> numpy ``(atoms, bonds, n_bonds, status)``: ONE asynchronous copy of all four arrays into pinned memory
+        and ONE synchronisation (of the current stream), done once and kept."""
+        if self._host is None:
+            dev = self._buf.device
+            with _host_sync_allowed():                  # the read-out's one wait, under a caller's sync debug mode
+                pinned = torch.empty(self._buf.numel(), dtype=torch.uint8, pin_memory=True)
+                if self.G > 0:
+                    stream = torch.cuda.current_stream(dev)
+                    with torch.cuda.device(dev):
+                        pinned.copy_(self._buf, non_blocking=True)
+                    stream.synchronize()
+            self._pinned = pinned                       # the arrays are views of it
+            self._host = self._views(pinned.numpy(), np)
+        return self._host
+
+    def molecule(self, i: int):
+        """-> ``(atoms [n, S], bonds [min(n_bonds, max_bonds), 3], status)`` of graph ``i`` on the host, ``n`` being
+        the rows that are not -1 throughout (``n_nodes`` unless a row below it is empty, status bit 1)."""
+        atoms, bonds, n_bonds, status = self.host()
+        a = atoms[i]
+        live = np.flatnonzero((a >= 0).any(axis=1))
+        n = int(live[-1]) + 1 if live.size else 0
+        return a[:n], bonds[i, :min(int(n_bonds[i]), self.max_bonds)], int(status[i])
+
+    def __len__(self):
+        return self.G
+
+
+def decode(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: torch.Tensor, groups: Sequence[int], *,
+           max_bonds: Optional[int] = None, strict: bool = False) -> DecodedMolecules:
+    """What ``graph_to_graph`` (GraphGenerator.py:659-804) reads out of the tensors, for all G graphs in one launch;
+    inputs as ``molecular_properties`` (``n_nodes`` required).
+
+    ``atoms`` [G, N, len(groups)] int8: for a node below ``n_nodes`` the index INSIDE each segment of that segment's
+    set entry — for a well-formed row what ``_features_to_atom`` derives from ``nonzero_idc[0]``, ``[1]``, ``[2]``,
+    ``[-1]`` minus the segment offsets (a segment with several set entries gives the first, one without gives -1) —
+    and -1 for the other nodes.  ``bonds`` [G, max_bonds, 3] int16 (``max_bonds`` defaults to 2 N, padded with -1)
+    and ``n_bonds`` [G]: the triples (i, j, bond type), i < j, of the non-zero entries of the whole N x N x Fe
+    tensor in the order of ``torch.nonzero(edge_features * edge_mask)``.  ``status`` [G] int32, bits ``lib.MOL_*``:
+    1 a node row below ``n_nodes`` is not one-hot per segment, 2 a bond touches a node >= ``n_nodes`` (the reference
+    raises ``KeyError``), 4 more than ``max_bonds`` bonds (the first ``max_bonds`` are kept, ``n_bonds`` is the true
+    count), 8 an entry is neither 0 nor 1, 16 a pair carries several bond types (all are emitted).
+
+    Nothing is read back: ``.host()`` of the returned object does that with one copy and one synchronisation.
+    ``strict=True`` does so at once and raises ``ValueError`` naming the first graph whose status is non-zero; the
+    default only returns the status, because the generation loop's dummy graph 0 is legitimately malformed."""
+    what = "decode"
+    G, N, Fn, Fe, dtype, n_nodes, nn_bytes, groups = _check_inputs(what, nodes, edges, n_nodes, groups, True)
+    if max(groups) > 127:
+        raise ValueError(f"{what}: a segment of more than 127 entries does not fit the int8 atom records")
+    mb = 2 * N if max_bonds is None else int(max_bonds)
+    if not 1 <= mb <= 1 << 20:
+        raise ValueError(f"{what}: max_bonds must be in [1, 2**20]")
+    S = len(groups)
+    dev = nodes.device
+    res = DecodedMolecules(torch.empty(DecodedMolecules.nbytes(G, N, S, mb), dtype=torch.uint8, device=dev),
+                           G, N, S, mb)
+    if G > 0:
+        seg = (C.c_int * S)(*groups)
+        with torch.cuda.device(dev):
+            L.check(L.load().gi_mol_decode(
+                G, N, Fn, Fe, nodes.data_ptr(), edges.data_ptr(), dtype, n_nodes.data_ptr(), nn_bytes, S, seg, mb,
+                res.atoms.data_ptr(), res.bonds.data_ptr(), res.n_bonds.data_ptr(), res.status.data_ptr(),
+                torch.cuda.current_stream(dev).cuda_stream), "gi_mol_decode")
+    if strict:
+        status = res.host()[3]
+        bad = np.flatnonzero(status)
+        if bad.size:
+            g = int(bad[0])
+            raise ValueError(f"decode: graph {g} (of {bad.size} with a non-zero status) has status {int(status[g])}: "
+                             f"{describe_status(int(status[g]))}")
+    return res
+
+
+def records(decoded, atom_types: Sequence, formal_charge: Sequence, imp_H: Optional[Sequence] = None,
+            chirality: Optional[Sequence] = None, int_to_bondtype=None) -> Iterator[tuple]:
+    """Pure Python: per molecule ``(atoms, bonds)`` in the order ``_graph_to_mol`` (GraphGenerator.py:732-788) calls
+    ``AddAtom`` and ``AddBond``.  ``atoms`` is a list of ``(symbol, formal_charge, total_num_h, cip_code)``, the
+    arguments of ``Chem.Atom``, ``SetFormalCharge``, ``SetUnsignedProp("_TotalNumHs", .)`` and
+    ``SetProp("_CIPCode", .)`` (``None`` where ``imp_H`` / ``chirality`` is not given, i.e. the reference makes no
+    such call); ``bonds`` a list of ``(i, j, bond)`` with ``bond = int_to_bondtype[type]`` (the bare type index when
+    no table is given).  ``decoded``: ``decode``'s result, or the ``(atoms, bonds, n_bonds, status)`` arrays of its
+    ``.host()``.  The tables are the constants' ``atom_types``, ``formal_charge``, ``imp_H``, ``chirality`` and
+    ``int_to_bondtype``; the optional ones must be given exactly for the segments that ``groups`` held.  An index of
+    ``None`` instead of the pair is yielded for a graph with status bit 1 or 2: the reference's ``_graph_to_mol``
+    misreads such a graph or raises on it (``IndexError``, which ``graph_to_graph`` turns into ``mol = None``, or
+    ``KeyError``).  The generation loop's dummy graph 0 is such a graph."""
+    atoms, bonds, n_bonds, status = decoded.host() if hasattr(decoded, "host") else decoded
+    tables = [atom_types, formal_charge] + [t for t in (imp_H, chirality) if t is not None]
+    if atoms.shape[2] != len(tables):
+        raise ValueError(f"records: {atoms.shape[2]} segments were decoded but {len(tables)} tables are given")
+    h_col = 2 if imp_H is not None else None
+    c_col = len(tables) - 1 if chirality is not None else None
+    for g in range(atoms.shape[0]):
+        if int(status[g]) & (L.MOL_ONEHOT | L.MOL_BOND_PAST_N):
+            yield None
+            continue
+        mol_atoms = []
+        for row in atoms[g].tolist():
+            if row[0] < 0:
+                break                                   # past n_nodes
+            mol_atoms.append((atom_types[row[0]], formal_charge[row[1]],
+                              None if h_col is None else imp_H[row[h_col]],
+                              None if c_col is None else chirality[row[c_col]]))
+        kept = min(int(n_bonds[g]), bonds.shape[1])
+        mol_bonds = [(i, j, t if int_to_bondtype is None else int_to_bondtype[t]) for i, j, t in bonds[g, :kept].tolist()]
+        yield mol_atoms, mol_bonds

@@ -145,6 +145,10 @@ ROUTE_ERR_RANK = 128                                    # GI_ROUTE_ERR_RANK (gi_
 ROUTE_BFS, ROUTE_DFS = 0, 1                             # GI_ROUTE_BFS, GI_ROUTE_DFS
 
 
+ANALYZE_MAX_FN, ANALYZE_MAX_HIST, ANALYZE_EDGE_BINS = 512, 1024, 10      # GI_ANALYZE_*
+MOL_ONEHOT, MOL_BOND_PAST_N, MOL_OVERFLOW, MOL_VALUE, MOL_MULTI_BOND = 1, 2, 4, 8, 16   # GI_MOL_*
+
+
 class RouteDims(C.Structure):
     """gi_route_dims"""
     _fields_ = [(n, ci) for n in ("M", "N", "Fn", "Fe", "n_seg")] + [("seg", ci * 4), ("apd_width", ci)]
@@ -257,6 +261,8 @@ SIGNATURES = {
     "gi_route_expand": (ci, [C.POINTER(RouteDims), vp, vp, vp, vp, ci, C.c_ulonglong, vp, vp, vp, ci, vp, vp, vp]),
     "gi_route_merge": (ci, [C.POINTER(RouteDims), vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]),
     "gi_route_reorder": (ci, [ci, ci, ci, ci, vp, vp, vp, C.c_ulonglong, C.c_ulonglong, vp, ci, vp, vp, vp, vp, vp]),
+    "gi_mol_properties": (ci, [ci, ci, ci, ci, vp, vp, ci, vp, ci, vp, ci, ci, vp, vp, vp]),
+    "gi_mol_decode": (ci, [ci, ci, ci, ci, vp, vp, ci, vp, ci, ci, C.POINTER(ci), ci, vp, vp, vp, vp, vp]),
 }
 FUSE_GATES_V4, FUSE_DH_SCATTER, FUSE_TIER2_DSELU, FUSE_SLOTS = 1, 2, 4, 8  # GI_FUSE_*
 

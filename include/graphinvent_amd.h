@@ -976,6 +976,46 @@ int gi_route_reorder(int M, int N, int Fn, int Fe, const signed char* nodes, con
                      int mode, signed char* out_nodes, signed char* out_edges, int* order, int* mol_err,
                      void* stream);
 
+/* Read-out of molecules (gi_analyze.hip): the tensor bookkeeping of `Analyzer.get_molecular_properties`
+ * (Analyzer.py:311-599) and of `graph_to_graph` (GraphGenerator.py:659-804) for G graphs in one launch each.
+ * nodes [G, N, Fn] / edges [G, N, N, Fe]: contiguous, GI_DTYPE_F32 or GI_DTYPE_I8, entries expected to be 0 / 1 (the
+ * statistics take any integer of magnitude <= 128).  n_nodes [G]: integers of n_nodes_bytes = 1, 4 or 8 bytes.  No
+ * alignment is asked of any input.  N <= GI_MAX_NODES and Fe <= GI_MAX_GROUPS (GI_EINVAL otherwise); Fn <=
+ * GI_ANALYZE_MAX_FN (GI_ELIMIT).  G = 0 returns 0 without a launch and without touching any buffer.
+ *
+ * gi_mol_properties: with H = max_n_nodes + 1 (max_n_nodes <= GI_ANALYZE_MAX_HIST), out (fp32) =
+ *   [ n_nodes_hist H | column sums of the node rows Fn | n_edges_hist GI_ANALYZE_EDGE_BINS | edge_feature_hist Fe |
+ *     avg_n_nodes | avg_n_edges | fraction_properly_terminated ]
+ * as the reference defines them: hist[n_nodes] += 1 (a count outside [0, min(N, max_n_nodes)] is not binned); the
+ * column sums over ALL N rows; for every node < n_nodes the degree over all N columns and all bond types, clamped to
+ * the bin count and counted at degree - 1, degree 0 in the LAST bin; per bond type the sum of the whole [N, N] plane
+ * / 2; the averages sum(n count) / G and sum((bin + 1) count) / sum(count) (0 / 0 = NaN); sum(termination) / G
+ * (termination [G] GI_DTYPE_I8 or GI_DTYPE_F32; NULL: 0).  n_nodes = NULL counts the non-zero node rows instead.
+ * Counts are summed as integers (any order gives the same result) and converted once: the exact integer as fp32,
+ * then one fp32 division, which is the reference's value bit for bit while every count is below 2^24.
+ * totals: H + Fn + GI_ANALYZE_EDGE_BINS + Fe + 2 64-bit words, ZERO on entry; they hold the integer counts (then
+ * the termination sum and a launch counter) on return.
+ *
+ * gi_mol_decode (n_nodes required): seg[n_seg] (HOST, 2 <= n_seg <= 4, entries 1 .. 127, sum Fn) are the one-hot
+ * segments of a node row.  atoms [G, N, n_seg] int8: for a node < n_nodes the index inside each segment of its
+ * first non-zero entry (-1: none), -1 for the other nodes.  bonds [G, max_bonds, 3] int16: the triples (i, j, type)
+ * with i < j of the non-zero entries of the WHOLE [N, N, Fe] tensor, in row-major order of (i, j, type), padded
+ * with -1; n_bonds [G] their true number.  status [G]: the GI_MOL_* bits. */
+#define GI_ANALYZE_MAX_FN 512
+#define GI_ANALYZE_MAX_HIST 1024
+#define GI_ANALYZE_EDGE_BINS 10
+#define GI_MOL_ONEHOT 1             /* a node row < n_nodes without exactly one non-zero entry in some segment */
+#define GI_MOL_BOND_PAST_N 2        /* a bond touches a node >= n_nodes */
+#define GI_MOL_OVERFLOW 4           /* more than max_bonds bonds: the first max_bonds are written */
+#define GI_MOL_VALUE 8              /* an entry of nodes or edges is neither 0 nor 1 */
+#define GI_MOL_MULTI_BOND 16        /* a pair i < j carries several bond types (every triple is emitted) */
+int gi_mol_properties(int G, int N, int Fn, int Fe, const void* nodes, const void* edges, int dtype,
+                      const void* n_nodes, int n_nodes_bytes, const void* termination, int term_dtype,
+                      int max_n_nodes, unsigned long long* totals, float* out, void* stream);
+int gi_mol_decode(int G, int N, int Fn, int Fe, const void* nodes, const void* edges, int dtype,
+                  const void* n_nodes, int n_nodes_bytes, int n_seg, const int* seg, int max_bonds,
+                  signed char* atoms, short* bonds, int* n_bonds, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,318 @@
+"""-m gpu: the molecule read-out on the device (graphinvent_amd.analyze: gi_mol_properties, gi_mol_decode).
+
+Every comparison is exact: integers, and the fp32 histograms and averages byte for byte — against
+tests/golden/golden_analyze.npz (the unmodified reference) and, where the golden has no such input, against the numpy
+restatement tests/analyze_model.py, which tests/test_analyze_cpu.py pins to that golden."""
+import contextlib
+import os
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+from graphinvent_amd import analyze
+from graphinvent_amd import lib as L
+from tests import analyze_model as AM
+from tests.test_analyze_cpu import PROPS, assert_props_equal, load_case
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+DTYPES = [torch.float32, torch.int8]
+NP_OF = {torch.float32: np.float32, torch.int8: np.int8}
+
+
+def to_dev(x, dtype, misalign=3):
+    """x on the device as `dtype`, contiguous, its first byte `misalign` elements past an aligned allocation: no
+    graph of the batch then starts on a 16-byte boundary by accident."""
+    x = np.ascontiguousarray(x)
+    buf = torch.zeros(x.size + misalign, dtype=dtype, device=DEV)
+    view = buf[misalign:].view(x.shape)
+    view.copy_(torch.from_numpy(x.astype(NP_OF[dtype])))
+    assert view.is_contiguous()
+    return view
+
+
+def host_props(props: dict) -> dict:
+    return {k: v if isinstance(v, list) else v.cpu().numpy() for k, v in props.items()}
+
+
+def assert_same_props(got: dict, want: dict, what=""):
+    assert set(got) == set(want), (what, set(got) ^ set(want))
+    for k, w in want.items():
+        g = got[k]
+        if isinstance(w, list):
+            assert g == w, (what, k)
+            continue
+        w = np.asarray(w, np.float32)
+        assert g.dtype == np.float32 and g.shape == w.shape and g.tobytes() == w.tobytes(), (what, k, g, w)
+
+
+def assert_same_decode(dec, want, what=""):
+    got = dec.host()
+    for name, g, w in zip(("atoms", "bonds", "n_bonds", "status"), got, want):
+        assert g.dtype == w.dtype and g.shape == w.shape, (what, name, g.dtype, g.shape)
+        assert np.array_equal(g, w), (what, name, np.argwhere(g != w)[:5])
+
+
+# ---- goldens ------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "int8"])
+@pytest.mark.parametrize("name", ["generator", "imp_h_chirality", "handmade"])
+def test_both_entry_points_reproduce_the_reference_golden(golden_dir, name, dtype):
+    g = load_case(golden_dir, name)
+    nodes, edges = to_dev(g["nodes"], dtype), to_dev(g["edges"], dtype)
+    n_nodes, term = torch.from_numpy(g["n_nodes"]).to(DEV), torch.from_numpy(g["termination"]).to(DEV)
+    props = analyze.molecular_properties(nodes, edges, n_nodes, g["groups"], termination=term, **g["flags"])
+    for k, v in props.items():
+        assert isinstance(v, list) or (v.is_cuda and v.dtype == torch.float32), k
+    assert_props_equal(host_props(props), g, (name, dtype))
+    keyed = analyze.molecular_properties(nodes, edges, None, g["groups"], termination=term.float(), epoch_key="Epoch 3",
+                                         **g["flags"])                 # the node mask for n_nodes, a float termination
+    assert set(keyed) == {("Epoch 3", k) for k in PROPS}
+    assert_props_equal(host_props({k[1]: v for k, v in keyed.items()}), g, (name, dtype, "derived"))
+    dec = analyze.decode(nodes, edges, n_nodes, g["groups"], strict=True)
+    assert_same_decode(dec, (g["atoms"], g["bonds"], g["n_bonds"], g["status"]), (name, dtype))
+    t = g["tables"]
+    mols = list(analyze.records(dec, t["atom_types"], t["formal_charge"], t["imp_H"], t["chirality"],
+                                dict(enumerate(t["bondtypes"]))))
+    assert [AM.calls_of(*m) for m in mols] == g["calls"]
+    a, b, st = dec.molecule(len(dec) - 1)
+    n_last = int(g["n_nodes"][-1])
+    assert np.array_equal(a, g["atoms"][-1, :n_last]) and np.array_equal(b, g["bonds"][-1, :g["n_bonds"][-1]]) and st == 0
+
+
+# ---- chunk seams --------------------------------------------------------------------------------------------------
+
+def random_batch(G, N, Fe, groups, seed):
+    """Random 0/1 tensors (rows NOT one-hot: the status bits are part of the comparison), the bond density rising
+    from graph to graph, n_nodes anywhere in [0, N]."""
+    rng = np.random.default_rng(seed)
+    Fn = sum(groups)
+    nodes = (rng.random((G, N, Fn)) < 0.3).astype(np.int8)
+    dens = np.linspace(0.02, 0.35, G)[:, None, None, None]
+    edges = (rng.random((G, N, N, Fe)) < dens).astype(np.int8)
+    n_nodes = rng.integers(0, N + 1, size=G).astype(np.int32 if N > 127 else np.int8)     # (int8 ends at 127)
+    n_nodes[-1] = N
+    return nodes, edges, n_nodes
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "int8"])
+@pytest.mark.parametrize("G,N,Fe,groups", [(5, 13, 3, [5, 3]), (3, 88, 4, [4, 3, 2]), (2, 128, 4, [6, 3, 3, 2]),
+                                           (1, 1, 1, [1, 1])])
+def test_random_graphs_at_the_chunk_seams_equal_the_model(G, N, Fe, groups, dtype):
+    """13 x 13 x 3 = 507 entries per graph (no multiple of a 16-byte granule or of a 256-granule chunk, every graph
+    at another misalignment), 88 and the 128-node limit (several chunks per graph: the running base), 1 x 1 x 1
+    (a single ragged granule, no upper triangle).  max_bonds is the (lower) median bond count, so that some graphs overflow
+    and some do not: the kept prefix, its order, the true count and bit 4 are all in the comparison."""
+    nodes, edges, n_nodes = random_batch(G, N, Fe, groups, seed=N * 7 + G)
+    counts = (edges != 0)[:, np.triu(np.ones((N, N), bool), 1)].reshape(G, -1).sum(axis=1)
+    mb = max(1, int(np.sort(counts)[(G - 1) // 2]))
+    want = AM.decode(nodes, edges, n_nodes, groups, max_bonds=mb)
+    if N > 1:
+        assert (want[3] & L.MOL_OVERFLOW).any() and not (want[3] & L.MOL_OVERFLOW).all()
+    dn, de = to_dev(nodes, dtype), to_dev(edges, dtype)
+    assert de.data_ptr() % 16 != 0
+    for nn in (torch.from_numpy(n_nodes).to(DEV), torch.from_numpy(n_nodes.astype(np.int64)).to(DEV),
+               torch.from_numpy(n_nodes.astype(np.int32)).to(DEV)):               # every width n_nodes may have
+        assert_same_decode(analyze.decode(dn, de, nn, groups, max_bonds=mb), want, (G, N, dtype, nn.dtype))
+    term = (np.arange(G) % 2).astype(np.int8)
+    flags = dict(n_imp_H=4, n_chirality=2)
+    for given in (n_nodes, None):
+        nn = None if given is None else torch.from_numpy(given).to(DEV)
+        got = analyze.molecular_properties(dn, de, nn, groups, termination=torch.from_numpy(term).to(DEV), **flags)
+        assert_same_props(host_props(got), AM.properties(nodes, edges, given, groups, termination=term, **flags),
+                          (G, N, dtype, given is None))
+    # a shorter and a longer n_nodes_hist
+    for max_n in (N // 2, N + 3):
+        got = analyze.molecular_properties(dn, de, torch.from_numpy(n_nodes).to(DEV), groups, max_n_nodes=max_n)
+        assert_same_props(host_props(got), AM.properties(nodes, edges, n_nodes, groups, max_n_nodes=max_n), (N, max_n))
+
+
+def test_more_graphs_than_workgroups_and_asymmetric_halves():
+    """3000 graphs: the properties' workgroups take several graphs each; an odd plane sum gives a half."""
+    G, N, Fe, groups = 3000, 6, 2, [3, 2]
+    nodes, edges, n_nodes = random_batch(G, N, Fe, groups, seed=1)
+    if edges[..., 0].sum() % 2 == 0:
+        edges[0, 0, 1, 0] ^= 1                                         # one entry without its mirror image
+    want = AM.properties(nodes, edges, n_nodes, groups)
+    assert want["edge_feature_hist"][0] % 1 == 0.5
+    got = analyze.molecular_properties(to_dev(nodes, torch.int8), to_dev(edges, torch.int8),
+                                       torch.from_numpy(n_nodes).to(DEV), groups)
+    assert_same_props(host_props(got), want)
+
+
+def test_a_batch_past_two_gigabytes():
+    """int8, 128 nodes, 8 bond types: 131072 bytes per graph, 16400 graphs = 2.15e9 bytes, so the last graph's offset
+    does not fit 31 bits.  Only the last two graphs hold anything; the expectation is the model's on those two plus
+    the empty graphs' share of n_nodes_hist."""
+    G, N, Fe, groups = 16400, 128, 8, [5, 3]
+    tn, te, tk = random_batch(2, N, Fe, groups, seed=9)
+    te[:, :, :, 1:] = 0                                                # sparse enough for a small max_bonds
+    te[:, 40:, :, :] = 0
+    nodes = torch.zeros(G, N, 8, dtype=torch.int8, device=DEV)
+    edges = torch.zeros(G, N, N, Fe, dtype=torch.int8, device=DEV)
+    n_nodes = torch.zeros(G, dtype=torch.int32, device=DEV)            # (128 nodes do not fit int8)
+    assert edges.numel() > 2 ** 31
+    nodes[-2:], edges[-2:], n_nodes[-2:] = torch.from_numpy(tn).to(DEV), torch.from_numpy(te).to(DEV), \
+        torch.from_numpy(tk).to(DEV)
+    want = AM.properties(tn, te, tk, groups)
+    want["n_nodes_hist"][0] += G - 2
+    want["avg_n_nodes"] = np.float32(np.float32(int(tk.sum())) / np.float32(G))
+    assert_same_props(host_props(analyze.molecular_properties(nodes, edges, n_nodes, groups)), want)
+    mb = 64
+    atoms, bonds, n_bonds, status = analyze.decode(nodes, edges, n_nodes, groups, max_bonds=mb).host()
+    w = AM.decode(tn, te, tk, groups, max_bonds=mb)
+    for got, ref in zip((atoms, bonds, n_bonds, status), w):
+        assert np.array_equal(got[-2:], ref)
+    assert not n_bonds[:-2].any() and not status[:-2].any() and (atoms[:-2] == -1).all() and (bonds[:-2] == -1).all()
+    assert n_bonds[-1] > mb
+
+
+# ---- status bits, strict ------------------------------------------------------------------------------------------
+
+def malformed():
+    N, groups = 5, [3, 2]
+    nodes, edges = np.zeros((6, N, 5), np.int8), np.zeros((6, N, N, 2), np.int8)
+    n = np.full(6, 2, np.int8)
+    nodes[:, :2, 0] = nodes[:, :2, 3] = 1
+    edges[:, 0, 1, 0] = edges[:, 1, 0, 0] = 1
+    nodes[1, 1, 3] = 0                                                # 1: a segment without an entry
+    edges[2, 1, 3, 1] = edges[2, 3, 1, 1] = 1                         # 2: a bond past n_nodes
+    edges[3, 0, 2:5, 0] = edges[3, 1, 2:5, 1] = 1                     # 4 (and 2): 7 bonds > max_bonds 3
+    nodes[4, 0, 0] = 2                                                # 8
+    edges[5, 0, 1, 1] = edges[5, 1, 0, 1] = 1                         # 16
+    return nodes, edges, n, groups
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "int8"])
+def test_one_graph_per_status_bit_and_strict_names_the_first(dtype):
+    nodes, edges, n, groups = malformed()
+    dn, de, dk = to_dev(nodes, dtype), to_dev(edges, dtype), torch.from_numpy(n).to(DEV)
+    dec = analyze.decode(dn, de, dk, groups, max_bonds=3)
+    assert_same_decode(dec, AM.decode(nodes, edges, n, groups, max_bonds=3), dtype)
+    assert dec.host()[3].tolist() == [0, 1, 2, 6, 8, 16]
+    assert [m is None for m in analyze.records(dec, "CNO", [0, 1])] == [False, True, True, True, False, False]
+    with pytest.raises(ValueError, match=r"graph 1 \(of 5 .* status 1: a node row"):
+        analyze.decode(dn, de, dk, groups, max_bonds=3, strict=True)
+    with pytest.raises(ValueError, match=r"graph 0 \(of 3 .* status 6"):
+        analyze.decode(dn[3:], de[3:], dk[3:], groups, max_bonds=3, strict=True)
+    analyze.decode(dn[:1], de[:1], dk[:1], groups, strict=True)           # well-formed: no error
+    if dtype == torch.float32:                                            # a fraction and a NaN are "neither 0 nor 1"
+        for bad in (0.5, float("nan")):
+            e2 = de.clone()
+            e2[0, 3, 2, 1] = bad                                          # below the diagonal: no bond, but a value
+            st = analyze.decode(dn, e2, dk, groups, max_bonds=3).host()[3]
+            assert st.tolist() == [8, 1, 2, 6, 8, 16]
+
+
+# ---- determinism, streams, empty batch ----------------------------------------------------------------------------
+
+def test_two_calls_agree_bit_for_bit():
+    nodes, edges, n_nodes = random_batch(700, 13, 3, [5, 3], seed=3)
+    dn, de, dk = to_dev(nodes, torch.float32), to_dev(edges, torch.float32), torch.from_numpy(n_nodes).to(DEV)
+    a, b = (analyze.decode(dn, de, dk, [5, 3], max_bonds=20) for _ in range(2))
+    assert torch.equal(a._buf, b._buf)
+    pa, pb = (analyze.molecular_properties(dn, de, dk, [5, 3], termination=dk) for _ in range(2))
+    for k in pa:
+        assert isinstance(pa[k], list) or pa[k].cpu().numpy().tobytes() == pb[k].cpu().numpy().tobytes(), k
+
+
+def test_a_call_on_a_side_stream_is_ordered_after_its_producer():
+    nodes, edges, n_nodes = random_batch(64, 13, 3, [5, 3], seed=4)
+    hn, he, hk = (torch.from_numpy(x).pin_memory() for x in (nodes, edges, n_nodes))
+    dn = torch.zeros(nodes.shape, dtype=torch.int8, device=DEV)
+    de = torch.zeros(edges.shape, dtype=torch.int8, device=DEV)
+    dk = torch.zeros(n_nodes.shape, dtype=torch.int8, device=DEV)
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        x = torch.randn(2048, 2048, device=DEV)
+        for _ in range(20):                                            # the producer's queue is busy for a while
+            x = x @ x * 1e-3
+        dn.copy_(hn, non_blocking=True), de.copy_(he, non_blocking=True), dk.copy_(hk, non_blocking=True)
+        props = analyze.molecular_properties(dn, de, dk, [5, 3])
+        dec = analyze.decode(dn, de, dk, [5, 3])
+        got = dec.host()                                               # waits for the side stream, the current one
+        side.synchronize()
+    assert_same_props(host_props(props), AM.properties(nodes, edges, n_nodes, [5, 3]))
+    for g, w in zip(got, AM.decode(nodes, edges, n_nodes, [5, 3])):
+        assert np.array_equal(g, w)
+
+
+def test_an_empty_batch_launches_nothing_and_returns_zeros():
+    dn = torch.zeros(0, 13, 8, device=DEV)
+    de = torch.zeros(0, 13, 13, 3, device=DEV)
+    dk = torch.zeros(0, dtype=torch.int8, device=DEV)
+    props = host_props(analyze.molecular_properties(dn, de, dk, [5, 3], termination=dk, n_imp_H=2))
+    assert props["n_nodes_hist"].shape == (14,) and props["n_edges_hist"].shape == (10,) and props["numh_hist"] == [0, 0]
+    assert all(not np.asarray(v).any() for v in props.values())
+    dec = analyze.decode(dn, de, dk, [5, 3], strict=True)
+    atoms, bonds, n_bonds, status = dec.host()
+    assert atoms.shape == (0, 13, 2) and bonds.shape == (0, 26, 3) and n_bonds.shape == status.shape == (0,)
+    assert list(analyze.records(dec, "CNOFS", [-1, 0, 1])) == []
+
+
+# ---- end to end ---------------------------------------------------------------------------------------------------
+
+def test_read_out_of_a_generation_run_with_one_synchronisation(golden_dir, monkeypatch):
+    """build_graphs on the small trained model of golden_generator.npz, then both read-outs on the generator's own
+    tensors (fp32 graphs, int8 n_nodes and termination flags) against the model applied to a host copy; and, by
+    counting, no synchronisation in either launch and exactly one in ``decode(...).host()``."""
+    from graphinvent_amd.generator import build_graphs
+    from graphinvent_amd.gnn import mpnn
+    from oracle import callers_oracle as CO
+    from oracle import ggnn_oracle as O
+    from tests.golden import ref_callers as RC
+    G = np.load(os.path.join(golden_dir, "golden_generator.npz"))
+    cfg = O.make_config(**{str(k): int(v) for k, v in zip(G["cfg_keys"], G["cfg_vals"])})
+    consts = RC.as_constants(RC.constants_dict("cuda", cfg, "/nonexistent", batch_size=100, epochs=1))
+    model = mpnn.GGNN(constants=consts)
+    model.load_state_dict({k[3:]: torch.from_numpy(G[k]) for k in G.files if k.startswith("w::")})
+    model = model.to(DEV).eval()
+    u = torch.from_numpy(CO.InverseCdfDraws(int(G["draw_seed"]), int(G["batch"])).u[:64].astype(np.float32))
+    gen = CO.GeneratorOracle(model, int(G["batch"]), consts, None)
+    assert build_graphs(gen, consts.dim_f_add, consts.dim_f_conn, uniforms=u) == int(G["n_generated"])
+    groups = list(consts.dim_f_add[1:-1])
+    hn, he = gen.generated_nodes.cpu().numpy(), gen.generated_edges.cpu().numpy()
+    hk, ht = gen.generated_n_nodes.cpu().numpy(), gen.properly_terminated.cpu().numpy()
+    assert hn.dtype == np.float32 and hk.dtype == np.int8 and hk.max() > 1
+
+    syncs = {"explicit": 0}
+    real = torch.cuda.Stream.synchronize
+
+    def counting(self):
+        syncs["explicit"] += 1
+        return real(self)
+
+    monkeypatch.setattr(torch.cuda.Stream, "synchronize", counting)
+    monkeypatch.setattr(analyze, "_host_sync_allowed", contextlib.nullcontext)   # let the debug mode see host()'s wait
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("warn")
+    try:
+        with warnings.catch_warnings(record=True) as w:
+            warnings.simplefilter("always")
+            torch.ones(1, device=DEV).item()
+            honoured = sum("synchroniz" in str(x.message) for x in w)
+            props = analyze.molecular_properties(gen.generated_nodes, gen.generated_edges, gen.generated_n_nodes,
+                                                 groups, termination=gen.properly_terminated, epoch_key="Epoch 1")
+            dec = analyze.decode(gen.generated_nodes, gen.generated_edges, gen.generated_n_nodes, groups)
+            launches = sum("synchroniz" in str(x.message) for x in w) - honoured
+            assert syncs["explicit"] == 0
+            host = dec.host()
+            total = sum("synchroniz" in str(x.message) for x in w) - honoured
+            assert dec.host() is host                                  # kept: no second copy, no second wait
+            mols = list(analyze.records(dec, ["C", "N", "O", "F", "S"], [-1, 0, 1]))
+    finally:
+        torch.cuda.set_sync_debug_mode(0)
+    print(f"\nset_sync_debug_mode honoured: {honoured}; warnings in the launches {launches}, with host() {total}; "
+          f"explicit stream waits {syncs['explicit']}")
+    assert syncs["explicit"] == 1 and launches == 0
+    assert total == (1 if honoured else 0)
+
+    want = AM.properties(hn, he, hk, groups, termination=ht)
+    assert_same_props(host_props({k[1]: v for k, v in props.items()}), want)
+    for g, r in zip(host, AM.decode(hn, he, hk, groups)):
+        assert np.array_equal(g, r)
+    assert np.array_equal(hk, G["n_nodes"]) and len(mols) == len(hk)
+    assert sum(len(m[0]) for m in mols if m) == int(hk.astype(np.int64).sum())
