@@ -515,6 +515,13 @@ extern "C" long long gi_route_rows_ws_bytes(int rows_cap, int merge) {
     return (long long)rows_layout(rows_cap, merge).total;
 }
 
+extern "C" int gi_route_rows_hot(void* rows_ws, int rows_cap, int** hot) {
+    if (!rows_ws || !hot || rows_cap < 0) return GI_EINVAL;
+    if (rows_cap > MAX_ROWS) return GI_ELIMIT;
+    *hot = (int*)((char*)rows_ws + rows_layout(rows_cap, 0).hot);
+    return 0;
+}
+
 extern "C" int gi_route_plan(const gi_route_dims* d, const signed char* nodes, const signed char* edges,
                              void* plan_ws, int* lengths, int* mol_err, int* counts, void* stream) {
     (void)hipGetLastError();

@@ -143,6 +143,7 @@ ROUTE_COUNTS = 4                                        # GI_ROUTE_COUNTS
  ROUTE_ERR_EMPTY) = 1, 2, 4, 8, 16, 32, 64               # GI_ROUTE_ERR_*
 ROUTE_ERR_RANK = 128                                    # GI_ROUTE_ERR_RANK (gi_route_reorder only)
 ROUTE_BFS, ROUTE_DFS = 0, 1                             # GI_ROUTE_BFS, GI_ROUTE_DFS
+LL_ERR_HOT, LL_ERR_MOL, LL_ERR_ORDER = 1, 2, 4          # GI_LL_ERR_*
 
 
 ANALYZE_MAX_FN, ANALYZE_MAX_HIST, ANALYZE_EDGE_BINS = 512, 1024, 10      # GI_ANALYZE_*
@@ -261,6 +262,10 @@ SIGNATURES = {
     "gi_route_expand": (ci, [C.POINTER(RouteDims), vp, vp, vp, vp, ci, C.c_ulonglong, vp, vp, vp, ci, vp, vp, vp]),
     "gi_route_merge": (ci, [C.POINTER(RouteDims), vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]),
     "gi_route_reorder": (ci, [ci, ci, ci, ci, vp, vp, vp, C.c_ulonglong, C.c_ulonglong, vp, ci, vp, vp, vp, vp, vp]),
+    "gi_route_rows_hot": (ci, [vp, ci, C.POINTER(vp)]),
+    "gi_row_loglik": (ci, [vp, cll, ci, ci, vp, vp, vp, vp, vp]),
+    "gi_row_loglik_bwd": (ci, [vp, cll, ci, ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, cll, vp, vp]),
+    "gi_mol_loglik_sum": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
     "gi_mol_properties": (ci, [ci, ci, ci, ci, vp, vp, ci, vp, ci, vp, ci, ci, vp, vp, vp]),
     "gi_mol_decode": (ci, [ci, ci, ci, ci, vp, vp, ci, vp, ci, ci, C.POINTER(ci), ci, vp, vp, vp, vp, vp]),
 }

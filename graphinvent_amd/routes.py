@@ -128,7 +128,7 @@ def _r16(x: int) -> int:
 class _Pending:
     """One enqueued expansion: device buffers and the counts still to be read back."""
     __slots__ = ("dims", "cap", "merge", "nodes", "edges", "apds", "row_mol", "row_step", "counts", "lengths",
-                 "mol_err", "keep_alive")
+                 "mol_err", "keep_alive", "hot")
 
 
 def _check_inputs(nodes: torch.Tensor, edges: torch.Tensor):
@@ -162,9 +162,12 @@ def _plan(nodes: torch.Tensor, edges: torch.Tensor, d: L.RouteDims):
 
 
 def _enqueue(nodes: torch.Tensor, edges: torch.Tensor, d: L.RouteDims, merge: bool, cap: int, planned=None,
-             hash_mask: int = 2 ** 64 - 1) -> _Pending:
+             hash_mask: int = 2 ** 64 - 1, _apds: bool = True) -> _Pending:
     """Plan (unless `planned`), expand and merge on the current stream of the inputs' device, with no host wait.
-    `cap` is the number of unmerged rows the outputs are sized for."""
+    `cap` is the number of unmerged rows the outputs are sized for.  `_apds=False` (unmerged only; ``likelihood``'s)
+    neither allocates nor writes the APD rows: `apds` is None and `hot` holds every row's hot APD index instead."""
+    if merge and not _apds:
+        raise ValueError("the merge sums APD rows: it cannot run without them")
     lib, dev = L.load(), nodes.device
     st = torch.cuda.current_stream(dev).cuda_stream
     plan_ws, lengths, mol_err, counts = planned if planned is not None else _plan(nodes, edges, d)
@@ -186,13 +189,20 @@ def _enqueue(nodes: torch.Tensor, edges: torch.Tensor, d: L.RouteDims, merge: bo
     if nbytes < 0:
         L.check(int(nbytes), "gi_route_rows_ws_bytes")
     rows_ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
-    un, ue, ua, um, us = new_outputs(True)
+    un, ue, ua, um, us = new_outputs(_apds)
     L.check(lib.gi_route_expand(C.byref(d), nodes.data_ptr(), plan_ws.data_ptr(), rows_ws.data_ptr(),
                                 counts.data_ptr(), cap, hash_mask, un.data_ptr(), ue.data_ptr(),
-                                None if merge else ua.data_ptr(), apd_dtype, um.data_ptr(), us.data_ptr(), st),
+                                None if merge or ua is None else ua.data_ptr(), apd_dtype, um.data_ptr(),
+                                us.data_ptr(), st),
             "gi_route_expand")
     p = _Pending()
     p.dims, p.cap, p.merge, p.counts, p.lengths, p.mol_err = d, cap, merge, counts, lengths, mol_err
+    p.hot = None
+    if not _apds:
+        ptr = C.c_void_p()
+        L.check(lib.gi_route_rows_hot(rows_ws.data_ptr(), cap, C.byref(ptr)), "gi_route_rows_hot")
+        at = int(ptr.value) - rows_ws.data_ptr()
+        p.hot = rows_ws[at:at + 4 * max(cap, 1)].view(torch.int32)[:cap]
     if merge:
         on, oe, _, om, os_ = new_outputs(False)
         L.check(lib.gi_route_merge(C.byref(d), rows_ws.data_ptr(), counts.data_ptr(), cap, un.data_ptr(),

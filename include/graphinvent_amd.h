@@ -947,6 +947,49 @@ int gi_route_merge(const gi_route_dims* d, void* rows_ws, int* counts, int rows_
                    signed char* out_nodes, signed char* out_edges, void* out_apd, int apd_dtype, int* out_row_mol,
                    int* out_row_step, void* stream);
 
+/* gi_route_rows_hot: *hot = the device pointer, inside the rows_ws of a gi_route_expand call with this rows_cap
+ * (whatever `merge` it was allocated with), of hot[rows_cap] int32: the hot APD index of every unmerged row (apd_width
+ * - 1 in the rows past the real ones, which row_mol marks with -1).  With out_apd = NULL this is all a likelihood
+ * needs of the APDs.  Host arithmetic only. */
+int gi_route_rows_hot(void* rows_ws, int rows_cap, int** hot);
+
+/* ------------------------------------------------------------------------------------------
+ * Log-likelihood of whole molecules along their decoding routes (gi_loglik.hip).  For route row r with logits z_r [W]
+ * and hot APD index a_r:  row_ll[r] = z_r[a_r] - logsumexp(z_r);  mol_ll[m] = the sum over the rows of molecule m.
+ * That is the log of the product over the route of the per-row probability of Analyzer.py:754-774 with a one-hot
+ * target; it is evaluated in log space with the row maximum subtracted, so it stays finite where the reference's
+ * linear-space product underflows.
+ *
+ * logits [rows, W] fp32 with row pitch ld >= W floats, W >= 1 without an upper limit; hot [rows] int32.  err: one int32
+ * word on the device, OR-ed with GI_LL_ERR_* bits, never cleared here.
+ *
+ * gi_row_loglik      row_ll[r] and row_lse[r] = logsumexp(z_r); each row is read once.  hot[r] == -1 (a padding row):
+ *                    nothing is read, both are 0.  hot[r] outside [-1, W): GI_LL_ERR_HOT, nothing is indexed with it
+ *                    and the row's outputs are not written.  A NaN logit gives NaN; hot's logit -inf gives -inf.
+ * gi_row_loglik_bwd  d_logits[r, j] = g_r (delta(j, hot[r]) - exp(z[r, j] - row_lse[r])), written, not accumulated
+ *                    (row pitch ldd >= W); an entry whose logit is -inf gets exactly 0.  g_r = g_mol[row_mol[r]], plus
+ *                    g_kind[row_mol[r], kind_r] when g_kind [n_mol, 3] is given (kind_r: hot < n_add -> 0, hot < n_add
+ *                    + n_conn -> 1, else 2; n_add + n_conn + 1 == W); row_mol = NULL: g_r = g_mol[r].  Rows with hot
+ *                    == -1 or row_mol == -1 are exactly zero; so are rows whose hot is outside [-1, W) (GI_LL_ERR_HOT)
+ *                    or whose row_mol is outside [-1, n_mol) (GI_LL_ERR_MOL).
+ * gi_mol_loglik_sum  mol_ll[m] += the sum of row_ll over the rows of the call with row_mol == m (-1: skipped), added
+ *                    one by one in row order by one thread per molecule (no atomics): splitting the rows over several
+ *                    calls in stream order, anywhere, gives the same bits as one call.  mol_kind [n_mol, 3] (NULL: not
+ *                    wanted; needs hot, W, n_add, n_conn as above) += the same sum split by kind_r.  Contract: row_mol
+ *                    is in [-1, n_mol) (GI_LL_ERR_MOL otherwise) and non-decreasing over the rows that are not -1
+ *                    (GI_LL_ERR_ORDER); on a violation, and while err carries one of these two bits from an earlier
+ *                    call, the launch writes nothing. */
+#define GI_LL_ERR_HOT 1             /* a hot index outside [-1, W) */
+#define GI_LL_ERR_MOL 2             /* a row_mol outside [-1, n_mol) */
+#define GI_LL_ERR_ORDER 4           /* row_mol decreases */
+int gi_row_loglik(const float* logits, long long ld, int rows, int W, const int* hot, float* row_ll, float* row_lse,
+                  int* err, void* stream);
+int gi_row_loglik_bwd(const float* logits, long long ld, int rows, int W, const int* hot, const float* row_lse,
+                      const float* g_mol, const float* g_kind, const int* row_mol, int n_mol, int n_add, int n_conn,
+                      float* d_logits, long long ldd, int* err, void* stream);
+int gi_mol_loglik_sum(const float* row_ll, const int* row_mol, const int* hot, int rows, int n_mol, int W, int n_add,
+                      int n_conn, float* mol_ll, float* mol_kind, int* err, void* stream);
+
 /* Node reordering (gi_reorder.hip): what `PreprocessingGraph.node_remap` (MolecularGraph.py:435-461) does once it has
  * a node ranking, for M molecules in one launch: a breadth- or depth-first search (:328-433) from node rank[0], then
  * `reorder_nodes` and `pad_graph_representation` (:592-633).  nodes [M, N, Fn] / edges [M, N, N, Fe] as above, except
