@@ -19,6 +19,12 @@
 // row (source graph, first and last round) from the per-graph start rounds in state[GI_GROW_STATE_WORDS + B + g].
 // gi_grow_traj_gather / gi_grow_traj_scatter rebuild the generated likelihood rows from the per-round likelihoods with
 // that record, and take the gradient back, for the autograd of the RL loop.
+//
+// gi_grow_graphs_seeded / gi_grow_graphs_rl_seeded run the same three launches with a seed bank (SeedArgs): a graph
+// written out in the round restarts from seed (B - 1 + row) mod S of the bank instead of from the empty graph, and
+// gen_seed[row] receives the seed it was grown from, kept per slot in state[GI_GROW_STATE_WORDS + 2 B + g].  The bank
+// is int8 and tightly packed, so a seed starts at any byte address: it is read one byte per element.
+// gi_grow_seed_init writes the first fill.
 #include "gi_common.h"
 
 namespace {
@@ -36,6 +42,16 @@ struct GrowArgs {
     const float* p_like;                     // [B]
     int* traj;                               // [3, C]
     int* start;                              // [B], in state
+};
+
+// the seed bank of the seeded entry points (gi_grow_seed_desc) and the per-slot seed indices in state
+struct SeedArgs {
+    const signed char* nodes;                // [S, N, Fn]
+    const signed char* edges;                // [S, N, N, Fe]
+    const signed char* n_nodes;              // [S]
+    int* gen_seed;                           // [C] or NULL
+    int* slot_seed;                          // [B], in state
+    int S;
 };
 
 __device__ __forceinline__ long long node_off(const gi_grow_desc& d, int g) { return (long long)g * d.N * d.Fn; }
@@ -124,7 +140,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void grow_scan_kernel(GrowArgs a) {
     for (int i = n + tid; i < end; i += SCAN_THREADS) d.properly_terminated[i] = 1;
 }
 
-__global__ __launch_bounds__(APPLY_THREADS) void grow_apply_kernel(GrowArgs a) {
+template <bool SEEDED>
+__device__ __forceinline__ void grow_apply(const GrowArgs& a, const SeedArgs& sd) {
     const gi_grow_desc& d = a.d;
     const int* st = d.state;
     if (!st[4]) return;
@@ -144,8 +161,18 @@ __global__ __launch_bounds__(APPLY_THREADS) void grow_apply_kernel(GrowArgs a) {
         float* gn = d.gen_nodes + (long long)row * NF;
         float* ge = d.gen_edges + (long long)row * NNF;
         float* gl = d.gen_likelihoods + row * d.L;
-        for (int i = tid; i < NF; i += APPLY_THREADS) { gn[i] = nodes[i]; nodes[i] = 0.f; }
-        for (int i = tid; i < NNF; i += APPLY_THREADS) { ge[i] = edges[i]; edges[i] = 0.f; }
+        int next = 0;
+        if (SEEDED) {
+            // the restart: seed (B - 1 + row) mod S, one byte per element (a seed starts at any byte address)
+            next = (int)(((long long)d.B - 1 + row) % sd.S);
+            const signed char* sn = sd.nodes + (long long)next * NF;
+            const signed char* se = sd.edges + (long long)next * NNF;
+            for (int i = tid; i < NF; i += APPLY_THREADS) { gn[i] = nodes[i]; nodes[i] = (float)sn[i]; }
+            for (int i = tid; i < NNF; i += APPLY_THREADS) { ge[i] = edges[i]; edges[i] = (float)se[i]; }
+        } else {
+            for (int i = tid; i < NF; i += APPLY_THREADS) { gn[i] = nodes[i]; nodes[i] = 0.f; }
+            for (int i = tid; i < NNF; i += APPLY_THREADS) { ge[i] = edges[i]; edges[i] = 0.f; }
+        }
         for (int j = tid; j < d.L; j += APPLY_THREADS) { gl[j] = j == r ? like : lrow[j]; lrow[j] = 0.f; }
         if (a.p_likelihoods) {
             const float plike = a.p_like[g];
@@ -155,7 +182,13 @@ __global__ __launch_bounds__(APPLY_THREADS) void grow_apply_kernel(GrowArgs a) {
         }
         if (tid == 0) {
             d.gen_n_nodes[row] = d.n_nodes[g];
-            d.n_nodes[g] = 0;
+            if (SEEDED) {                    // (only block g touches slot_seed[g])
+                d.n_nodes[g] = sd.n_nodes[next];
+                if (sd.gen_seed) sd.gen_seed[row] = sd.slot_seed[g];
+                sd.slot_seed[g] = next;
+            } else {
+                d.n_nodes[g] = 0;
+            }
             if (a.start) {                   // (only block g touches start[g])
                 if (a.traj) {
                     a.traj[row] = g;
@@ -206,6 +239,40 @@ __global__ __launch_bounds__(APPLY_THREADS) void grow_apply_kernel(GrowArgs a) {
     }
 }
 
+__global__ __launch_bounds__(APPLY_THREADS) void grow_apply_kernel(GrowArgs a) { grow_apply<false>(a, SeedArgs{}); }
+
+__global__ __launch_bounds__(APPLY_THREADS) void grow_apply_seeded_kernel(GrowArgs a, SeedArgs sd) {
+    grow_apply<true>(a, sd);
+}
+
+// the first fill: slot g >= 1 takes seed (g - 1) mod S; slot 0 (the dummy graph) is left as it is
+__global__ __launch_bounds__(APPLY_THREADS) void grow_seed_init_kernel(GrowArgs a, SeedArgs sd) {
+    const gi_grow_desc& d = a.d;
+    const int g = blockIdx.x, tid = threadIdx.x;
+    if (g == 0) {
+        if (tid == 0) sd.slot_seed[0] = -1;
+        return;
+    }
+    const int NF = d.N * d.Fn, NNF = d.N * d.N * d.Fe;
+    const int seed = (g - 1) % sd.S;
+    const signed char* sn = sd.nodes + (long long)seed * NF;
+    const signed char* se = sd.edges + (long long)seed * NNF;
+    float* nodes = d.nodes + node_off(d, g);
+    float* edges = d.edges + edge_off(d, g);
+    float* lrow = d.likelihoods + (long long)g * d.L;
+    for (int i = tid; i < NF; i += APPLY_THREADS) nodes[i] = (float)sn[i];
+    for (int i = tid; i < NNF; i += APPLY_THREADS) edges[i] = (float)se[i];
+    for (int j = tid; j < d.L; j += APPLY_THREADS) lrow[j] = 0.f;
+    if (a.p_likelihoods) {
+        float* prow = a.p_likelihoods + (long long)g * d.L;
+        for (int j = tid; j < d.L; j += APPLY_THREADS) prow[j] = 0.f;
+    }
+    if (tid == 0) {
+        d.n_nodes[g] = sd.n_nodes[seed];
+        sd.slot_seed[g] = seed;
+    }
+}
+
 __global__ __launch_bounds__(64) void grow_commit_kernel(int* state, int* host_state) {
     if (threadIdx.x != 0) return;
     if (state[4]) {
@@ -249,10 +316,26 @@ int grow_args(const gi_grow_desc& d, GrowArgs& a) {
     return 0;
 }
 
-int grow_launch(const GrowArgs& a, void* stream) {
+// gi_grow_seed_desc's checks; fills sd (slot_seed from d.state)
+int seed_args(const gi_grow_desc& d, const gi_grow_seed_desc* seeds, SeedArgs& sd) {
+    if (!seeds || seeds->S < 1 || !seeds->nodes || !seeds->edges || !seeds->n_nodes) return GI_EINVAL;
+    if ((long long)seeds->S * d.N * d.N * d.Fe > 0x7fffffffffffLL) return GI_ELIMIT;
+    sd.nodes = seeds->nodes;
+    sd.edges = seeds->edges;
+    sd.n_nodes = seeds->n_nodes;
+    sd.gen_seed = seeds->gen_seed;
+    sd.slot_seed = d.state + GI_GROW_STATE_WORDS + 2LL * d.B;
+    sd.S = seeds->S;
+    return 0;
+}
+
+int grow_launch(const GrowArgs& a, void* stream, const SeedArgs* sd = nullptr) {
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(grow_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, a);
-    hipLaunchKernelGGL(grow_apply_kernel, dim3(a.d.B), dim3(APPLY_THREADS), 0, st, a);
+    if (sd)
+        hipLaunchKernelGGL(grow_apply_seeded_kernel, dim3(a.d.B), dim3(APPLY_THREADS), 0, st, a, *sd);
+    else
+        hipLaunchKernelGGL(grow_apply_kernel, dim3(a.d.B), dim3(APPLY_THREADS), 0, st, a);
     hipLaunchKernelGGL(grow_commit_kernel, dim3(1), dim3(64), 0, st, a.d.state, a.d.host_state);
     return gi_launch_status();
 }
@@ -312,10 +395,11 @@ extern "C" int gi_grow_graphs(const gi_grow_desc* desc, void* stream) {
 
 extern "C" int gi_grow_rl_state_words(int B) { return B < 0 ? GI_EINVAL : GI_GROW_STATE_WORDS + 2 * B; }
 
-extern "C" int gi_grow_graphs_rl(const gi_grow_rl_desc* desc, void* stream) {
-    (void)hipGetLastError();
+namespace {
+
+// gi_grow_rl_desc's checks on top of grow_args'
+int grow_args_rl(const gi_grow_rl_desc* desc, GrowArgs& a) {
     if (!desc) return GI_EINVAL;
-    GrowArgs a;
     const int rc = grow_args(desc->base, a);
     if (rc) return rc;
     const int n_prior = !!desc->prior_likelihoods + !!desc->gen_prior_likelihoods + !!desc->prior_likelihood;
@@ -326,7 +410,61 @@ extern "C" int gi_grow_graphs_rl(const gi_grow_rl_desc* desc, void* stream) {
     a.p_like = desc->prior_likelihood;
     a.traj = desc->traj;
     a.start = desc->base.state + GI_GROW_STATE_WORDS + desc->base.B;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int gi_grow_graphs_rl(const gi_grow_rl_desc* desc, void* stream) {
+    (void)hipGetLastError();
+    GrowArgs a;
+    const int rc = grow_args_rl(desc, a);
+    if (rc) return rc;
     return grow_launch(a, stream);
+}
+
+extern "C" int gi_grow_seeded_state_words(int B) { return B < 0 ? GI_EINVAL : GI_GROW_STATE_WORDS + 3 * B; }
+
+extern "C" int gi_grow_seed_init(const gi_grow_desc* desc, const gi_grow_seed_desc* seeds, float* prior_likelihoods,
+                                 void* stream) {
+    (void)hipGetLastError();
+    if (!desc) return GI_EINVAL;
+    const gi_grow_desc& d = *desc;
+    if (d.B <= 0 || d.N <= 0 || d.Fn <= 0 || d.Fe <= 0 || d.L <= 0) return GI_EINVAL;
+    if (d.N > GI_MAX_NODES) return GI_ELIMIT;
+    if ((long long)d.N * d.N * d.Fe > 0x7fffffffLL || (long long)d.N * d.Fn > 0x7fffffffLL) return GI_ELIMIT;
+    if (!d.nodes || !d.edges || !d.n_nodes || !d.likelihoods || !d.state) return GI_EINVAL;
+    GrowArgs a{};
+    a.d = d;
+    a.p_likelihoods = prior_likelihoods;
+    SeedArgs sd;
+    const int rc = seed_args(d, seeds, sd);
+    if (rc) return rc;
+    hipLaunchKernelGGL(grow_seed_init_kernel, dim3(d.B), dim3(APPLY_THREADS), 0, (hipStream_t)stream, a, sd);
+    return gi_launch_status();
+}
+
+extern "C" int gi_grow_graphs_seeded(const gi_grow_desc* desc, const gi_grow_seed_desc* seeds, void* stream) {
+    (void)hipGetLastError();
+    if (!desc) return GI_EINVAL;
+    GrowArgs a;
+    int rc = grow_args(*desc, a);
+    if (rc) return rc;
+    SeedArgs sd;
+    rc = seed_args(a.d, seeds, sd);
+    if (rc) return rc;
+    return grow_launch(a, stream, &sd);
+}
+
+extern "C" int gi_grow_graphs_rl_seeded(const gi_grow_rl_desc* desc, const gi_grow_seed_desc* seeds, void* stream) {
+    (void)hipGetLastError();
+    GrowArgs a;
+    int rc = grow_args_rl(desc, a);
+    if (rc) return rc;
+    SeedArgs sd;
+    rc = seed_args(a.d, seeds, sd);
+    if (rc) return rc;
+    return grow_launch(a, stream, &sd);
 }
 
 extern "C" int gi_grow_traj_gather(int n, int R, int B, int C, int L, const int* traj, const float* like_a,

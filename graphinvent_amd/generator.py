@@ -20,6 +20,14 @@ draws, and ``gi_grow_graphs_rl`` carries both likelihood streams and records eac
 graph, first and last round).  The generated likelihood rows are then rebuilt from the stacked per-round likelihoods
 by an autograd Function (``gi_grow_traj_gather`` forward, ``gi_grow_traj_scatter`` backward), so that
 ``Workflow.compute_loss_component`` differentiates through every applied round into both models.
+
+Seeded generation (scaffold decoration, fragment growing): ``build_graphs(..., seeds=SeedBank(...))`` and
+``build_graphs_rl(..., seeds=...)`` start every graph from a molecule of the bank instead of from the empty graph, and
+restart it from the next one when it is written out (``gi_grow_seed_init``, ``gi_grow_graphs_seeded``,
+``gi_grow_graphs_rl_seeded``): still no read-back inside a round, in the blocking, sync-free and captured modes alike.
+``gen.generated_seed`` then names the seed behind every generated row, and the generated likelihood rows are those of
+the COMPLETION given the seed (``likelihood.molecule_log_likelihood(..., given_actions=bank.n_actions[...])`` scores
+the same quantity for stored molecules).
 """
 from __future__ import annotations
 
@@ -28,9 +36,11 @@ import contextlib
 import ctypes as C
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import lib as L
+from . import routes as R
 from .sampler import _add_dims, _SampleRL, sample_actions_raw
 
 #: the generator tensors the step reads and writes, in gi_grow_desc's order, with their dtypes
@@ -40,10 +50,10 @@ _STATE_TENSORS = (("nodes", torch.float32), ("edges", torch.float32), ("n_nodes"
                   ("generated_likelihoods", torch.float32), ("properly_terminated", torch.int8))
 
 
-def new_state(batch_size: int, target: int, device, rl: bool = False) -> torch.Tensor:
-    """The step's device state: int32 [GI_GROW_STATE_WORDS + B] (``rl``: + 2 B, ``gi_grow_rl_state_words``), zero
-    with ``state[2] = target``."""
-    words = L.GROW_STATE_WORDS + (2 if rl else 1) * batch_size
+def new_state(batch_size: int, target: int, device, rl: bool = False, seeded: bool = False) -> torch.Tensor:
+    """The step's device state: int32 [GI_GROW_STATE_WORDS + B] (``rl``: + 2 B, ``gi_grow_rl_state_words``;
+    ``seeded``, with or without ``rl``: + 3 B, ``gi_grow_seeded_state_words``), zero with ``state[2] = target``."""
+    words = L.GROW_STATE_WORDS + (3 if seeded else 2 if rl else 1) * batch_size
     state = torch.zeros(words, dtype=torch.int32, device=device)
     state.narrow(0, 2, 1).fill_(int(target))          # a fill launch: no host -> device copy
     return state
@@ -88,17 +98,99 @@ def _validate(t: dict, dim_f_add: Sequence[int], dim_f_conn: Sequence[int]):
     return (B, N, Fn, Fe, Lc, Cg), sub, groups
 
 
+class SeedBank:
+    """A bank of ``S >= 1`` seed molecules (scaffolds, fragments) for seeded generation: int8 device molecules
+    ``nodes [S, N, Fn]`` / ``edges [S, N, N, Fe]`` in the loader's format, validated once on the device with
+    ``routes.check`` (0 / 1 entries, one-hot feature groups, symmetric edges with one bond type per pair, zero-padded
+    prefix, every node i > 0 bonded to a node of lower index — which implies a connected molecule); an all-zero
+    molecule is accepted as the empty seed.  ``reorder="bfs"`` / ``"dfs"`` runs ``routes.reorder`` first, so seeds in
+    any node order are accepted.  ONE read-back, here; a violated rule raises ``ValueError`` naming it.
+
+    ``n_nodes`` (int8 ``[S]``) and ``n_actions`` (int32 ``[S]``: the build actions a seed stands for, ``n_edges + 1``,
+    0 for the empty seed — the ``given_actions`` of ``likelihood.molecule_log_likelihood``) are on the device.
+    The generation loops take the seeds round-robin in bank order: shuffle the molecules before building the bank
+    to randomise."""
+
+    def __init__(self, nodes: torch.Tensor, edges: torch.Tensor, dim_f_add: Sequence[int],
+                 dim_f_conn: Sequence[int], *, reorder: Optional[str] = None):
+        if reorder not in (None, "bfs", "dfs"):
+            raise ValueError("reorder must be None, 'bfs' or 'dfs'")
+        nodes, edges = R._check_inputs(nodes, edges)
+        if nodes.shape[0] < 1:
+            raise ValueError("a seed bank needs at least one molecule (the all-zero molecule is the empty seed)")
+        with torch.cuda.device(nodes.device):
+            empty = ~((nodes != 0).flatten(1).any(1) | (edges != 0).flatten(1).any(1))
+            bits = torch.zeros(nodes.shape[0], dtype=torch.int32, device=nodes.device)
+            if reorder is not None:
+                nodes, edges, bits = R.reorder(nodes, edges, route=reorder, invalid="skip")
+            disconnected = (bits & L.ROUTE_ERR_CONNECT) != 0              # (reorder's meaning of the bit)
+            bits = (bits & ~L.ROUTE_ERR_CONNECT) | R.check(nodes, edges, dim_f_add, dim_f_conn)
+            bits = torch.where(empty, bits & ~L.ROUTE_ERR_EMPTY, bits)
+            n_nodes = (nodes != 0).flatten(2).any(2).sum(1)
+            n_edges = (edges != 0).flatten(1).sum(1) // 2
+            with _host_sync_allowed():
+                flags = torch.stack((bits, disconnected.to(torch.int32))).cpu().numpy()      # the read-back
+        bad = flags[0] != 0
+        if bad.any() or flags[1].any():
+            what = R.describe_errors(int(np.bitwise_or.reduce(flags[0])))
+            if flags[1].any():
+                what = "; ".join(filter(None, [what, "a molecule is not connected"]))
+            first = int((bad | (flags[1] != 0)).argmax())
+            raise ValueError(f"invalid seed(s) in the bank (first: seed {first}): {what}")
+        self.nodes, self.edges = nodes, edges
+        self.n_nodes = n_nodes.to(torch.int8)
+        self.n_actions = torch.where(empty, 0, n_edges + 1).to(torch.int32)
+        self.device = nodes.device
+
+    def __len__(self) -> int:
+        return self.nodes.shape[0]
+
+    def desc(self, N: int, Fn: int, Fe: int, device, gen_seed: Optional[torch.Tensor]) -> "L.GrowSeedDesc":
+        """gi_grow_seed_desc for generator tensors of the given dims (checked against the bank's)."""
+        S, bN, bFn = self.nodes.shape
+        bFe = self.edges.shape[3]
+        if (bN, bFn, bFe) != (N, Fn, Fe):
+            raise ValueError(f"the seed bank has N, Fn, Fe = {(bN, bFn, bFe)}, the generator's tensors {(N, Fn, Fe)}")
+        if self.device != device:
+            raise ValueError(f"the seed bank is on {self.device}, the generator's tensors on {device}")
+        d = L.GrowSeedDesc()
+        d.nodes, d.edges, d.n_nodes = self.nodes.data_ptr(), self.edges.data_ptr(), self.n_nodes.data_ptr()
+        d.gen_seed = gen_seed.data_ptr() if gen_seed is not None else None
+        d.S = S
+        return d
+
+
+def _check_gen_seed(gen_seed: Optional[torch.Tensor], Cg: int, device) -> None:
+    if gen_seed is not None and (gen_seed.dtype != torch.int32 or tuple(gen_seed.shape) != (Cg,) or
+                                 not gen_seed.is_contiguous() or gen_seed.device != device):
+        raise ValueError(f"generated_seed must be a contiguous int32 [{Cg}] tensor on {device}")
+
+
 class _Grower:
-    """Validated gi_grow_desc of one set of generator tensors; ``step`` enqueues one round."""
+    """Validated gi_grow_desc of one set of generator tensors; ``step`` enqueues one round.  With ``seeds`` (a
+    SeedBank) the rounds are gi_grow_graphs_seeded's, ``seed_init`` enqueues the first fill and ``gen_seed`` (int32
+    [C], optional) receives the seed of every generated row."""
 
     def __init__(self, t: dict, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], state: torch.Tensor,
-                 host_state: Optional[int] = None):
+                 host_state: Optional[int] = None, seeds: Optional[SeedBank] = None,
+                 gen_seed: Optional[torch.Tensor] = None):
         (B, N, Fn, Fe, Lc, Cg), sub, groups = _validate(t, dim_f_add, dim_f_conn)
         nodes = t["nodes"]
         if state.dtype != torch.int32 or state.device != nodes.device or not state.is_contiguous() or \
                 state.numel() < L.GROW_STATE_WORDS + B:
             raise ValueError("state must be a contiguous int32 tensor of GI_GROW_STATE_WORDS + B words on the "
                              "tensors' device (generator.new_state)")
+        self.seeds, self.gen_seed, self.seed_desc = seeds, gen_seed, None
+        if seeds is not None:
+            if not isinstance(seeds, SeedBank):
+                raise TypeError("seeds must be a generator.SeedBank")
+            _check_gen_seed(gen_seed, Cg, nodes.device)
+            self.seed_desc = seeds.desc(N, Fn, Fe, nodes.device, gen_seed)
+            if state.numel() < L.GROW_STATE_WORDS + 3 * B:
+                raise ValueError("state must hold gi_grow_seeded_state_words(B) = GI_GROW_STATE_WORDS + 3 B words "
+                                 "(generator.new_state(..., seeded=True))")
+        elif gen_seed is not None:
+            raise ValueError("generated_seed is only written with seeds")
         self.t, self.state, self.B, self.device = t, state, B, nodes.device
         self.A = 1
         for x in sub:
@@ -125,9 +217,21 @@ class _Grower:
                 raise ValueError(f"grow_step: {name} must be contiguous {dtype} {shape} (gi_sample_actions' output)")
         d = self.desc
         d.action, d.likelihood, d.flags = action.data_ptr(), likelihood.data_ptr(), flags.data_ptr()
+        st = torch.cuda.current_stream(self.device).cuda_stream
         with torch.cuda.device(self.device):
-            L.check(L.load().gi_grow_graphs(C.byref(d), torch.cuda.current_stream(self.device).cuda_stream),
-                    "gi_grow_graphs")
+            if self.seed_desc is not None:
+                L.check(L.load().gi_grow_graphs_seeded(C.byref(d), C.byref(self.seed_desc), st),
+                        "gi_grow_graphs_seeded")
+            else:
+                L.check(L.load().gi_grow_graphs(C.byref(d), st), "gi_grow_graphs")
+
+    def seed_init(self, prior_likelihoods: Optional[torch.Tensor] = None) -> None:
+        """gi_grow_seed_init on the current stream: every slot but 0 starts from its seed."""
+        with torch.cuda.device(self.device):
+            L.check(L.load().gi_grow_seed_init(C.byref(self.desc), C.byref(self.seed_desc),
+                                               None if prior_likelihoods is None else prior_likelihoods.data_ptr(),
+                                               torch.cuda.current_stream(self.device).cuda_stream),
+                    "gi_grow_seed_init")
 
 
 def _tensors(gen) -> dict:
@@ -136,15 +240,62 @@ def _tensors(gen) -> dict:
 
 def grow_step(nodes, edges, n_nodes, likelihoods, generated_nodes, generated_edges, generated_n_nodes,
               generated_likelihoods, properly_terminated, action, likelihood, flags,
-              dim_f_add: Sequence[int], dim_f_conn: Sequence[int], state: torch.Tensor) -> None:
+              dim_f_add: Sequence[int], dim_f_conn: Sequence[int], state: torch.Tensor, *,
+              seeds: Optional[SeedBank] = None, generated_seed: Optional[torch.Tensor] = None) -> None:
     """One growth step (gi_grow_graphs) on the given generator tensors, in place, from ``sample_actions_raw``'s
     ``(action, likelihood, flags)``.  ``state`` (``new_state``) carries the counters from round to round: ``state[0]``
-    graphs generated, ``[1]`` round, ``[2]`` target, ``[3]`` error bits (``lib.GROW_ERR_*``)."""
+    graphs generated, ``[1]`` round, ``[2]`` target, ``[3]`` error bits (``lib.GROW_ERR_*``).
+
+    ``seeds`` (a SeedBank): the seeded step (gi_grow_graphs_seeded) — a graph written out restarts from a seed, and
+    ``generated_seed`` (int32 [C], optional) receives the seed of every generated row.  ``state`` is then
+    ``new_state(..., seeded=True)`` and the tensors were filled by ``seed_init`` before the first round."""
     L.load()
     t = dict(zip((n for n, _ in _STATE_TENSORS),
                  (nodes, edges, n_nodes, likelihoods, generated_nodes, generated_edges, generated_n_nodes,
                   generated_likelihoods, properly_terminated)))
-    _Grower(t, dim_f_add, dim_f_conn, state).step(action, likelihood, flags)
+    _Grower(t, dim_f_add, dim_f_conn, state, seeds=seeds, gen_seed=generated_seed).step(action, likelihood, flags)
+
+
+def seed_init(nodes, edges, n_nodes, likelihoods, state: torch.Tensor, seeds: SeedBank, *,
+              prior_likelihoods: Optional[torch.Tensor] = None) -> None:
+    """The first fill of seeded generation (gi_grow_seed_init), in place: slot 0 stays the dummy graph, slot
+    ``g >= 1`` takes seed ``(g - 1) mod S`` (nodes, edges, n_nodes; its likelihood row — and the row of
+    ``prior_likelihoods`` — zeroed), and ``state`` (``new_state(..., seeded=True)``, before the first round) records
+    every slot's seed.  ``build_graphs`` / ``build_graphs_rl`` do this themselves."""
+    L.load()
+    if not isinstance(seeds, SeedBank):
+        raise TypeError("seeds must be a generator.SeedBank")
+    rows = [("nodes", nodes, torch.float32), ("edges", edges, torch.float32), ("n_nodes", n_nodes, torch.int8),
+            ("likelihoods", likelihoods, torch.float32)]
+    if prior_likelihoods is not None:
+        rows.append(("prior_likelihoods", prior_likelihoods, torch.float32))
+    for name, x, dtype in rows:
+        if not x.is_cuda:
+            raise RuntimeError(f"seed_init needs CUDA (ROCm) tensors ({name} is on {x.device}): the MI355X HIP path "
+                               "has no CPU fallback")
+        if x.dtype != dtype or not x.is_contiguous() or x.device != nodes.device:
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor on {nodes.device}")
+    if nodes.dim() != 3 or edges.dim() != 4:
+        raise ValueError("nodes must be [B, N, Fn] and edges [B, N, N, Fe]")
+    B, N, Fn = nodes.shape
+    Fe = edges.shape[3]
+    if tuple(edges.shape) != (B, N, N, Fe) or tuple(n_nodes.shape) != (B,) or likelihoods.dim() != 2 or \
+            likelihoods.shape[0] != B or likelihoods.shape[1] < 1 or \
+            (prior_likelihoods is not None and prior_likelihoods.shape != likelihoods.shape):
+        raise ValueError("edges / n_nodes / likelihoods do not match nodes' [B, N, Fn]")
+    if state.dtype != torch.int32 or state.device != nodes.device or not state.is_contiguous() or \
+            state.numel() < L.GROW_STATE_WORDS + 3 * B:
+        raise ValueError("state must hold gi_grow_seeded_state_words(B) = GI_GROW_STATE_WORDS + 3 B int32 words "
+                         "(generator.new_state(..., seeded=True))")
+    d = L.GrowDesc()
+    d.nodes, d.edges, d.n_nodes, d.likelihoods = (x.data_ptr() for x in (nodes, edges, n_nodes, likelihoods))
+    d.state = state.data_ptr()
+    d.B, d.N, d.Fn, d.Fe, d.L = B, N, Fn, Fe, likelihoods.shape[1]
+    sd = seeds.desc(N, Fn, Fe, nodes.device, None)
+    with torch.cuda.device(nodes.device):
+        L.check(L.load().gi_grow_seed_init(C.byref(d), C.byref(sd),
+                                           None if prior_likelihoods is None else prior_likelihoods.data_ptr(),
+                                           torch.cuda.current_stream(nodes.device).cuda_stream), "gi_grow_seed_init")
 
 
 class _HostMirror:
@@ -178,7 +329,8 @@ def _host_sync_allowed():
 
 
 def build_graphs(gen, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], *, uniforms: Optional[torch.Tensor] = None,
-                 generator: Optional[torch.Generator] = None, poll_every: int = 8, capture: bool = False) -> int:
+                 generator: Optional[torch.Generator] = None, poll_every: int = 8, capture: bool = False,
+                 seeds: Optional[SeedBank] = None) -> int:
     """Drop-in for ``GraphGenerator.build_graphs`` (GraphGenerator.py:99-161): ``gen`` is the reference's generator
     (duck-typed: ``model``, ``batch_size`` and the tensors its ``__init__`` allocates), mutated in place; returns
     ``n_generated_so_far`` and sets ``gen.generation_rounds`` (rounds applied).
@@ -188,7 +340,13 @@ def build_graphs(gen, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], *, un
     rounds back, never for the whole device; the result does not depend on it.  ``capture=True`` records one round
     (sync-free forward, draw, growth) into a hipGraph and replays it.  No progress bar; no autograd (the rounds run
     under ``torch.no_grad``).  Raises ``IndexError`` where the reference does (more rounds than likelihood columns),
-    ``RuntimeError`` for other states it would reject."""
+    ``RuntimeError`` for other states it would reject.
+
+    ``seeds`` (a SeedBank): seeded generation, in every mode.  ``gen``'s tensors are as the reference's ``__init__``
+    leaves them; one launch fills slot ``g >= 1`` with seed ``(g - 1) mod S``, every graph written out restarts from
+    seed ``(B - 1 + row) mod S`` (``row`` its index in ``generated_*``), and ``gen.generated_seed`` (int32 [C], on the
+    device, -1 past the rows written) names the seed each generated row was grown from.  The generated likelihood
+    rows hold the actions sampled after the (re)start only: the likelihood of the completion given the seed."""
     if poll_every < 1:
         raise ValueError("poll_every must be >= 1")
     model, B = gen.model, int(gen.batch_size)
@@ -202,9 +360,16 @@ def build_graphs(gen, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], *, un
             raise ValueError(f"uniforms must be [R, {B}], got {tuple(uniforms.shape)}")
         with _host_sync_allowed():                       # (set-up: a host tensor's upload may synchronise)
             uniforms = uniforms.to(device=dev, dtype=torch.float32).contiguous()
-    state = new_state(B, B, dev)
+    state = new_state(B, B, dev, seeded=seeds is not None)
+    gen_seed = None
+    if seeds is not None:
+        gen_seed = torch.full((t["generated_nodes"].shape[0],), -1, dtype=torch.int32, device=dev)
     mirror = _HostMirror(B)
-    grower = _Grower(t, dim_f_add, dim_f_conn, state, mirror.dev.value)
+    try:
+        grower = _Grower(t, dim_f_add, dim_f_conn, state, mirror.dev.value, seeds, gen_seed)
+    except Exception:
+        mirror.close()
+        raise
     nodes, edges, n_nodes, A = t["nodes"], t["edges"], t["n_nodes"], grower.A
     stream = torch.cuda.current_stream(dev)
     sync_free = capture or bool(getattr(model, "sync_free", False))
@@ -212,6 +377,8 @@ def build_graphs(gen, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], *, un
     graph = None
     try:
         with torch.no_grad(), torch.cuda.device(dev):
+            if seeds is not None:
+                grower.seed_init()
             if capture:
                 model.sync_free = True
                 u_buf = torch.zeros(B, dtype=torch.float32, device=dev)
@@ -263,6 +430,8 @@ def build_graphs(gen, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], *, un
             del graph
             mirror.close()
     gen.generation_rounds = rounds
+    if seeds is not None:
+        gen.generated_seed = gen_seed
     _raise_for_outcome("build_graphs", n, rounds, target, err, t["likelihoods"], uniforms)
     return n
 
@@ -320,9 +489,10 @@ class _GrowerRL(_Grower):
 
     def __init__(self, t: dict, prior: Sequence[torch.Tensor], traj: Optional[torch.Tensor],
                  dim_f_add: Sequence[int], dim_f_conn: Sequence[int], state: torch.Tensor,
-                 host_state: Optional[int] = None):
+                 host_state: Optional[int] = None, seeds: Optional[SeedBank] = None,
+                 gen_seed: Optional[torch.Tensor] = None):
         (B, _, _, _, _, Cg), _, _ = _validate_rl(t, prior, dim_f_add, dim_f_conn)
-        super().__init__(t, dim_f_add, dim_f_conn, state, host_state)
+        super().__init__(t, dim_f_add, dim_f_conn, state, host_state, seeds, gen_seed)
         if state.numel() < L.GROW_STATE_WORDS + 2 * B:
             raise ValueError("state must hold gi_grow_rl_state_words(B) = GI_GROW_STATE_WORDS + 2 B words "
                              "(generator.new_state(..., rl=True))")
@@ -351,24 +521,30 @@ class _GrowerRL(_Grower):
         d = self.desc_rl
         d.base.action, d.base.likelihood, d.base.flags = action.data_ptr(), like_agent.data_ptr(), flags.data_ptr()
         d.prior_likelihood = like_prior.data_ptr()
+        st = torch.cuda.current_stream(self.device).cuda_stream
         with torch.cuda.device(self.device):
-            L.check(L.load().gi_grow_graphs_rl(C.byref(d), torch.cuda.current_stream(self.device).cuda_stream),
-                    "gi_grow_graphs_rl")
+            if self.seed_desc is not None:
+                L.check(L.load().gi_grow_graphs_rl_seeded(C.byref(d), C.byref(self.seed_desc), st),
+                        "gi_grow_graphs_rl_seeded")
+            else:
+                L.check(L.load().gi_grow_graphs_rl(C.byref(d), st), "gi_grow_graphs_rl")
 
 
 def grow_step_rl(nodes, edges, n_nodes, agent_likelihoods, prior_likelihoods, generated_nodes, generated_edges,
                  generated_n_nodes, generated_agent_likelihoods, generated_prior_likelihoods, properly_terminated,
                  action, like_agent, like_prior, flags, dim_f_add: Sequence[int], dim_f_conn: Sequence[int],
-                 state: torch.Tensor, traj: Optional[torch.Tensor] = None) -> None:
+                 state: torch.Tensor, traj: Optional[torch.Tensor] = None, *, seeds: Optional[SeedBank] = None,
+                 generated_seed: Optional[torch.Tensor] = None) -> None:
     """One RL growth step (gi_grow_graphs_rl) on GraphGeneratorRL's tensors, in place, from
     ``sample_actions_rl_raw``'s ``(action, like_agent, like_prior, flags)``.  ``state`` = ``new_state(..., rl=True)``;
-    ``traj`` (int32 [3, C], optional) receives each generated row's source graph, first and last round."""
+    ``traj`` (int32 [3, C], optional) receives each generated row's source graph, first and last round.
+    ``seeds`` / ``generated_seed``: the seeded step (gi_grow_graphs_rl_seeded), as in ``grow_step``."""
     L.load()
     t = dict(nodes=nodes, edges=edges, n_nodes=n_nodes, likelihoods=agent_likelihoods,
              generated_nodes=generated_nodes, generated_edges=generated_edges, generated_n_nodes=generated_n_nodes,
              generated_likelihoods=generated_agent_likelihoods, properly_terminated=properly_terminated)
     _GrowerRL(t, (prior_likelihoods, generated_prior_likelihoods), traj, dim_f_add, dim_f_conn,
-              state).step(action, like_agent, like_prior, flags)
+              state, seeds=seeds, gen_seed=generated_seed).step(action, like_agent, like_prior, flags)
 
 
 def traj_gather(like_agent: Optional[torch.Tensor], like_prior: Optional[torch.Tensor], traj: torch.Tensor, n: int,
@@ -435,7 +611,7 @@ class _TrajGather(torch.autograd.Function):
 
 def build_graphs_rl(gen, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], *,
                     uniforms: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
-                    poll_every: int = 1) -> int:
+                    poll_every: int = 1, seeds: Optional[SeedBank] = None) -> int:
     """Drop-in for ``GraphGeneratorRL.build_graphs`` (GraphGeneratorRL.py:109-172): ``gen`` is the reference's RL
     generator (duck-typed: ``agent_model``, ``prior_model``, ``batch_size`` and the tensors of its
     ``allocate_graph_tensors`` / ``initialize_graph_batch``), mutated in place; returns ``n_generated_so_far`` and
@@ -449,7 +625,11 @@ def build_graphs_rl(gen, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], *,
     values without an autograd graph.  ``uniforms``, ``generator`` and the exceptions are ``build_graphs``'.  The host
     reads the mapped counters every ``poll_every`` rounds after waiting for the round ``poll_every - 1`` rounds back:
     every round already waits for its forwards' counts, so the default 1 costs a short wait per round and enqueues
-    no round past the target (each would cost two forwards with grad); the result does not depend on it."""
+    no round past the target (each would cost two forwards with grad); the result does not depend on it.
+
+    ``seeds`` (a SeedBank): seeded generation as in ``build_graphs`` — the first fill, restarts from seed
+    ``(B - 1 + row) mod S``, ``gen.generated_seed``; both likelihood streams and their gradients are those of the
+    completions given the seeds."""
     if poll_every < 1:
         raise ValueError("poll_every must be >= 1")
     agent, prior, B = gen.agent_model, gen.prior_model, int(gen.batch_size)
@@ -463,15 +643,19 @@ def build_graphs_rl(gen, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], *,
         with _host_sync_allowed():
             uniforms = uniforms.to(device=dev, dtype=torch.float32).contiguous()
     Cg, L_cols = t["generated_likelihoods"].shape
-    state = new_state(B, B, dev, rl=True)
+    state = new_state(B, B, dev, rl=True, seeded=seeds is not None)
     traj = torch.zeros((3, Cg), dtype=torch.int32, device=dev)
+    gen_seed = torch.full((Cg,), -1, dtype=torch.int32, device=dev) if seeds is not None else None
     mirror = _HostMirror(B)
     try:
-        grower = _GrowerRL(t, prior_t, traj, dim_f_add, dim_f_conn, state, mirror.dev.value)
+        grower = _GrowerRL(t, prior_t, traj, dim_f_add, dim_f_conn, state, mirror.dev.value, seeds, gen_seed)
         nodes, edges, n_nodes, A = t["nodes"], t["edges"], t["n_nodes"], grower.A
         stream = torch.cuda.current_stream(dev)
         likes_a, likes_p = [], []
         with torch.cuda.device(dev):
+            if seeds is not None:
+                with torch.no_grad():
+                    grower.seed_init(prior_t[0])
             pending = collections.deque()
             r = 0
             while uniforms is None or r < uniforms.shape[0]:
@@ -502,6 +686,8 @@ def build_graphs_rl(gen, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], *,
         with _host_sync_allowed():
             mirror.close()
     gen.generation_rounds = rounds
+    if seeds is not None:
+        gen.generated_seed = gen_seed
     _raise_for_outcome("build_graphs_rl", n, rounds, target, err, t["likelihoods"], uniforms)
     del likes_a[rounds:], likes_p[rounds:]               # frozen rounds leave the autograd graph with these
     gen_a, gen_p = _TrajGather.apply(torch.stack(likes_a), torch.stack(likes_p), traj, n, L_cols)

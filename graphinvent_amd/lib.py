@@ -133,6 +133,11 @@ class GrowRlDesc(C.Structure):
                                                          "prior_likelihood", "traj")]
 
 
+class GrowSeedDesc(C.Structure):
+    """gi_grow_seed_desc"""
+    _fields_ = [(n, vp) for n in ("nodes", "edges", "n_nodes", "gen_seed")] + [("S", ci)]
+
+
 class DropoutParams(C.Structure):                       # gi_dropout_params
     _fields_ = [("seed", C.c_ulonglong), ("id", C.c_uint), ("thresh", C.c_uint),
                 ("a", C.c_float), ("b_keep", C.c_float), ("b_drop", C.c_float)]
@@ -225,6 +230,10 @@ SIGNATURES = {
     "gi_grow_graphs": (ci, [C.POINTER(GrowDesc), vp]),
     "gi_grow_rl_state_words": (ci, [ci]),
     "gi_grow_graphs_rl": (ci, [C.POINTER(GrowRlDesc), vp]),
+    "gi_grow_seeded_state_words": (ci, [ci]),
+    "gi_grow_seed_init": (ci, [C.POINTER(GrowDesc), C.POINTER(GrowSeedDesc), vp, vp]),
+    "gi_grow_graphs_seeded": (ci, [C.POINTER(GrowDesc), C.POINTER(GrowSeedDesc), vp]),
+    "gi_grow_graphs_rl_seeded": (ci, [C.POINTER(GrowRlDesc), C.POINTER(GrowSeedDesc), vp]),
     "gi_grow_traj_gather": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]),
     "gi_grow_traj_scatter": (ci, [ci, ci, ci, ci, ci, vp, vp, ci, vp, ci, vp, vp, vp]),
     "gi_side_stream_create": (ci, [C.POINTER(vp)]),

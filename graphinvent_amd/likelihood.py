@@ -152,10 +152,21 @@ class _ChunkLogLik(torch.autograd.Function):
         return d, None, None, None, None, None, g_ll, g_kind
 
 
+def completion_hot(hot: torch.Tensor, row_mol: torch.Tensor, row_step: torch.Tensor, lengths: torch.Tensor,
+                   given_actions: torch.Tensor) -> torch.Tensor:
+    """``hot`` with -1 on the rows of the given part of every route.  Row ``k`` of a route is the state before the
+    ``k``-th last build action (``k = 0`` the terminate), and molecule ``m`` has ``lengths[m] - 1 = n_edges + 1``
+    build actions: with the first ``given_actions[m]`` of them given, the rows that stay are those with
+    ``row_step <= n_edges + 1 - given_actions[m]``.  Torch ops on the tensors' device, no read-back."""
+    m = row_mol.clamp(min=0).long()
+    last = (lengths.to(torch.int32) - 1 - given_actions.to(torch.int32))[m]
+    return torch.where((row_mol < 0) | (row_step > last), -1, hot).to(torch.int32)
+
+
 class _Scored:
     """The expansion of a call and what its chunk loop needs."""
 
-    def __init__(self, nodes, edges, dim_f_add, dim_f_conn, batch_rows, n_rows, invalid):
+    def __init__(self, nodes, edges, dim_f_add, dim_f_conn, batch_rows, n_rows, invalid, given_actions=None):
         if invalid not in ("raise", "skip"):
             raise ValueError("invalid must be 'raise' or 'skip'")
         if int(batch_rows) < 1:
@@ -167,6 +178,13 @@ class _Scored:
         self.n_conn = N * d.Fe
         self.n_add = self.W - 1 - self.n_conn
         self.p = None
+        self.given_bad = None
+        if given_actions is not None:
+            with _host_sync_allowed():                               # (set-up: a host sequence's upload)
+                given_actions = torch.as_tensor(given_actions)
+                if tuple(given_actions.shape) != (M,) or given_actions.dtype.is_floating_point:
+                    raise ValueError(f"given_actions must be {M} integers, one per molecule")
+                given_actions = given_actions.to(device=self.dev, dtype=torch.int32)
         if M == 0:
             return
         with torch.cuda.device(self.dev):
@@ -186,6 +204,9 @@ class _Scored:
             self.row_mol = p.row_mol[:cap]
             # the rows past the real ones (an n_rows larger than the molecules need, skipped molecules) are padding
             self.hot = torch.where(self.row_mol < 0, -1, p.hot).to(torch.int32)
+            if given_actions is not None:
+                self.hot = completion_hot(self.hot, self.row_mol, p.row_step[:cap], p.lengths, given_actions)
+                self.given_bad = (((given_actions < 0) | (given_actions > p.lengths - 1)) & (p.mol_err == 0)).any()
             self.err = torch.zeros(1, dtype=torch.int32, device=self.dev)
 
     def chunks(self):
@@ -200,6 +221,7 @@ class _Scored:
         with _host_sync_allowed():
             counts = p.counts.cpu().tolist()
             bits = int(self.err.item())
+            given_bad = self.given_bad is not None and bool(self.given_bad.item())
             if getattr(model, "sync_free", False) and hasattr(model, "last_bounded_error"):
                 model.last_bounded_error()
         err, total = int(counts[0]), int(counts[1])
@@ -208,6 +230,8 @@ class _Scored:
         if total > p.cap or (self.expect is not None and not err and total != self.expect):
             raise ValueError(f"the molecules expand to {total} rows, not the {p.cap} the call was sized for "
                              "(n_rows must be route_lengths(nodes, edges).sum())")
+        if given_bad:
+            raise ValueError("given_actions: a value is outside [0, n_edges + 1] of its molecule")
         if bits:
             raise RuntimeError("graphinvent_amd likelihood: " + _describe(bits))
         if self.invalid == "raise":
@@ -227,7 +251,7 @@ def _result(ll, kind, mol_err, by_kind, invalid):
 
 def molecule_log_likelihood(model, nodes: torch.Tensor, edges: torch.Tensor, dim_f_add: Sequence[int],
                             dim_f_conn: Sequence[int], *, batch_rows: int = 1000, by_kind: bool = False,
-                            n_rows: Optional[int] = None, invalid: str = "raise"):
+                            n_rows: Optional[int] = None, invalid: str = "raise", given_actions=None):
     """``ll_m`` (module docstring) of ``M`` whole molecules under ``model``: fp32 ``[M]`` on the molecules' device.
 
     ``nodes`` / ``edges``: int8 device molecules ``[M, N, Fn]`` / ``[M, N, N, Fe]`` under ``routes.expand``'s
@@ -253,8 +277,19 @@ def molecule_log_likelihood(model, nodes: torch.Tensor, edges: torch.Tensor, dim
     ``invalid="raise"``: a molecule that violates the contract raises ``ValueError`` naming the rule.  ``"skip"``:
     such molecules give NaN and the per-molecule error bits (int32 ``[M]``, ``lib.ROUTE_ERR_*``) are appended to
     the result, as ``routes.reorder`` does.  ``M == 0`` returns empty tensors; CPU tensors raise ``RuntimeError``.
+
+    ``given_actions`` (int32 ``[M]`` device tensor, or a sequence; default None = 0 everywhere, bit-identical):
+    the likelihood of a COMPLETION.  The first ``given_actions[m]`` build actions of molecule ``m``'s route (a
+    molecule has ``n_edges + 1`` of them: its first atom, then one per bond) are taken as given — e.g.
+    ``SeedBank.n_actions`` of the seed a generated molecule was grown from — and the sum runs over the rest, the
+    terminate included: the rows with ``row_step <= n_edges + 1 - given_actions[m]``.  The other rows still pass
+    through the model but enter with ``hot = -1``, which the kernels turn into exact zeros, forward and backward;
+    ``by_kind`` follows the same mask.  A value outside ``[0, n_edges + 1]`` raises ``ValueError`` (with the call's
+    read-back, after the loop).  Because the route fixes ONE order of a node's ring-closing bonds, this value equals
+    the completion likelihood the generator recorded for a sampled molecule only when the sampled order was the
+    route's.
     """
-    s = _Scored(nodes, edges, dim_f_add, dim_f_conn, batch_rows, n_rows, invalid)
+    s = _Scored(nodes, edges, dim_f_add, dim_f_conn, batch_rows, n_rows, invalid, given_actions)
     mol_ll = torch.zeros(s.M, dtype=torch.float32, device=s.dev)
     mol_kind = torch.zeros((s.M, 3), dtype=torch.float32, device=s.dev) if by_kind else None
     if s.M == 0:
@@ -272,7 +307,7 @@ def molecule_log_likelihood(model, nodes: torch.Tensor, edges: torch.Tensor, dim
 
 def weighted_log_likelihood_backward(model, nodes: torch.Tensor, edges: torch.Tensor, dim_f_add: Sequence[int],
                                      dim_f_conn: Sequence[int], weights: torch.Tensor, *, batch_rows: int = 1000,
-                                     n_rows: Optional[int] = None, invalid: str = "raise"):
+                                     n_rows: Optional[int] = None, invalid: str = "raise", given_actions=None):
     """Accumulates the gradients of ``sum_m weights[m] * ll_m`` with respect to the model's parameters into their
     ``.grad`` and returns the ``ll`` values (detached; with ``invalid="skip"`` also the error bits), for the
     arguments of ``molecule_log_likelihood``.
@@ -281,8 +316,9 @@ def weighted_log_likelihood_backward(model, nodes: torch.Tensor, edges: torch.Te
     whatever the size of the set.  This is exact, not an approximation: once the weights are known the objective is
     linear in the row terms, so the gradient of the whole is the sum of the chunks' gradients, each taken with
     ``d objective / d row_ll[r] = weights[row_mol[r]]``.  ``weights`` (``[M]``, on the molecules' device) is a
-    constant here; a molecule that ``invalid="skip"`` refuses has no rows and contributes nothing."""
-    s = _Scored(nodes, edges, dim_f_add, dim_f_conn, batch_rows, n_rows, invalid)
+    constant here; a molecule that ``invalid="skip"`` refuses has no rows and contributes nothing.
+    ``given_actions``: as in ``molecule_log_likelihood`` — the given rows contribute neither value nor gradient."""
+    s = _Scored(nodes, edges, dim_f_add, dim_f_conn, batch_rows, n_rows, invalid, given_actions)
     if not torch.is_tensor(weights) or tuple(weights.shape) != (s.M,):
         raise ValueError(f"weights must be a tensor of {s.M} entries, one per molecule")
     if s.M and weights.device != s.dev:

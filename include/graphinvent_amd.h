@@ -749,6 +749,42 @@ typedef struct gi_grow_rl_desc {
 int gi_grow_rl_state_words(int B);
 int gi_grow_graphs_rl(const gi_grow_rl_desc* desc, void* stream);
 
+/* Seeded generation — the growth step with a bank of S >= 1 seed molecules (scaffolds) in the loader's int8 molecule
+ * format, from which every graph starts and restarts instead of from the empty graph.  The bank is tightly packed
+ * (seed s begins at byte s * N * Fn of nodes, s * N * N * Fe of edges): nothing is assumed of its alignment beyond
+ * the base pointers, and the kernels read it one byte per element.  The caller guarantees what routes.check verifies:
+ * 0 / 1 entries, n_nodes[s] in [0, N] equal to the number of non-padding node rows, nodes in a valid decoding order.
+ *   - gi_grow_seed_init writes the first fill: slot 0 stays the dummy graph; slot g >= 1 takes seed (g - 1) mod S —
+ *     nodes and edges converted to fp32, n_nodes set, its likelihood row (and the row of prior_likelihoods [B, L] when
+ *     that is not NULL) zeroed.  Of desc it reads nodes, edges, n_nodes, likelihoods, state and B, N, Fn, Fe, L.
+ *   - seed[g] = state[GI_GROW_STATE_WORDS + 2 B + g] is the seed slot g currently grows from (-1 for slot 0).
+ *     state = gi_grow_seeded_state_words(B) = GI_GROW_STATE_WORDS + 3 B ints, for both seeded steps; every word
+ *     of gi_grow_graphs / gi_grow_graphs_rl keeps its meaning (the start rounds stay at + B), zero-filled with
+ *     state[2] = target before gi_grow_seed_init.
+ *   - gi_grow_graphs_seeded / gi_grow_graphs_rl_seeded are gi_grow_graphs / gi_grow_graphs_rl (same three launches,
+ *     slots, freeze after the target or an error, dummy graph's restore, host mirror, trajectory record, error bits)
+ *     except that graph S[k], copied to generated row `row` = n + k, is reset to seed (B - 1 + row) mod S instead of
+ *     to zeros, gen_seed[row] (when not NULL) receives seed[g], and seed[g] becomes the new seed.  No counter is
+ *     added: the choice is a function of the row alone, deterministic and round-robin over the bank (the first fill
+ *     uses seeds 0 .. B - 2, row 0 continues with B - 1); shuffle the bank to randomise.  The likelihood rows are
+ *     reset to zeros as before.
+ * A generated likelihood row holds only the actions sampled after the slot's (re)start: it is the likelihood of the
+ * COMPLETION given the seed, not of the whole molecule.  The empty seed (n_nodes = 0, all bytes zero) is legal and
+ * behaves exactly like the unseeded reset; a seed with n_nodes = N is legal too: the sampler's validity rules then
+ * leave only connect and terminate. */
+typedef struct gi_grow_seed_desc {
+    const signed char* nodes;      /* [S, N, Fn] int8, device */
+    const signed char* edges;      /* [S, N, N, Fe] */
+    const signed char* n_nodes;    /* [S] */
+    int* gen_seed;                 /* [C] or NULL: the seed each generated row was grown from */
+    int S;
+} gi_grow_seed_desc;
+int gi_grow_seeded_state_words(int B);
+int gi_grow_seed_init(const gi_grow_desc* desc, const gi_grow_seed_desc* seeds, float* prior_likelihoods,
+                      void* stream);
+int gi_grow_graphs_seeded(const gi_grow_desc* desc, const gi_grow_seed_desc* seeds, void* stream);
+int gi_grow_graphs_rl_seeded(const gi_grow_rl_desc* desc, const gi_grow_seed_desc* seeds, void* stream);
+
 /* The generated likelihood rows of a finished RL loop from the per-round likelihoods, and the backward of that map;
  * both sides (agent a, prior p) in one launch each, a side with NULL pointers skipped.  like_* are [R, B] (row c =
  * round c's like_agent / like_prior), traj is the [3, C] record of gi_grow_graphs_rl, n = rows generated.
