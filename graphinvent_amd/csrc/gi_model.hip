@@ -215,7 +215,8 @@ void make_ws(const Model& m, int S, int E, int U, int D0, Ws& w) {
     w.ldG = gi_r4(d.G); w.ldA = gi_r4(d.A); w.ldC = gi_r4(d.C); w.ldEh = gi_r4(d.enn_hidden);
     w.ldAtt = gi_r4(d.att_hidden); w.ldEmb = gi_r4(d.emb_hidden); w.ldM1 = gi_r4(d.mlp1_hidden);
     w.ldM2 = gi_r4(d.mlp2_hidden); w.ldNA = gi_r4(m.NA); w.ldNC = gi_r4(m.NC);
-    w.ldCA = gi_r4(m.NA + d.G); w.ldCC = gi_r4(m.NC + d.G); w.ldZG = gi_r4(2 * d.G);
+    w.ldCA = gi_r4(m.NA + d.G); w.ldCC = gi_r4(m.NC + d.G);
+    w.ldZG = 2 * d.G;         // (gi_gather_readout_bwd writes zpart dense, [B, 2 G]: no pitch argument, no padding)
     const bool attn = d.kind == GI_KIND_ATTGGNN;
     w.ldEa = attn ? gi_r4(d.eatt_hidden) : 4;
     long long o = 0;

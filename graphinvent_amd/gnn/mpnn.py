@@ -59,6 +59,10 @@ def _dims_from_constants(c, B: int, kind: int = _L.KIND_GGNN) -> "_L.GgnnDims":
     return d
 
 
+#: the smallest hidden / message / embedding width of the HIP models (see ``_check_limits``)
+MIN_WIDTH = 4
+
+
 def _check_limits(c, kind: int) -> None:
     """The compiled-in limits of the HIP model (``gi_ggnn_num_params``), checked when the model is built: the
     reference accepts any value, and past a limit the forward could only report a parameter-table mismatch."""
@@ -74,6 +78,23 @@ def _check_limits(c, kind: int) -> None:
         v = getattr(c, key)
         if not lo <= v <= hi:
             raise ValueError(f"{key} = {v}: the HIP model supports {key} from {lo} to {hi}")
+    # Widths: every weight matrix is read as PyTorch stores it, [fan_out, fan_in] with rows of fan_in floats, and the
+    # GEMM family reads rows in 16-byte vectors (gi_gemm refuses narrower rows unless they are stored padded; the chain
+    # kernels and the fused GRU need 4 columns too).  So every width that is some layer's fan-in — the hidden and message
+    # sizes, the graph embedding, the hidden width of every stack that has a hidden layer — must be at least 4; the
+    # reference accepts 1 to 3, and the forward could only answer GI_EINVAL.
+    widths = [("hidden_node_features", None), ("message_size", None), ("mlp1_hidden_dim", "mlp1_depth"),
+              ("mlp2_hidden_dim", "mlp2_depth")]
+    if kind != _L.KIND_MNN:
+        widths += [("gather_width", None), ("gather_att_hidden_dim", "gather_att_depth"),
+                   ("gather_emb_hidden_dim", "gather_emb_depth")]
+        widths += [("msg_hidden_dim", "msg_depth"), ("att_hidden_dim", "att_depth")] if kind == _L.KIND_ATTGGNN \
+            else [("enn_hidden_dim", "enn_depth")]
+    for key, depth in widths:
+        v = getattr(c, key)
+        if v < MIN_WIDTH and (depth is None or getattr(c, depth) > 0):
+            raise ValueError(f"{key} = {v}: the HIP model supports {key} of at least {MIN_WIDTH} "
+                             f"(one 16-byte vector of fp32)")
 
 
 def _unused_without_passes(c, dims) -> int:

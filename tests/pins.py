@@ -110,7 +110,8 @@ class OraclePins:
         self.E = eb.size
         self.etype = edges[eb, ei, ej, :].argmax(1)
         in_perm = np.asarray(g["in_perm"]).astype(np.int64)
-        assert in_perm.size == self.E
+        # (MNN has no per-edge SELU; its batches may carry several bond types on a pair = parallel edges in in_perm)
+        assert in_perm.size == self.E or model == "MNN"
         self.edge_row = torch.from_numpy(in_perm)          # oracle edge k -> message row
         self.cidx = torch.from_numpy(np.asarray(g["cidx"]).astype(np.int64))
         # pass-0 class rows: message row u -> class row (same bond type, same source feature row)

@@ -276,11 +276,15 @@ def _variant(name):
     if name == "narrow_readout":             # every node-level layer below BF3_MIN_WIDTH: no 16-bit-pipe launch
         return "GGNN", O.shaped_config(*g, gather_att_hidden_dim=160, gather_emb_hidden_dim=160,
                                        mlp1_hidden_dim=160, mlp2_hidden_dim=160), plain, None
+    if name in ("ggnn_r2_r1", "att_r2_r1", "mnn_r2_r1"):    # widths that are no multiple of 4: padded images and cells
+        from tests.test_widths_gpu import CASES, config
+        kind, over = CASES[name]
+        return kind, config(kind, over), plain, None
     raise KeyError(name)
 
 
 @pytest.mark.parametrize("name", ["mnn", "wide_enn", "wide_h", "implicit_h", "narrow_readout", "depth0", "passes1",
-                                  "chain_maxl", "chain_over"])
+                                  "chain_maxl", "chain_over", "ggnn_r2_r1", "att_r2_r1", "mnn_r2_r1"])
 @pytest.mark.parametrize("sync_free", [False, True])
 def test_model_variants(name, sync_free):
     kind, cfg, make, bounds = _variant(name)

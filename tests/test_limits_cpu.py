@@ -3,7 +3,8 @@
 The reference accepts any depth, pass count, graph size and number of bond types; the HIP model supports stack
 depths 0..11, 0..16 message passes, max_n_nodes <= GI_MAX_NODES and n_edge_features <= GI_MAX_GROUPS
 (csrc/gi_model.hip build_model).  Past a limit the model must refuse at construction, naming the limit; the C ABI
-answers GI_ELIMIT, as include/graphinvent_amd.h documents."""
+answers GI_ELIMIT, as include/graphinvent_amd.h documents.  Widths below 4 floats (one 16-byte vector) are refused at
+construction too, for every width that is some layer's fan-in."""
 import ctypes as C
 
 import pytest
@@ -70,6 +71,40 @@ def test_mnn_past_a_limit_fails_at_construction(key, value):
     with pytest.raises(ValueError, match=rf"{key} = {value}: "):
         mpnn.MNN(MO.as_constants(cfg))
     assert L.load().gi_ggnn_num_params(C.byref(_dims(cfg, L.KIND_MNN))) == -2
+
+
+WIDTH_KEYS = {
+    "GGNN": [("hidden_node_features", None), ("message_size", None), ("gather_width", None),
+             ("enn_hidden_dim", "enn_depth"), ("gather_att_hidden_dim", "gather_att_depth"),
+             ("gather_emb_hidden_dim", "gather_emb_depth"), ("mlp1_hidden_dim", "mlp1_depth"),
+             ("mlp2_hidden_dim", "mlp2_depth")],
+    "AttGGNN": [("hidden_node_features", None), ("message_size", None), ("gather_width", None),
+                ("msg_hidden_dim", "msg_depth"), ("att_hidden_dim", "att_depth"),
+                ("gather_att_hidden_dim", "gather_att_depth"), ("gather_emb_hidden_dim", "gather_emb_depth"),
+                ("mlp1_hidden_dim", "mlp1_depth"), ("mlp2_hidden_dim", "mlp2_depth")],
+    "MNN": [("hidden_node_features", None), ("message_size", None), ("mlp1_hidden_dim", "mlp1_depth"),
+            ("mlp2_hidden_dim", "mlp2_depth")],
+}
+
+
+@pytest.mark.parametrize("model,key,depth", [(m, k, d) for m, keys in WIDTH_KEYS.items() for k, d in keys])
+def test_a_width_below_one_vector_fails_at_construction_naming_it(model, key, depth):
+    """Widths of 1 to 3 (the reference accepts them) are the row length of a weight matrix that the GEMM family reads
+    as stored, in 16-byte vectors: refused when the model is built, for every such key; 4 builds, and so does a
+    narrower hidden width of a stack without hidden layers (depth 0), which never uses it."""
+    if model == "MNN":
+        cls, make, consts = mpnn.MNN, lambda **kw: MO.tiny_config(**kw), MO.as_constants
+    else:
+        cls = mpnn.AttentionGGNN if model == "AttGGNN" else mpnn.GGNN
+        make = lambda **kw: O.make_config(**dict(TINY_ATT if model == "AttGGNN" else TINY, **kw))
+        consts = O.as_constants
+    for v in (1, 2, 3):
+        with pytest.raises(ValueError, match=rf"{key} = {v}: .* at least 4"):
+            cls(consts(make(**{key: v})))
+    if key != "hidden_node_features":                          # (H >= n_node_features, which the tiny configs set to 5)
+        cls(consts(make(**{key: 4})))
+    if depth is not None:
+        cls(consts(make(**{key: 1, depth: 0})))
 
 
 def test_chain_longer_than_its_layer_limit_is_a_limit_error():

@@ -166,3 +166,61 @@ def test_aggregate_first_identity_fp64(nodedup):
                 dh[c] += dS[g["mu_dst"][k], :, u_type[u]]
     lhs = float((dS.reshape(R, -1) * S).sum())
     assert abs(lhs - float((dh * h).sum())) < 1e-10 * max(1.0, abs(lhs))
+
+
+# ---- the fp32 mirrors of the MNN kernels (what tests/test_mnn_dims_gpu.py compares the kernels with bit for bit) ----
+def _mirror_cases():
+    return [(name, H) for name, hs in MO.KERNEL_CASES.items() for H in hs]
+
+
+@pytest.mark.parametrize("name,H", _mirror_cases())
+def test_typed_sum_mirrors_within_the_fp32_bound_of_fp64(name, H):
+    """The mirrors add fp32 terms in the kernels' documented order; against the fp64 sums they may lose at most
+    (terms - 1) * 2^-24 * sum |terms| per element — and nothing where an element has at most one term."""
+    n, e, nodedup = MO.kernel_case(name)
+    Fe = e.shape[3]
+    g = compact(n, e, nodedup=nodedup)
+    R = g["S"] + 1
+    if name.startswith("fe"):
+        assert (np.diff(g["type_off"]) > 0).all()
+    if name.startswith("hub"):
+        assert np.diff(g["seg_off"]).max() == 127 and np.diff(g["src_off"]).max() >= 3
+        assert name == "hub_alone" and R == 129 or R * ((H + 3) // 4) > 3 * 256
+    rng = np.random.default_rng(H)
+    h = rng.standard_normal((R, H)).astype(np.float32)
+    h[R - 1] = 0.0
+    ut = MO.u_types(g)
+    ref = MO.typed_sums(h.astype(np.float64), g["in_perm"], g["u_src"], ut, g["seg_off"], Fe)
+    got = MO.typed_sums_mirror(h, g, Fe)
+    bound = MO.typed_sums_bound(h, g, Fe)
+    assert got.dtype == np.float32 and (np.abs(got - ref) <= bound).all()
+    assert not got[np.diff(g["seg_off"]) == 0].any()
+    if g["E"]:
+        assert bound.max() > 0                                # (the case does have sums of several terms)
+    # transpose
+    dS = rng.standard_normal((R, H * Fe)).astype(np.float32)
+    dh0 = rng.standard_normal((R, H)).astype(np.float32)
+    ref_t, terms, mag = MO.typed_sums_t(dS.astype(np.float64), g, Fe)
+    got_t = MO.typed_sums_t_mirror(dS, g, Fe)
+    assert (np.abs(got_t - ref_t) <= (np.maximum(terms - 1, 0) * 2.0 ** -24)[:, None] * mag).all()
+    got_a = MO.typed_sums_t_mirror(dS, g, Fe, dh0)
+    assert (np.abs(got_a - (ref_t + dh0)) <= (terms * 2.0 ** -24)[:, None] * (mag + np.abs(dh0))).all()
+    # the adjoint identity ties the two index structures together: <dS, T h> == <T^t dS, h>
+    lhs = float((dS.astype(np.float64) * ref).sum())
+    assert abs(lhs - float((ref_t * h).sum())) < 1e-9 * max(1.0, float((np.abs(dS) * np.abs(ref)).sum()))
+
+
+@pytest.mark.parametrize("N", [1, 13, 88, 128])
+@pytest.mark.parametrize("H", [1, 10, 50])
+def test_graph_sum_mirror_within_the_fp32_bound_of_fp64(N, H):
+    B = 7
+    n, e, _ = synthetic.make_batch(B, N, 3, 2, 3, seed=N, frac_empty=0.15, frac_single=0.15)
+    g = compact(n, e)
+    R = g["S"] + 1
+    h = np.random.default_rng(N + H).standard_normal((R, H)).astype(np.float32)
+    h[R - 1] = 0.0
+    c = g["cidx"].reshape(B, N)
+    ref = h.astype(np.float64)[c].sum(1)
+    mag = np.abs(h.astype(np.float64))[c].sum(1)
+    got = MO.graph_sum_mirror(h, g["cidx"], B, N)
+    assert got.dtype == np.float32 and (np.abs(got - ref) <= (N - 1) * 2.0 ** -24 * mag).all()
