@@ -7,9 +7,14 @@ graph and ``.item()`` on every bond index, i.e. one device-to-host synchronisati
 
 ``molecular_properties(nodes, edges, n_nodes, groups, ...)`` is one launch (``gi_mol_properties``) over the generator's
 own tensors and returns the dictionary entries of ``get_molecular_properties`` that need no RDKit, as fp32 tensors on
-the device with the reference's shapes and values.  ``fraction_unique``, ``fraction_valid`` and
-``fraction_valid_properly_terminated`` are NOT produced: they come from RDKit's sanitisation and SMILES, and the
-caller merges them into the dictionary.
+the device with the reference's shapes and values.  ``fraction_valid`` and ``fraction_valid_properly_terminated`` are
+NOT produced: they come from RDKit's sanitisation, and the caller merges them into the dictionary, as it does
+``fraction_unique`` (from ``fraction_unique`` below, with RDKit's validity as the mask).
+
+``canonical`` / ``unique`` / ``fraction_unique`` / ``SeenSet`` decide which molecules are the SAME molecule, on the
+device (``gi_mol_canon``, ``gi_mol_unique``, ``gi_mol_seen_add``): the reference's ``uniqueness_tensor``
+(util.py:549-585) and ``fraction_unique`` (Analyzer.py:480-499) without a SMILES string.  Identity here is isomorphism
+of the labelled graph (node feature rows, bond types), see ``canonical``.
 
 ``decode(nodes, edges, n_nodes, groups)`` is one launch (``gi_mol_decode``) that writes what ``_graph_to_mol`` reads
 out of the tensors: per atom the index inside each one-hot segment, per graph the bond triples in
@@ -68,8 +73,8 @@ def _check_inputs(what: str, nodes, edges, n_nodes, groups: Sequence[int], need_
         raise ValueError(f"{what}: edges is on {edges.device}, nodes on {nodes.device}")
     if not nodes.is_contiguous() or not edges.is_contiguous():
         raise ValueError(f"{what}: nodes and edges must be contiguous (they are read in place, once)")
-    groups = [int(g) for g in groups]
-    if not 2 <= len(groups) <= 4 or min(groups) < 1 or sum(groups) != Fn:
+    groups = None if groups is None else [int(g) for g in groups]     # None: the caller has no use for segments
+    if groups is not None and (not 2 <= len(groups) <= 4 or min(groups) < 1 or sum(groups) != Fn):
         raise ValueError(f"{what}: groups {groups} must be 2 to 4 positive segment sizes (atom type, formal charge, "
                          f"[implicit H], [chirality]) that sum to Fn = {Fn}")
     if N < 1 or Fn < 1 or Fe < 1 or N > L.GI_MAX_NODES or Fe > L.GI_MAX_GROUPS or Fn > L.ANALYZE_MAX_FN:
@@ -311,3 +316,208 @@ def records(decoded, atom_types: Sequence, formal_charge: Sequence, imp_H: Optio
         kept = min(int(n_bonds[g]), bonds.shape[1])
         mol_bonds = [(i, j, t if int_to_bondtype is None else int_to_bondtype[t]) for i, j, t in bonds[g, :kept].tolist()]
         yield mol_atoms, mol_bonds
+
+
+# ---- molecule identity -------------------------------------------------------------------------------------------
+#: status bits of ``canonical`` beyond ``STATUS_MESSAGES``' MOL_BOND_PAST_N and MOL_VALUE
+CANON_STATUS_MESSAGES = {
+    L.MOL_BOND_PAST_N: STATUS_MESSAGES[L.MOL_BOND_PAST_N],
+    L.MOL_VALUE: STATUS_MESSAGES[L.MOL_VALUE],
+    L.MOL_ASYMMETRIC: "edges[i, j, t] is set and edges[j, i, t] is not",
+    L.MOL_NODE_PAST_N: "a node row >= n_nodes has a set entry, or n_nodes is outside [0, N]",
+}
+
+
+class CanonicalMolecules:
+    """What ``canonical`` wrote, on the device: ``order`` / ``rank`` [G, N] int32, ``key`` [G, 2] int64 (the two
+    64-bit words of the key, as torch has no uint64 arithmetic; ``host()`` gives uint64), ``status`` [G] int32 — views
+    of one byte buffer so that ``host()`` needs one copy — and, if asked for, ``nodes`` [G, N, Fn] / ``edges``
+    [G, N, N, Fe] int8, the canonical molecules (``None`` otherwise; not part of ``host()``)."""
+
+    def __init__(self, buf: torch.Tensor, G: int, N: int, nodes=None, edges=None):
+        self._buf, self._host, self._pinned = buf, None, None
+        self.G, self.N, self.nodes, self.edges = G, N, nodes, edges
+        self.order, self.rank, self.key, self.status = self._views(buf, torch)
+
+    @staticmethod
+    def nbytes(G: int, N: int) -> int:
+        return 16 * G + 8 * G * N + 4 * G                   # key | order | rank | status: each aligned to itself
+
+    def _views(self, buf, xp):
+        G, N = self.G, self.N
+        o_o, o_r, o_s = 16 * G, 16 * G + 4 * G * N, 16 * G + 8 * G * N
+        key = buf[:o_o].view(xp.int64 if xp is torch else xp.uint64).reshape(G, 2)
+        order, rank = buf[o_o:o_r].view(xp.int32).reshape(G, N), buf[o_r:o_s].view(xp.int32).reshape(G, N)
+        return order, rank, key, buf[o_s:].view(xp.int32)
+
+    def host(self):
+        """-> numpy ``(order, rank, key, status)``, ``key`` as uint64: ONE asynchronous copy into pinned memory and
+        ONE synchronisation (of the current stream), done once and kept."""
+        if self._host is None:
+            dev = self._buf.device
+            with _host_sync_allowed():
+                pinned = torch.empty(self._buf.numel(), dtype=torch.uint8, pin_memory=True)
+                if self.G > 0:
+                    stream = torch.cuda.current_stream(dev)
+                    with torch.cuda.device(dev):
+                        pinned.copy_(self._buf, non_blocking=True)
+                    stream.synchronize()
+            self._pinned = pinned
+            self._host = self._views(pinned.numpy(), np)
+        return self._host
+
+    def __len__(self):
+        return self.G
+
+
+def canonical(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Optional[torch.Tensor] = None, *,
+              want_molecules: bool = False) -> CanonicalMolecules:
+    """A canonical node order, the canonical form and a 128-bit key of every molecule, in one launch
+    (``gi_mol_canon``); inputs as ``molecular_properties`` (no ``groups``; ``n_nodes = None`` takes the number of
+    LEADING node rows with a set entry, the convention of ``routes.check``).  The nodes may be in any order.
+
+    WHAT IDENTITY MEANS: two molecules are equal iff their labelled graphs are isomorphic — node feature rows and bond
+    types, nothing else.  The reference compares canonical SMILES after RDKit's sanitisation, so a Kekule and an
+    aromatic encoding of one compound are equal there and DIFFERENT here; two tensors that differ only in the order of
+    the nodes are equal in both.
+
+    ``order[g, a]`` is the input index of canonical position ``a`` (-1 past n), ``rank`` its inverse; the canonical
+    molecule is ``nodes[order]``, ``edges[order][:, order]``, zero padded (``want_molecules=True`` returns it as int8
+    ``.nodes`` / ``.edges``); ``key`` is a hash of it (include/graphinvent_amd.h has the algorithm, tests/canon_model.py
+    a numpy version).  ``status``: 0, or ``lib.MOL_VALUE | MOL_BOND_PAST_N | MOL_ASYMMETRIC | MOL_NODE_PAST_N``
+    (``CANON_STATUS_MESSAGES``); such a molecule keeps the identity order, gets a zero form and a key of its own.
+
+    COMPLETENESS: the order comes from colour refinement with individualisation and NO backtracking.  Equal forms
+    always mean isomorphic graphs.  The converse holds when every refinement cell is an orbit of the automorphism
+    group (every molecule of the fixtures; rings, cages such as cubane, adamantane or dodecahedrane); a graph with a
+    cell that is not an orbit (the Frucht graph, the Shrikhande graph, a disconnected C6 + 2 C3) can come out in
+    several forms, so two copies of it in different node orders may count as distinct.  The error is always towards
+    "unique".  Nothing is read back: ``.host()`` does that with one copy and one synchronisation."""
+    what = "canonical"
+    G, N, Fn, Fe, dtype, n_nodes, nn_bytes, _ = _check_inputs(what, nodes, edges, n_nodes, None, False)
+    dev = nodes.device
+    cn = ce = None
+    if want_molecules:
+        cn = torch.empty((G, N, Fn), dtype=torch.int8, device=dev)
+        ce = torch.empty((G, N, N, Fe), dtype=torch.int8, device=dev)
+    res = CanonicalMolecules(torch.empty(CanonicalMolecules.nbytes(G, N), dtype=torch.uint8, device=dev), G, N, cn, ce)
+    if G > 0:
+        with torch.cuda.device(dev):
+            L.check(L.load().gi_mol_canon(
+                G, N, Fn, Fe, nodes.data_ptr(), edges.data_ptr(), dtype,
+                None if n_nodes is None else n_nodes.data_ptr(), nn_bytes, res.order.data_ptr(), res.rank.data_ptr(),
+                res.key.data_ptr(), res.status.data_ptr(), None if cn is None else cn.data_ptr(),
+                None if ce is None else ce.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "gi_mol_canon")
+    return res
+
+
+def _check_mask(what: str, mask, G: int, dev):
+    if mask is None:
+        return None
+    if not isinstance(mask, torch.Tensor) or not mask.is_cuda or mask.device != dev:
+        raise RuntimeError(f"{what}: mask must be a CUDA tensor on {dev} (no CPU fallback)")
+    if tuple(mask.shape) != (G,):
+        raise ValueError(f"{what}: mask has shape {tuple(mask.shape)}, expected ({G},)")
+    return (mask != 0).to(torch.int8)
+
+
+def _unique(what: str, nodes, edges, n_nodes, mask):
+    """-> (canonical molecules, uniqueness, rep, counts) on the device."""
+    G, N = _check_inputs(what, nodes, edges, n_nodes, None, False)[:2]      # everything is checked before a launch
+    dev = nodes.device
+    mask = _check_mask(what, mask, G, dev)
+    can = canonical(nodes, edges, n_nodes, want_molecules=True)
+    lib = L.load()
+    uniq = torch.empty(G, dtype=torch.float32, device=dev)
+    rep = torch.empty(G, dtype=torch.int32, device=dev)
+    counts = torch.empty(L.MOL_COUNTS, dtype=torch.int32, device=dev)
+    ws = torch.empty(max(int(lib.gi_mol_unique_ws_bytes(G)), 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.gi_mol_unique(
+            G, N, nodes.shape[2], edges.shape[3], can.key.data_ptr(), can.nodes.data_ptr(), can.edges.data_ptr(),
+            can.status.data_ptr(), None if mask is None else mask.data_ptr(), ws.data_ptr(), rep.data_ptr(),
+            uniq.data_ptr(), counts.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "gi_mol_unique")
+    return can, uniq, rep, counts
+
+
+def unique(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Optional[torch.Tensor] = None, *,
+           mask: Optional[torch.Tensor] = None):
+    """The reference's ``uniqueness_tensor`` (util.py:549-585) for a batch of generated graphs, without a SMILES
+    string and without a read-back: ``(uniqueness, rep, n_classes)``.
+
+    ``uniqueness`` [G] fp32 is 0 exactly where ``mask[i]`` is set and an earlier masked-in molecule ``j < i`` is the
+    same molecule (``canonical``'s identity, decided by comparing the canonical bytes), 1 elsewhere: it drops into
+    ``Workflow.compute_loss_component`` / ``ScoringFunction.compute_score`` in place of the reference's tensor.
+    ``mask`` [G] (any dtype, non-zero = in; default all) plays the part of the reference's validity: a masked-out
+    molecule keeps 1 and is not remembered.  ``rep`` [G] int32: the lowest index of the molecule's class (-1 where
+    masked out) — ``rep == arange(G)`` picks one representative per distinct graph.  ``n_classes``: a 0-d int32 device
+    tensor, the number of classes among the masked-in molecules.  A malformed molecule (``canonical``'s status) is a
+    class of its own."""
+    _, uniq, rep, counts = _unique("unique", nodes, edges, n_nodes, mask)
+    return uniq, rep, counts[2]
+
+
+def fraction_unique(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Optional[torch.Tensor] = None, *,
+                    mask: Optional[torch.Tensor] = None) -> float:
+    """``Analyzer._get_fraction_unique``'s quotient (Analyzer.py:494-496): distinct molecules among the masked-in
+    (valid) ones divided by ALL G, under ``canonical``'s identity.  One read-back; G = 0 gives 0."""
+    can, _, _, counts = _unique("fraction_unique", nodes, edges, n_nodes, mask)
+    G = can.G
+    if G == 0:
+        return 0.0
+    with _host_sync_allowed():
+        return int(counts[2].item()) / G
+
+
+class SeenSet:
+    """Molecules seen so far, across calls: "unique over a whole generation epoch", or "novel against the training
+    set" (add the training molecules first).  A device table of ``capacity`` (a power of two) 128-bit keys of
+    ``canonical``; the molecules themselves are not kept, so ACROSS CALLS EQUALITY IS BY KEY, not by bytes (inside one
+    call it is by bytes, as in ``unique``): two different molecules with one key, a 2**-128 accident per pair, would
+    count as one.  Keep the table at most half full: a probe is linear."""
+
+    def __init__(self, capacity: int, device="cuda"):
+        capacity = int(capacity)
+        if capacity < 1 or capacity & (capacity - 1):
+            raise ValueError(f"SeenSet: capacity must be a power of two, got {capacity}")
+        self.capacity, self.device = capacity, torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError(f"SeenSet needs a CUDA (ROCm) device, got {self.device}: the MI355X HIP path has no CPU "
+                               "fallback")
+        self._table = torch.zeros((capacity, 2), dtype=torch.int64, device=self.device)
+        self._info = torch.zeros(2, dtype=torch.int32, device=self.device)
+        self._dims = None
+
+    def add(self, nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Optional[torch.Tensor] = None,
+            mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """-> ``new`` [G] int32, no read-back: 1 for the first masked-in occurrence (inside this call) of a molecule
+        whose key was not in the table, which now holds it; 0 for later copies, masked-out molecules and molecules
+        seen in an earlier call.  A malformed masked-in molecule gets 1 and is not stored.  When the table is full,
+        ``overflowed()`` turns true, nothing more is stored and unseen molecules keep reporting 1."""
+        what = "SeenSet.add"
+        dims = _check_inputs(what, nodes, edges, n_nodes, None, False)[1:4]
+        if nodes.device != self._table.device:
+            raise ValueError(f"{what}: the molecules are on {nodes.device}, the table on {self._table.device}")
+        if self._dims not in (None, dims):
+            raise ValueError(f"{what}: (N, Fn, Fe) = {dims}, the table holds keys of {self._dims}")
+        can, _, rep, _ = _unique(what, nodes, edges, n_nodes, mask)
+        self._dims = dims
+        new = torch.empty(can.G, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(L.load().gi_mol_seen_add(
+                can.G, can.key.data_ptr(), can.status.data_ptr(), rep.data_ptr(), self._table.data_ptr(),
+                self.capacity, self._info.data_ptr(), new.data_ptr(),
+                torch.cuda.current_stream(self.device).cuda_stream), "gi_mol_seen_add")
+        return new
+
+    def _read(self):
+        with _host_sync_allowed():
+            return self._info.tolist()
+
+    def count(self) -> int:
+        """Keys in the table (one read-back)."""
+        return int(self._read()[0])
+
+    def overflowed(self) -> bool:
+        """Whether a key ever found the table full (sticky; one read-back)."""
+        return bool(self._read()[1] & L.SEEN_FULL)

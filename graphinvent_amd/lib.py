@@ -153,6 +153,8 @@ LL_ERR_HOT, LL_ERR_MOL, LL_ERR_ORDER = 1, 2, 4          # GI_LL_ERR_*
 
 ANALYZE_MAX_FN, ANALYZE_MAX_HIST, ANALYZE_EDGE_BINS = 512, 1024, 10      # GI_ANALYZE_*
 MOL_ONEHOT, MOL_BOND_PAST_N, MOL_OVERFLOW, MOL_VALUE, MOL_MULTI_BOND = 1, 2, 4, 8, 16   # GI_MOL_*
+MOL_ASYMMETRIC, MOL_NODE_PAST_N = 32, 64                # GI_MOL_* of gi_mol_canon
+MOL_COUNTS, SEEN_FULL = 3, 1                            # GI_MOL_COUNTS, GI_SEEN_FULL
 
 
 class RouteDims(C.Structure):
@@ -277,6 +279,10 @@ SIGNATURES = {
     "gi_mol_loglik_sum": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
     "gi_mol_properties": (ci, [ci, ci, ci, ci, vp, vp, ci, vp, ci, vp, ci, ci, vp, vp, vp]),
     "gi_mol_decode": (ci, [ci, ci, ci, ci, vp, vp, ci, vp, ci, ci, C.POINTER(ci), ci, vp, vp, vp, vp, vp]),
+    "gi_mol_canon": (ci, [ci, ci, ci, ci, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp]),
+    "gi_mol_unique_ws_bytes": (cll, [ci]),
+    "gi_mol_unique": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "gi_mol_seen_add": (ci, [ci, vp, vp, vp, vp, cll, vp, vp, vp]),
 }
 FUSE_GATES_V4, FUSE_DH_SCATTER, FUSE_TIER2_DSELU, FUSE_SLOTS = 1, 2, 4, 8  # GI_FUSE_*
 

@@ -1095,6 +1095,60 @@ int gi_mol_decode(int G, int N, int Fn, int Fe, const void* nodes, const void* e
                   const void* n_nodes, int n_nodes_bytes, int n_seg, const int* seg, int max_bonds,
                   signed char* atoms, short* bonds, int* n_bonds, int* status, void* stream);
 
+/* Molecule identity (gi_canon.hip): which molecules of a batch are the same labelled graph — node feature rows and
+ * bond types, nothing else — which the reference decides on the host from canonical SMILES (util.py:549-585,
+ * Analyzer.py:480-499).  nodes / edges / n_nodes / dtype as for gi_mol_decode; n_nodes = NULL takes the number of
+ * LEADING node rows with a set entry.  The nodes may be in any order; bonds may carry several types and loops.
+ *
+ * gi_mol_canon, one launch: per molecule a canonical node order by colour refinement with individualisation.  With
+ * mix64 the splitmix64 step of gi_route_reorder and all sums modulo 2^64:
+ *   col_i  = #{j < n : row_j < row_i}, feature rows compared as byte strings;
+ *   round:   h_i = sum over (t, j) with edges[i, j, t] set of mix64(t << 32 | col_j),
+ *            col'_i = #{j : (col_j, h_j) < (col_i, h_i)}; rounds repeat until the number of distinct colours stops
+ *            growing;
+ *   while colours repeat: in the non-singleton cell of smallest colour r the member of lowest input index keeps r,
+ *            the others get r + 1; rounds again.  There is NO backtracking: a molecule with a refinement cell that is
+ *            not an automorphism orbit may get different orders from different input orders;
+ *   order [G, N] int32 = the input index of every canonical position (-1 past n), rank [G, N] its inverse;
+ *   out_nodes [G, N, Fn] / out_edges [G, N, N, Fe] int8 (either may be NULL; not the inputs) = nodes[order],
+ *            edges[order][:, order], zero padded;
+ *   key [G, 2] (64-bit words): k0 = mix64(n) + sum mix64(1 << 40 | a Fn + f) + sum mix64(2 << 40 | (a N + b) Fe + t)
+ *            over the set entries (a, f) / (a, b, t) of the canonical molecule, k1 the same with the tags 3, 4, 5 in
+ *            place of none, 1, 2; a word that comes out 0 is stored as 1.
+ * status [G]: GI_MOL_VALUE, GI_MOL_BOND_PAST_N, GI_MOL_ASYMMETRIC (edges[i, j, t] set, edges[j, i, t] not),
+ * GI_MOL_NODE_PAST_N (a node row >= n has a set entry, or n_nodes is outside [0, N]).  A molecule with a non-zero
+ * status gets order = rank = the identity over all N slots, a zero canonical molecule and the key
+ * (mix64(6 << 40 | g), mix64(7 << 40 | g)) of its index g; the two entry points below never find it equal to anything.
+ * At most 2 N + 2 rounds run whatever the data holds.  Fn <= GI_ANALYZE_MAX_FN (GI_ELIMIT).
+ *
+ * gi_mol_unique: first occurrences inside one call.  mask [G] int8 (NULL: all ones) says which molecules take part.
+ * Two molecules are the same if both have status 0, equal keys AND byte-identical canonical molecules.  rep [G] = the
+ * lowest index of the molecule's class, -1 where mask is 0; unique [G] fp32 = 0 where mask is set and rep < the
+ * molecule's index, 1 elsewhere (util.py:549-573: an invalid molecule keeps 1 and is not remembered); counts
+ * [GI_MOL_COUNTS] (zeroed here) = the OR of all G status words, the masked-in molecules, the classes among them.  The
+ * result does not depend on timing.  ws: gi_mol_unique_ws_bytes(G) bytes.
+ *
+ * gi_mol_seen_add: across calls, by the 128-bit KEY ALONE (the molecules are not kept).  table: `capacity` (a power
+ * of two) pairs of 64-bit words, zero = empty, owned and zeroed once by the caller; info [2] int32, zeroed with it:
+ * [0] the number of keys stored, [1] GI_SEEN_FULL once a key found every slot taken by others.  For a molecule with
+ * rep[i] == i and status 0: is_new[i] = 1 and the key is stored if it was not in the table, else 0.  Other molecules
+ * get 0, except that one with rep[i] == i and a non-zero status gets 1 and is not stored.  A probe visits at most
+ * `capacity` slots and waits for nobody; when the table is full the key is not stored (is_new stays 1) and which keys
+ * of that call were stored depends on timing. */
+#define GI_MOL_ASYMMETRIC 32        /* gi_mol_canon: edges[i, j, t] is set and edges[j, i, t] is not */
+#define GI_MOL_NODE_PAST_N 64       /* gi_mol_canon: a node row >= n has a set entry, or n_nodes outside [0, N] */
+#define GI_MOL_COUNTS 3
+#define GI_SEEN_FULL 1
+int gi_mol_canon(int G, int N, int Fn, int Fe, const void* nodes, const void* edges, int dtype,
+                 const void* n_nodes, int n_nodes_bytes, int* order, int* rank, unsigned long long* key,
+                 int* status, signed char* out_nodes, signed char* out_edges, void* stream);
+long long gi_mol_unique_ws_bytes(int G);
+int gi_mol_unique(int G, int N, int Fn, int Fe, const unsigned long long* key, const signed char* canon_nodes,
+                  const signed char* canon_edges, const int* status, const signed char* mask, void* ws, int* rep,
+                  float* unique, int* counts, void* stream);
+int gi_mol_seen_add(int G, const unsigned long long* key, const int* status, const int* rep,
+                    unsigned long long* table, long long capacity, int* info, int* is_new, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

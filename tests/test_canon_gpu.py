@@ -1,0 +1,305 @@
+"""-m gpu: molecule identity on the device (graphinvent_amd.analyze.canonical / unique / fraction_unique / SeenSet:
+gi_mol_canon, gi_mol_unique, gi_mol_seen_add).
+
+Every comparison is exact — order, rank, key, canonical bytes, status, unique, rep, counts — against the numpy
+specification tests/canon_model.py, which tests/test_canon_cpu.py pins to networkx's VF2 classes
+(tests/golden/golden_canon.npz).  The model's results on the stored sets are computed once and shared."""
+import numpy as np
+import pytest
+import torch
+
+from graphinvent_amd import analyze
+from graphinvent_amd import lib as L
+from tests import canon_model as CM
+from tests import rl_callers
+from tests.test_canon_cpu import CONFIGS, fixture_set, golden, mixed_batch, model_of, permuted_copies
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+DTYPES = [torch.float32, torch.int8]
+NP_OF = {torch.float32: np.float32, torch.int8: np.int8}
+
+
+def to_dev(x, dtype=torch.int8, misalign=1):
+    """x on the device as `dtype`, contiguous, its first byte `misalign` elements past an aligned allocation (int8:
+    one byte), so that the 16-byte pieces start and end raggedly."""
+    x = np.ascontiguousarray(x)
+    buf = torch.zeros(x.size + misalign, dtype=dtype, device=DEV)
+    view = buf[misalign:].view(x.shape)
+    view.copy_(torch.from_numpy(x.astype(NP_OF[dtype])))
+    assert view.is_contiguous()
+    return view
+
+
+def assert_same_canon(can, want, what=""):
+    order, rank, key, status = can.host()
+    for name, g in (("status", status), ("order", order), ("rank", rank), ("key", key),
+                    ("nodes", can.nodes.cpu().numpy()), ("edges", can.edges.cpu().numpy())):
+        w = want[name]
+        assert g.dtype == w.dtype and g.shape == w.shape, (what, name, g.dtype, g.shape, w.dtype, w.shape)
+        assert np.array_equal(g, w), (what, name, np.argwhere(g != w)[:5])
+
+
+def run(nodes, edges, n_nodes=None, dtype=torch.int8, misalign=1):
+    return analyze.canonical(to_dev(nodes, dtype, misalign), to_dev(edges, dtype, misalign), n_nodes,
+                             want_molecules=True)
+
+
+# ---- device against model ---------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "int8"])
+@pytest.mark.parametrize("c", CONFIGS + ["sym"])
+def test_device_equals_the_model_on_the_stored_sets(golden_dir, c, dtype):
+    nodes, edges = fixture_set(golden_dir, c)
+    can = run(nodes, edges, dtype=dtype)
+    assert can.order.is_cuda and can.key.dtype == torch.int64 and can.nodes.dtype == torch.int8
+    assert_same_canon(can, model_of(golden_dir, c), (c, dtype))
+    bare = analyze.canonical(to_dev(nodes, dtype, 0), to_dev(edges, dtype, 0))        # aligned, no molecules wanted
+    assert bare.nodes is None and bare.edges is None
+    assert all(np.array_equal(a, b) for a, b in zip(bare.host(), can.host()))
+
+
+@pytest.mark.parametrize("nn", [torch.int8, torch.int32, torch.int64, None], ids=["i8", "i32", "i64", "derived"])
+def test_n_nodes_of_every_width(golden_dir, nn):
+    nodes, edges = fixture_set(golden_dir, "gdb13")
+    n = nodes.any(axis=2).sum(axis=1)
+    can = run(nodes, edges, None if nn is None else torch.from_numpy(n).to(DEV, nn))
+    assert_same_canon(can, model_of(golden_dir, "gdb13"), nn)
+
+
+def test_batch_sizes_1_0_and_257(golden_dir):
+    nodes, edges = fixture_set(golden_dir, "gdb13")
+    pn, pe = permuted_copies(golden_dir, "gdb13", 3)
+    want = model_of(golden_dir, "gdb13")
+    one = run(nodes[7:8], edges[7:8])
+    assert one.host()[0].tolist() == want["order"][7:8].tolist() and np.array_equal(one.host()[2], want["key"][7:8])
+    none = run(nodes[:0], edges[:0])
+    assert [x.shape for x in none.host()] == [(0, 13), (0, 13), (0, 2), (0,)] and none.nodes.shape == (0, 13, 8)
+    big_n, big_e = np.concatenate([nodes, pn[:117]]), np.concatenate([edges, pe[:117]])
+    can = run(big_n, big_e)
+    assert len(can) == 257
+    order, rank, key, status = can.host()
+    assert np.array_equal(key[:140], want["key"]) and np.array_equal(key[140:], want["key"][:117])
+    assert np.array_equal(can.edges.cpu().numpy()[140:], want["edges"][:117]) and not status.any()
+    assert np.array_equal(order[:140], want["order"])
+    uniq, rep, n_classes = analyze.unique(to_dev(big_n), to_dev(big_e))
+    assert rep.cpu().tolist() == list(range(140)) + list(range(117)) and int(n_classes) == 140
+    assert uniq.cpu().tolist() == [1.0] * 140 + [0.0] * 117
+
+
+@pytest.mark.parametrize("c", CONFIGS + ["sym"])
+def test_eight_node_orders_give_one_form(golden_dir, c):
+    base = model_of(golden_dir, c)
+    for k in range(8):
+        pn, pe = permuted_copies(golden_dir, c, k)
+        can = run(pn, pe, misalign=k)
+        assert np.array_equal(can.host()[2], base["key"]), (c, k)
+        assert np.array_equal(can.nodes.cpu().numpy(), base["nodes"]), (c, k)
+        assert np.array_equal(can.edges.cpu().numpy(), base["edges"]), (c, k)
+        assert_same_canon(can, model_of(golden_dir, c, k), (c, k))               # and the orders are the model's
+
+
+def test_known_misses_match_the_model_and_never_merge(golden_dir):
+    nodes, edges = fixture_set(golden_dir, "miss")
+    sn, se = fixture_set(golden_dir, "sym")
+    for k in (None, 0, 5):
+        mn, me = (nodes, edges) if k is None else permuted_copies(golden_dir, "miss", k)
+        assert_same_canon(run(mn, me), model_of(golden_dir, "miss", k), k)
+    # the originals, one stored order of each and the symmetric graphs in one call: a copy may count as distinct (the
+    # documented miss), nothing is merged with a different graph
+    pn, pe = permuted_copies(golden_dir, "miss", 0)
+    _, rep, _ = analyze.unique(to_dev(np.concatenate([nodes, pn, sn])), to_dev(np.concatenate([edges, pe, se])))
+    rep, M = rep.cpu().numpy(), len(nodes)
+    assert all(rep[M + s] in (s, M + s) for s in range(M)) and np.array_equal(rep[2 * M:], np.arange(2 * M, len(rep)))
+    want = CM.unique(CM.canonical(np.concatenate([nodes, pn, sn]), np.concatenate([edges, pe, se])))[1]
+    assert np.array_equal(rep, want)
+
+
+# ---- the edges of the limits ------------------------------------------------------------------------------------
+
+def limit_cases():
+    """name -> (nodes [G, N, Fn], edges, n_nodes or None)."""
+    rng = np.random.default_rng(5)
+    cases = {}
+    # n = 0 and n = 1 (and n = 2), given and derived
+    z = [CM.from_bonds(6, 3, 2, [1] * n, CM.path(n)) for n in (0, 1, 2)]
+    cases["n_0_1"] = (np.stack([a for a, _ in z]), np.stack([b for _, b in z]), None)
+    # N = 64 / 65 / 128: a ring and a path of N nodes (the most rounds), a random tree with ring closures, permuted
+    for N in (64, 65, 128):
+        mols = [CM.from_bonds(N, 2, 2, [0] * N, CM.ring(N)), CM.from_bonds(N, 2, 2, [0] * N, CM.path(N, 1)),
+                CM.from_bonds(N, 2, 2, rng.integers(0, 2, N).tolist(),
+                              [(i, int(rng.integers(0, i)), int(rng.integers(0, 2))) for i in range(1, N)])]
+        mols += [CM.permute(a, b, rng.permutation(N)) for a, b in mols]
+        cases[f"N_{N}"] = (np.stack([a for a, _ in mols]), np.stack([b for _, b in mols]), None)
+    # Fe = 8: every bond type in use, two types on one pair, a loop
+    bonds = [(i, i + 1, i % 8) for i in range(11)] + [(0, 5, 7), (0, 1, 3), (4, 4, 2)]
+    a, b = CM.from_bonds(12, 5, 8, (np.arange(12) % 5).tolist(), bonds)
+    p = rng.permutation(12)
+    cases["Fe_8"] = (np.stack([a, CM.permute(a, b, p)[0]]), np.stack([b, CM.permute(a, b, p)[1]]), None)
+    # K13: the most individualisations; with n_nodes given and zero rows below n (13 unlabelled nodes)
+    a, b = CM.from_bonds(13, 4, 3, [2] * 13, CM.complete(13, 1))
+    cases["K13"] = (np.stack([a, np.zeros_like(a)]), np.stack([b, b]), np.array([13, 13], np.int8))
+    # Fn = 70: three words of feature bits per node
+    a, b = CM.from_bonds(9, 70, 1, [69, 31, 32, 0, 64, 63, 33, 1, 69], CM.ring(9))
+    cases["Fn_70"] = (np.stack([a, CM.permute(a, b, p[p < 9])[0]]), np.stack([b, CM.permute(a, b, p[p < 9])[1]]), None)
+    return cases
+
+
+LIMITS = limit_cases()
+_MODEL = {}                                                                # the model's results, computed once
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "int8"])
+@pytest.mark.parametrize("name", list(LIMITS))
+def test_limits_of_the_dims(name, dtype):
+    nodes, edges, n = LIMITS[name]
+    key = ("limit", name)
+    if key not in _MODEL:
+        _MODEL[key] = CM.canonical(nodes, edges, n)
+    want = _MODEL[key]
+    can = run(nodes, edges, None if n is None else torch.from_numpy(n).to(DEV), dtype=dtype)
+    assert_same_canon(can, want, (name, dtype))
+    assert not want["status"].any()
+    if name.startswith("N_") or name in ("Fe_8", "Fn_70"):                 # the permuted copies: the same forms
+        h = len(nodes) // 2
+        assert np.array_equal(want["key"][:h], want["key"][h:]) and np.array_equal(want["edges"][:h], want["edges"][h:])
+
+
+def test_model_rounds_stay_inside_the_bound():
+    """The bound the kernel's loop relies on: at most 2 n rounds, at most n - 1 individualisations."""
+    for name in ("N_128", "K13"):
+        nodes, edges, n = LIMITS[name]
+        for g in range(len(nodes)):
+            stats = {}
+            k = CM.derived_n(nodes[g]) if n is None else int(n[g])
+            CM.canonical_order(nodes[g], edges[g], k, stats)
+            assert stats["rounds"] <= 2 * k and stats["individualisations"] <= k - 1, (name, g, stats)
+            if name == "K13":
+                assert stats["individualisations"] == 12
+
+
+# ---- unique -----------------------------------------------------------------------------------------------------
+
+def test_unique_planted_duplicates_and_the_mask(golden_dir):
+    G, _ = golden(golden_dir)
+    nodes, edges, mask = mixed_batch(golden_dir)
+    dn, de = to_dev(nodes), to_dev(edges)
+    for m in (torch.from_numpy(mask).to(DEV), torch.from_numpy(mask).to(DEV).float(), torch.from_numpy(mask != 0).to(DEV)):
+        prev = torch.cuda.get_sync_debug_mode()
+        torch.cuda.set_sync_debug_mode("error")                            # no read-back, no synchronisation
+        try:
+            uniq, rep, n_classes = analyze.unique(dn, de, mask=m)
+        finally:
+            torch.cuda.set_sync_debug_mode(prev)
+        assert uniq.dtype == torch.float32 and rep.dtype == torch.int32 and n_classes.is_cuda and n_classes.dim() == 0
+        assert np.array_equal(uniq.cpu().numpy(), G["mix::unique"]) and np.array_equal(rep.cpu().numpy(), G["mix::rep"])
+        assert int(n_classes) == int((G["mix::rep"] == np.arange(len(mask))).sum())
+    # masked-out molecules keep 1 and do not shadow: with molecule 0 masked out, its copy 1 is the first
+    m2 = mask.copy()
+    m2[0] = 0
+    want = CM.unique(CM.canonical(nodes, edges), m2)
+    uniq, rep, n_classes = analyze.unique(dn, de, mask=torch.from_numpy(m2).to(DEV))
+    assert np.array_equal(uniq.cpu().numpy(), want[0]) and np.array_equal(rep.cpu().numpy(), want[1])
+    assert uniq[0] == 1 and rep[0] == -1 and uniq[1] == 1 and rep[1] == 1 and rep[-1] == 1 and uniq[-1] == 0
+    # no mask: all ones; the fraction is classes / G
+    want = CM.unique(CM.canonical(nodes, edges))
+    uniq, rep, n_classes = analyze.unique(dn, de)
+    assert np.array_equal(uniq.cpu().numpy(), want[0]) and int(n_classes) == want[2][2]
+    assert analyze.fraction_unique(dn, de) == want[2][2] / len(mask)
+    assert analyze.fraction_unique(dn, de, mask=torch.from_numpy(mask).to(DEV)) == \
+        int((G["mix::rep"] == np.arange(len(mask))).sum()) / len(mask)
+    assert analyze.fraction_unique(dn[:0], de[:0]) == 0.0
+
+
+def test_unique_all_equal_and_all_distinct(golden_dir):
+    nodes, edges = fixture_set(golden_dir, "chiral6")
+    perm = golden(golden_dir)[0]["chiral6::perm"]
+    copies = [(nodes[3], edges[3])] + [CM.permute(nodes[3], edges[3], p[p >= 0]) for p in perm[3]] * 4
+    uniq, rep, n_classes = analyze.unique(to_dev(np.stack([a for a, _ in copies])),
+                                          to_dev(np.stack([b for _, b in copies])))
+    assert uniq.cpu().tolist() == [1.0] + [0.0] * 32 and not rep.any() and int(n_classes) == 1
+    uniq, rep, n_classes = analyze.unique(to_dev(nodes, torch.float32), to_dev(edges, torch.float32))
+    assert uniq.cpu().tolist() == [1.0] * 12 and rep.cpu().tolist() == list(range(12)) and int(n_classes) == 12
+
+
+def test_unique_feeds_the_rl_loss(golden_dir):
+    nodes, edges, mask = mixed_batch(golden_dir)
+    uniq, _, _ = analyze.unique(to_dev(nodes), to_dev(edges), mask=torch.from_numpy(mask).to(DEV))
+    model = torch.from_numpy(CM.unique(CM.canonical(nodes, edges), mask)[0]).to(DEV)
+    g = torch.Generator().manual_seed(3)
+    scores, agent, prior = (torch.rand(len(mask), generator=g).to(DEV) for _ in range(3))
+    got = rl_callers.compute_loss_component(scores, -agent, -prior, uniq, 20.0)
+    want = rl_callers.compute_loss_component(scores, -agent, -prior, model, 20.0)
+    assert torch.equal(got, want) and 0 < int((got == 0).sum()) < len(mask)
+
+
+# ---- SeenSet ----------------------------------------------------------------------------------------------------
+
+def test_seen_set_across_calls(golden_dir):
+    nodes, edges = fixture_set(golden_dir, "gdb13")
+    pn, pe = permuted_copies(golden_dir, "gdb13", 2)
+    seen = analyze.SeenSet(1024, DEV)
+    first = seen.add(to_dev(nodes[:80]), to_dev(edges[:80]))
+    assert first.dtype == torch.int32 and first.cpu().tolist() == [1] * 80 and seen.count() == 80
+    second = seen.add(to_dev(pn[60:140]), to_dev(pe[60:140]))              # 60..79 overlap, in another node order
+    assert second.cpu().tolist() == [0] * 20 + [1] * 60 and seen.count() == 140 and not seen.overflowed()
+    # training set first, then a generated batch: planted duplicates, a mask, a malformed molecule
+    train = analyze.SeenSet(256, DEV)
+    train.add(to_dev(nodes[:60]), to_dev(edges[:60]))
+    mn, me, mask = mixed_batch(golden_dir)                                 # molecules 0, 5, .., 115 of the fixture
+    mn, me, mask = mn.copy(), me.copy(), mask.copy()
+    mn[2, 0, 0] = 2
+    mask[2] = 1
+    src = golden(golden_dir)[0]["mix::src"]
+    can = CM.canonical(mn, me)
+    model = CM.SeenSet(256)
+    model.add(CM.canonical(nodes[:60], edges[:60]), np.arange(60))
+    want = model.add(can, CM.unique(can, mask)[1])
+    new = train.add(to_dev(mn), to_dev(me), mask=torch.from_numpy(mask).to(DEV))
+    assert np.array_equal(new.cpu().numpy(), want) and train.count() == model.count()
+    assert new[2] == 1 and all(new[b] == 0 for b in range(len(src)) if src[b] < 60 and b != 2)
+    assert 0 < int(new.sum()) < len(src)
+    with pytest.raises(ValueError, match="holds keys of"):
+        train.add(*(to_dev(x) for x in fixture_set(golden_dir, "arom5")))
+
+
+def test_seen_set_overfilled_does_not_hang(golden_dir):
+    nodes, edges = fixture_set(golden_dir, "gdb13")
+    seen = analyze.SeenSet(8, DEV)
+    assert seen.add(to_dev(nodes[:6]), to_dev(edges[:6])).cpu().tolist() == [1] * 6 and not seen.overflowed()
+    new = seen.add(to_dev(nodes[4:24]), to_dev(edges[4:24]))               # 2 known, 18 new, room for 2
+    assert new.cpu().tolist() == [0, 0] + [1] * 18
+    assert seen.overflowed() and seen.count() == 8                          # the sticky bit; the table is full
+    again = seen.add(to_dev(nodes[:6]), to_dev(edges[:6]))                 # the earlier entries are intact
+    assert again.cpu().tolist() == [0] * 6 and seen.overflowed() and seen.count() == 8
+    assert int(seen.add(to_dev(nodes[100:110]), to_dev(edges[100:110])).sum()) == 10   # unseen: still reported new
+
+
+# ---- malformed molecules ----------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "int8"])
+def test_malformed_molecules_stand_alone(golden_dir, dtype):
+    nodes, edges = fixture_set(golden_dir, "gdb13")
+    nodes, edges = np.repeat(nodes[10:11], 8, 0), np.repeat(edges[10:11], 8, 0)      # eight copies of one molecule
+    n = int(nodes[0].any(axis=1).sum())
+    nodes[1, 0, np.flatnonzero(nodes[1, 0])[0]] = 2                                  # a value 2
+    nodes[2, 0, np.flatnonzero(nodes[2, 0])[0]] = 2                                  # the same defect twice
+    edges[4, 0, 12, 1] = edges[4, 12, 0, 1] = 1                                      # a bond past n
+    edges[5, 1, 2, 2] = 1 - edges[5, 2, 1, 2]                                        # one direction only
+    nn = np.full(8, n, np.int8)
+    nn[6] = n - 1                                                                    # the last node is past n
+    want = CM.canonical(nodes, edges, nn)
+    assert want["status"].tolist() == [0, 8, 8, 0, 2, 32, 64 | 2, 0] and n < 12
+    can = run(nodes, edges, torch.from_numpy(nn).to(DEV), dtype=dtype)
+    assert_same_canon(can, want, dtype)
+    dn, de, dk = to_dev(nodes, dtype), to_dev(edges, dtype), torch.from_numpy(nn).to(DEV)
+    uniq, rep, n_classes = analyze.unique(dn, de, dk)
+    assert rep.cpu().tolist() == [0, 1, 2, 0, 4, 5, 6, 0] and int(n_classes) == 6    # neighbours unaffected
+    assert uniq.cpu().tolist() == [1, 1, 1, 0, 1, 1, 1, 0]
+    w = CM.unique(want)
+    assert np.array_equal(uniq.cpu().numpy(), w[0]) and np.array_equal(rep.cpu().numpy(), w[1])
+    if dtype == torch.float32:                                                       # a fraction, a NaN, a -0.0
+        x = dn.clone()
+        x[0, 0, 0], x[3, 1, 1], x[7, 2, 2] = 0.5, float("nan"), -0.0
+        status = analyze.canonical(x, de, dk).host()[3]
+        assert status.tolist() == [8, 8, 8, 8, 2, 32, 64 | 2, 0]
