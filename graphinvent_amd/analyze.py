@@ -8,8 +8,13 @@ graph and ``.item()`` on every bond index, i.e. one device-to-host synchronisati
 ``molecular_properties(nodes, edges, n_nodes, groups, ...)`` is one launch (``gi_mol_properties``) over the generator's
 own tensors and returns the dictionary entries of ``get_molecular_properties`` that need no RDKit, as fp32 tensors on
 the device with the reference's shapes and values.  ``fraction_valid`` and ``fraction_valid_properly_terminated`` are
-NOT produced: they come from RDKit's sanitisation, and the caller merges them into the dictionary, as it does
-``fraction_unique`` (from ``fraction_unique`` below, with RDKit's validity as the mask).
+NOT produced by that call: the caller merges them into the dictionary from ``fraction_valid`` below (or from RDKit's
+sanitisation), as it does ``fraction_unique`` (from ``fraction_unique`` below, with the validity as the mask).
+
+``ValenceRules`` / ``validity`` / ``fraction_valid`` decide which molecules are VALID, on the device
+(``gi_mol_valence``): the reference's ``validity_tensor`` (util.py:549-585, one ``SanitizeMol`` per molecule) as a
+valence test of the labelled graph — a table look-up per atom, NOT RDKit's sanitisation, no kekulisation — together
+with the hydrogen fill, mass, component and ring counts of every molecule, see ``validity``.
 
 ``canonical`` / ``unique`` / ``fraction_unique`` / ``SeenSet`` decide which molecules are the SAME molecule, on the
 device (``gi_mol_canon``, ``gi_mol_unique``, ``gi_mol_seen_add``): the reference's ``uniqueness_tensor``
@@ -126,7 +131,8 @@ def molecular_properties(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Opti
     rows, ``edge_feature_hist`` halves the whole plane's sum.  Nothing is read back and nothing synchronises.
 
     NOT produced: ``fraction_unique``, ``fraction_valid``, ``fraction_valid_properly_terminated``.  They come from
-    RDKit; merge them into the dictionary in the caller.  Values are the reference's bit for bit while every count
+    ``fraction_unique`` and ``fraction_valid`` of this module (or from RDKit); merge them into the dictionary in the
+    caller.  Values are the reference's bit for bit while every count
     is below 2**24 (see the module docstring for what happens beyond).  G = 0 returns zeros without a launch (the
     reference raises)."""
     what = "molecular_properties"
@@ -521,3 +527,286 @@ class SeenSet:
     def overflowed(self) -> bool:
         """Whether a key ever found the table full (sticky; one read-back)."""
         return bool(self._read()[1] & L.SEEN_FULL)
+
+
+# ---- molecule validity -------------------------------------------------------------------------------------------
+#: (period, group) of the elements the default table knows; hydrogen is handled apart
+_ELEMENTS = {"B": (2, 13), "C": (2, 14), "N": (2, 15), "O": (2, 16), "F": (2, 17), "Si": (3, 14), "P": (3, 15),
+             "S": (3, 16), "Cl": (3, 17), "Se": (4, 16), "Br": (4, 17), "I": (5, 17)}
+#: allowed total valences of a NEUTRAL atom by group: the first row (period 2), and the rows below it
+_GROUP_VALENCES = {2: {13: (3,), 14: (4,), 15: (3,), 16: (2,), 17: (1,), 18: (0,)},
+                   3: {13: (3,), 14: (4,), 15: (3, 5), 16: (2, 4, 6), 17: (1,), 18: (0,)}}
+#: standard atomic weights in millidalton
+DEFAULT_MASSES = {"H": 1008, "B": 10810, "C": 12011, "N": 14007, "O": 15999, "F": 18998, "Si": 28085, "P": 30974,
+                  "S": 32060, "Cl": 35450, "Se": 78971, "Br": 79904, "I": 126904}
+_BOND_ORDER2 = {1: 2, 1.5: 3, 2: 4, 3: 6}
+
+#: status bits of ``validity`` that make a molecule invalid, and the informational ones
+VALIDITY_STATUS_MESSAGES = {
+    L.MOL_ONEHOT: "a node row below n_nodes does not have exactly one set entry in the atom type, formal charge or "
+                  "implicit-H segment",
+    L.MOL_BOND_PAST_N: STATUS_MESSAGES[L.MOL_BOND_PAST_N],
+    L.MOL_VALUE: STATUS_MESSAGES[L.MOL_VALUE],
+    L.MOL_MULTI_BOND: STATUS_MESSAGES[L.MOL_MULTI_BOND],
+    L.MOL_ASYMMETRIC: CANON_STATUS_MESSAGES[L.MOL_ASYMMETRIC],
+    L.MOL_NODE_PAST_N: CANON_STATUS_MESSAGES[L.MOL_NODE_PAST_N],
+    L.VAL_EMPTY: "the molecule has no atoms (the reference's mol = None)",
+    L.VAL_SELF_LOOP: "an atom is bonded to itself (RDKit's AddBond refuses it)",
+    L.VAL_OVER: "an atom has more bonds than any allowed valence of its element and charge",
+    L.VAL_FRAGMENTS: "more than one connected component (invalid only with require_connected)",
+    L.VAL_AROMATIC: "a bond of order 1.5 is present: counted 3 per 2, NOT kekulised (informational)",
+    L.VAL_H_MISMATCH: "a stored implicit-H count differs from the hydrogen fill (informational)",
+}
+MALFORMED_BITS = (L.MOL_ONEHOT | L.MOL_BOND_PAST_N | L.MOL_VALUE | L.MOL_MULTI_BOND | L.MOL_ASYMMETRIC |
+                  L.MOL_NODE_PAST_N)
+INVALID_BITS = MALFORMED_BITS | L.VAL_EMPTY | L.VAL_SELF_LOOP | L.VAL_OVER
+
+
+def default_valences(symbol: str, charge: int):
+    """The default table's allowed total valences of ``symbol`` with formal charge ``charge``, or ``None`` where the
+    table has no entry.  OURS, NOT CHECKED AGAINST RDKit.  Neutral atoms: H 1; B 3; C, Si 4; N 3; P 3, 5; O 2; S, Se
+    2, 4, 6; F, Cl, Br, I 1; a noble gas 0.  An atom of group g with charge c in {-1, 0, +1} takes the list of group
+    g - c of its own period (period 2 the first-row lists, lower periods those of P / S): N+ 4, O+ 3, N- 2, O- 1,
+    C- 3, C+ 3, B- 4, S+ 3 / 5, Cl- 0, Cl+ 2 / 4 / 6.  H+ and H- are 0."""
+    if charge not in (-1, 0, 1):
+        return None
+    if symbol == "H":
+        return (1,) if charge == 0 else (0,)
+    if symbol not in _ELEMENTS:
+        return None
+    period, group = _ELEMENTS[symbol]
+    return _GROUP_VALENCES[2 if period == 2 else 3].get(group - charge)
+
+
+class ValenceRules:
+    """The tables ``validity`` judges by, built once and kept on the device.
+
+    ``atom_types`` (symbols), ``formal_charge`` (integers) and ``imp_H`` (hydrogen counts; ``None``: no implicit-H
+    segment) are the constants' lists in the node row's segment order; whatever follows them in a node row (a
+    chirality segment) is ignored.  ``bond_orders``: the order of every bond type, from {1, 1.5, 2, 3}; without it
+    edges of three bond types are read as ``(1, 2, 3)`` and of four as ``(1, 2, 3, 1.5)`` (the reference's
+    ``bondtype_to_int`` order), and any other number of bond types raises ``ValueError`` in ``validity``.  ``allowed``
+    ``{(symbol, charge): (valences, ...)}`` overrides or extends the default table (``default_valences``, which is
+    ours and NOT CHECKED AGAINST RDKit) per entry; a combination of ``atom_types`` x ``formal_charge`` that neither
+    has raises ``ValueError``.  ``masses`` ``{symbol: millidalton}`` overrides ``DEFAULT_MASSES``.
+
+    Device tables: ``allowed_mask`` [A * C] int16 (bit v = total valence v allowed, 0..15), ``mass`` [A] int32
+    (millidalton), ``order2(Fe)`` [Fe] int8 (twice the bond order), ``h_values`` [H] int8; their host copies are
+    ``mask_table`` [A, C] uint16, ``mass_table`` and ``order2_tables``, and ``valences`` maps (symbol, charge) to the
+    tuple.  ``device=None`` builds the host copies only (for inspection; ``validity`` refuses such rules)."""
+
+    def __init__(self, atom_types: Sequence[str], formal_charge: Sequence[int], *, imp_H: Optional[Sequence[int]] = None,
+                 bond_orders: Optional[Sequence[float]] = None, allowed: Optional[dict] = None,
+                 masses: Optional[dict] = None, device="cuda"):
+        self.atom_types, self.formal_charge = [str(a) for a in atom_types], [int(c) for c in formal_charge]
+        self.imp_H = None if imp_H is None else [int(h) for h in imp_H]
+        if not self.atom_types or not self.formal_charge or (self.imp_H is not None and not self.imp_H):
+            raise ValueError("ValenceRules: atom_types, formal_charge and (if given) imp_H must not be empty")
+        if self.imp_H is not None and not all(0 <= h <= 127 for h in self.imp_H):
+            raise ValueError(f"ValenceRules: imp_H {self.imp_H} must hold hydrogen counts in [0, 127]")
+        if bond_orders is not None:
+            if not 1 <= len(bond_orders) <= L.GI_MAX_GROUPS:
+                raise ValueError(f"ValenceRules: 1 to {L.GI_MAX_GROUPS} bond types, got {len(bond_orders)}")
+            for b in bond_orders:
+                if b not in _BOND_ORDER2:
+                    raise ValueError(f"ValenceRules: bond order {b!r} is not one of 1, 1.5, 2, 3")
+        self.bond_orders = None if bond_orders is None else tuple(bond_orders)
+        allowed = dict(allowed or {})
+        for key, vals in allowed.items():
+            if (not isinstance(key, tuple) or len(key) != 2 or not all(isinstance(v, (int, np.integer)) and 0 <= v <= 15
+                                                                       for v in vals)):
+                raise ValueError(f"ValenceRules: allowed[{key!r}] = {vals!r} must map (symbol, charge) to valences in "
+                                 "[0, 15]")
+        mass_of = dict(DEFAULT_MASSES)
+        mass_of.update({str(k): int(v) for k, v in (masses or {}).items()})
+        self.valences = {}
+        masks = []
+        for a in self.atom_types:
+            if a not in mass_of:
+                raise ValueError(f"ValenceRules: no mass for element {a!r}; give masses={{{a!r}: millidalton}}")
+            for c in self.formal_charge:
+                vals = allowed[(a, c)] if (a, c) in allowed else default_valences(a, c)
+                if vals is None:
+                    raise ValueError(f"ValenceRules: no allowed valences for element {a!r} with formal charge {c:+d}; "
+                                     f"give allowed={{({a!r}, {c}): (valences, ...)}}")
+                self.valences[(a, c)] = tuple(sorted(int(v) for v in vals))
+                masks.append(sum(1 << v for v in set(self.valences[(a, c)])))
+        if "H" not in mass_of:
+            raise ValueError("ValenceRules: masses must keep an entry for 'H'")
+        self.masses = {a: mass_of[a] for a in self.atom_types}
+        self.mass_h = mass_of["H"]
+        self.h_type = self.atom_types.index("H") if "H" in self.atom_types else -1
+        self.groups = (len(self.atom_types), len(self.formal_charge), len(self.imp_H or ()))
+        self.mask_table = np.array(masks, np.uint16).reshape(self.groups[0], self.groups[1])
+        self.mass_table = np.array([self.masses[a] for a in self.atom_types], np.int32)
+        sets = [(1, 2, 3), (1, 2, 3, 1.5)] if self.bond_orders is None else [self.bond_orders]
+        self.order2_tables = {len(bo): np.array([_BOND_ORDER2[b] for b in bo], np.int8) for bo in sets}
+        self.device = None if device is None else torch.device(device)
+        self.allowed_mask = self.mass = self.h_values = None
+        self._order2, self._scratch = {}, {}
+        if self.device is None:
+            return
+        if self.device.type != "cuda":
+            raise RuntimeError(f"ValenceRules needs a CUDA (ROCm) device, got {self.device}: the MI355X HIP path has no "
+                               "CPU fallback (device=None keeps the tables on the host, for inspection only)")
+        self.allowed_mask = torch.from_numpy(self.mask_table.view(np.int16).reshape(-1)).to(self.device)
+        self.mass = torch.from_numpy(self.mass_table).to(self.device)
+        self._order2 = {k: torch.from_numpy(v).to(self.device) for k, v in self.order2_tables.items()}
+        if self.imp_H is not None:
+            self.h_values = torch.tensor(self.imp_H, dtype=torch.int8, device=self.device)
+
+    def scratch(self, stream: int) -> torch.Tensor:
+        """The counters' scratch words of ``gi_mol_valence`` for calls issued on ``stream`` (zero between calls)."""
+        if stream not in self._scratch:
+            self._scratch[stream] = torch.zeros(L.VAL_SCRATCH, dtype=torch.int32, device=self.device)
+        return self._scratch[stream]
+
+    def order2(self, Fe: int) -> torch.Tensor:
+        """Twice the bond order of each of ``Fe`` bond types, int8, on the device."""
+        if Fe not in self.order2_tables:
+            if self.bond_orders is None:
+                raise ValueError(f"ValenceRules: bond_orders is required for {Fe} bond types (the defaults cover three: "
+                                 "1, 2, 3 and four: 1, 2, 3, 1.5)")
+            raise ValueError(f"ValenceRules: the rules hold {len(self.bond_orders)} bond orders, edges has Fe = {Fe}")
+        return self._order2[Fe]
+
+
+class MoleculeValidity:
+    """What ``validity`` wrote, on the device: ``valid`` [G] fp32, ``status`` / ``first_bad`` [G] int32,
+    ``atom_valence`` / ``atom_h`` [G, N] int8, ``desc`` [G, 6] int32 (``DESC_NAMES``) and ``counts`` [4] int32 (valid,
+    terminated, valid and terminated, G) — views of one byte buffer (made when first asked for) so that ``host()`` needs
+    one copy."""
+
+    DESC_NAMES = ("n_atoms", "n_h", "mass_mda", "n_bonds", "n_components", "n_rings")
+    _NAMES = ("valid", "status", "first_bad", "atom_valence", "atom_h", "desc", "counts")
+
+    def __init__(self, buf: torch.Tensor, G: int, N: int):
+        self._buf, self._host, self._pinned = buf, None, None
+        self.G, self.N = G, N
+
+    @staticmethod
+    def nbytes(G: int, N: int) -> int:
+        return 16 + 36 * G + 2 * G * N       # counts | status | first_bad | valid | desc | atom_valence | atom_h
+
+    @staticmethod
+    def layout(G: int, N: int) -> dict:
+        """name -> (byte offset, bytes, dtype name, shape) inside the buffer; every array is aligned to itself."""
+        return {"counts": (0, 16, "int32", (L.VAL_COUNTS,)), "status": (16, 4 * G, "int32", (G,)),
+                "first_bad": (16 + 4 * G, 4 * G, "int32", (G,)), "valid": (16 + 8 * G, 4 * G, "float32", (G,)),
+                "desc": (16 + 12 * G, 24 * G, "int32", (G, L.VAL_DESC)),
+                "atom_valence": (16 + 36 * G, G * N, "int8", (G, N)),
+                "atom_h": (16 + 36 * G + G * N, G * N, "int8", (G, N))}
+
+    def _view(self, name, buf, xp):
+        off, size, dtype, shape = self.layout(self.G, self.N)[name]
+        return buf[off:off + size].view(getattr(xp, dtype)).reshape(shape)
+
+    def __getattr__(self, name):
+        # the device views are made when first asked for: a caller that wants `valid` does not pay for seven
+        if name in MoleculeValidity._NAMES:
+            view = self._view(name, self._buf, torch)
+            self.__dict__[name] = view
+            return view
+        raise AttributeError(name)
+
+    def host(self) -> dict:
+        """-> ``{name: numpy array}`` of all seven outputs: ONE asynchronous copy into pinned memory and ONE
+        synchronisation (of the current stream), done once and kept."""
+        if self._host is None:
+            dev = self._buf.device
+            with _host_sync_allowed():
+                pinned = torch.empty(self._buf.numel(), dtype=torch.uint8, pin_memory=True)
+                stream = torch.cuda.current_stream(dev)
+                with torch.cuda.device(dev):
+                    pinned.copy_(self._buf, non_blocking=True)
+                stream.synchronize()
+            self._pinned = pinned
+            host = pinned.numpy()
+            self._host = {name: self._view(name, host, np) for name in self._NAMES}
+        return self._host
+
+    def __len__(self):
+        return self.G
+
+
+def validity(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Optional[torch.Tensor], rules: ValenceRules, *,
+             termination: Optional[torch.Tensor] = None, require_connected: bool = False) -> MoleculeValidity:
+    """The reference's ``validity_tensor`` (util.py:549-585; ``fraction_valid``, Analyzer.py:501-544) for all G
+    molecules in one launch (``gi_mol_valence``), with no RDKit and no read-back; inputs as ``canonical``
+    (``n_nodes = None``: the leading node rows with a set entry), the node row's segments from ``rules``.
+
+    **THIS IS A VALENCE TEST OF THE LABELLED GRAPH, NOT RDKit's SANITISATION.**  What ``SanitizeMol`` can reject for
+    the default bond set (single / double / triple) is an atom with more bonds than its element and charge allow;
+    that, a table look-up per atom, is what is judged here, by ``rules``' table, which is ours.  **No kekulisation or
+    aromaticity perception is done**: a bond of order 1.5 counts 3 per 2 and raises ``VAL_AROMATIC``, so that the
+    caller can route such molecules to RDKit.
+
+    Per atom i < n, in integers: ``o2 = sum_t order2[t] * #{j : edges[i, j, t]}``, ``x = ceil(o2 / 2)``, ``v*`` the
+    smallest allowed valence >= x; without one the atom is over its valence, otherwise its hydrogen fill is
+    ``h = v* - x``.  An implicit-H segment does not enter the verdict (the reference stores it only as the
+    ``_TotalNumHs`` property, which sanitisation does not read); it is compared with the fill (``VAL_H_MISMATCH``).
+
+    Result (``MoleculeValidity``, views of one device buffer; ``.host()`` is one copy and one synchronisation):
+    ``valid`` [G] fp32, 1 / 0, drops into ``ScoringFunction.compute_score`` and ``unique(..., mask=valid)``;
+    ``status`` [G] int32 (``VALIDITY_STATUS_MESSAGES``: the ``lib.MOL_*`` bits of a malformed molecule, ``VAL_EMPTY``,
+    ``VAL_SELF_LOOP``, ``VAL_OVER`` — all invalidating — and ``VAL_FRAGMENTS`` (invalidating only with
+    ``require_connected``: sanitisation accepts fragments), ``VAL_AROMATIC``, ``VAL_H_MISMATCH``); ``first_bad`` [G]
+    the lowest atom over its valence (-1: none); ``atom_valence`` [G, N] int8 = min(x, 127) and ``atom_h`` [G, N] int8
+    = the fill (0 for an atom over its valence), both -1 past n and throughout a malformed molecule, for which nothing
+    beyond the malformed bits, ``VAL_EMPTY`` and ``VAL_SELF_LOOP`` is evaluated and ``desc`` is zero; ``desc`` [G, 6]
+    int32 = n_atoms, n_h (fills + atoms of type "H"), mass_mda (``sum mass[type] + fills * mass_H``), n_bonds (pairs
+    i < j with a bond), n_components, n_rings (= n_bonds - n_atoms + n_components); ``counts`` [4] int32 = valid,
+    terminated (``termination`` [G] non-zero; none given: 0), valid and terminated, G."""
+    what = "validity"
+    if not isinstance(rules, ValenceRules):
+        raise TypeError(f"{what}: rules must be a ValenceRules, got {type(rules).__name__}")
+    G, N, Fn, Fe, dtype, n_nodes, nn_bytes, _ = _check_inputs(what, nodes, edges, n_nodes, None, False)
+    dev = nodes.device
+    A, Cn, H = rules.groups
+    if A + Cn + H > Fn:
+        raise ValueError(f"{what}: the rules' segments {rules.groups} do not fit node rows of Fn = {Fn}")
+    order2 = rules.order2(Fe)
+    if rules.device is None:
+        raise RuntimeError(f"{what}: the rules were built with device=None and hold no device tables (no CPU fallback)")
+    if rules.allowed_mask.device != dev:
+        raise ValueError(f"{what}: the molecules are on {dev}, the rules' tables on {rules.allowed_mask.device}")
+    term_dtype = L.DTYPE_I8
+    if termination is not None:
+        if not isinstance(termination, torch.Tensor) or not termination.is_cuda or termination.device != dev:
+            raise RuntimeError(f"{what}: termination must be a CUDA tensor on {dev} (no CPU fallback)")
+        if tuple(termination.shape) != (G,):
+            raise ValueError(f"{what}: termination has shape {tuple(termination.shape)}, expected ({G},)")
+        if termination.dtype != torch.int8:
+            termination = termination.float()
+            term_dtype = L.DTYPE_F32
+        termination = termination.contiguous()
+    if G == 0:                                               # no launch: the counts are zero
+        return MoleculeValidity(torch.zeros(MoleculeValidity.nbytes(0, N), dtype=torch.uint8, device=dev), 0, N)
+    res = MoleculeValidity(torch.empty(MoleculeValidity.nbytes(G, N), dtype=torch.uint8, device=dev), G, N)
+    base = res._buf.data_ptr()
+    out = {name: base + off for name, (off, _, _, _) in MoleculeValidity.layout(G, N).items()}
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        L.check(L.load().gi_mol_valence(
+            G, N, Fn, Fe, nodes.data_ptr(), edges.data_ptr(), dtype,
+            None if n_nodes is None else n_nodes.data_ptr(), nn_bytes, A, Cn, H, rules.allowed_mask.data_ptr(),
+            rules.mass.data_ptr(), order2.data_ptr(), None if rules.h_values is None else rules.h_values.data_ptr(),
+            rules.h_type, rules.mass_h, None if termination is None else termination.data_ptr(), term_dtype,
+            int(bool(require_connected)), out["valid"], out["status"], out["first_bad"], out["atom_valence"],
+            out["atom_h"], out["desc"], out["counts"], rules.scratch(stream).data_ptr(), stream), "gi_mol_valence")
+    return res
+
+
+def fraction_valid(nodes, edges=None, n_nodes=None, rules=None, *, termination=None, require_connected=False):
+    """``Analyzer._get_fraction_valid``'s three quotients (Analyzer.py:532-541) from ``validity``'s ``counts``:
+    ``(fraction_valid, fraction_valid_properly_terminated, fraction_properly_terminated)`` as 0-d fp32 device tensors,
+    with no read-back.  Takes ``validity``'s arguments, or its result as the only argument.  The reference's quirk is
+    kept: ``fraction_valid_properly_terminated`` is 0.0 when nothing is terminated.  G = 0 gives zeros (the reference
+    raises)."""
+    res = nodes if isinstance(nodes, MoleculeValidity) else \
+        validity(nodes, edges, n_nodes, rules, termination=termination, require_connected=require_connected)
+    c = res.counts.to(torch.float32)
+    zero = torch.zeros((), dtype=torch.float32, device=c.device)
+    some = c[3] > 0
+    return (torch.where(some, c[0] / c[3], zero), torch.where(c[1] > 0, c[2] / c[1], zero),
+            torch.where(some, c[1] / c[3], zero))

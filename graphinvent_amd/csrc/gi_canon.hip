@@ -35,13 +35,14 @@
 //                    word has found it, anybody else walks on.  No thread ever waits for another; a probe ends after
 //                    `capacity` slots.
 #include "gi_common.h"
+#include "gi_molread.h"
 
 namespace {
 
 typedef signed char i8;
 typedef unsigned long long u64;
 
-constexpr int NT = 256;
+constexpr int NT = GI_MOL_NT;
 constexpr int MAXN = GI_MAX_NODES;
 constexpr unsigned EMPTY = 0xFFFFFFFFu;
 constexpr int NO_TARGET = 0x7fffffff;
@@ -54,39 +55,6 @@ __device__ __forceinline__ u64 mix64(u64 x) {               // splitmix64 finali
 }
 __device__ __forceinline__ u64 tagged(int tag, u64 x) { return mix64(((u64)tag << 40) | x); }
 __device__ __forceinline__ u64 nonzero_word(u64 x) { return x ? x : 1ull; }
-
-__device__ __forceinline__ bool is01(float x) { return x == 0.f || x == 1.f; }
-__device__ __forceinline__ bool is01(i8 x) { return x == 0 || x == 1; }
-
-__device__ __forceinline__ long long load_count(const void* p, int bytes, long long g) {
-    return bytes == 1 ? (long long)((const i8*)p)[g] : bytes == 4 ? (long long)((const int*)p)[g]
-                                                                  : ((const long long*)p)[g];
-}
-
-// f(offset, is the value 1) for every non-zero element of p[0, len): whole 16-byte granules of the ADDRESS range are one
-// load each, a ragged first or last granule is read element by element; nothing outside p[0, len) is touched
-template <typename T, class F>
-__device__ __forceinline__ void for_each_nonzero(const T* p, int len, int tid, F f) {
-    constexpr int E = 16 / (int)sizeof(T);
-    const int shift = (int)(((uintptr_t)p & 15) / sizeof(T));
-    const int P = (shift + len + E - 1) / E;
-    for (int q = tid; q < P; q += NT) {
-        const int lo = q * E - shift;
-        const int a = max(lo, 0), b = min(lo + E, len);
-        T v[E];
-        if (b - a == E) {
-            const uint4 w = *reinterpret_cast<const uint4*>(p + a);
-            if ((w.x | w.y | w.z | w.w) == 0) continue;     // molecules are mostly zeros (+0.f is all zero bits)
-            __builtin_memcpy(v, &w, 16);
-        } else {
-#pragma unroll
-            for (int k = 0; k < E; ++k) v[k] = k < b - a ? p[a + k] : (T)0;
-        }
-#pragma unroll
-        for (int k = 0; k < E; ++k)
-            if (k < b - a && !(v[k] == (T)0)) f(a + k, is01(v[k]));
-    }
-}
 
 // bytes [0, len) at `p`, a [D0, D1, D2] array, written in 16-byte pieces between the ragged ends of the address range
 // (as store_bytes of gi_reorder.hip): src(a, b) names the source of the D2 bytes of pair (a, b) (negative: zeros) and
@@ -118,12 +86,6 @@ __device__ __forceinline__ void store_bytes(i8* p, int len, int tid, int D0, int
         }
         *reinterpret_cast<uint4*>(p + o) = make_uint4(w[0], w[1], w[2], w[3]);
     }
-}
-
-// bits [0, k) set, 0 <= k <= 128, as four 32-bit words
-__device__ __forceinline__ unsigned below_word(int k, int w) {
-    const int r = k - 32 * w;
-    return r <= 0 ? 0u : r >= 32 ? ~0u : (1u << r) - 1u;
 }
 
 __device__ __forceinline__ u64 wave_sum64(u64 x) {
@@ -160,13 +122,13 @@ __global__ __launch_bounds__(NT) void mol_canon_kernel(const T* __restrict__ nod
 
     // ---- 1: read and check -------------------------------------------------------------------------------
     int err = 0;
-    for_each_nonzero(nd, len_n, tid, [&](int o, bool ok) {
+    gi_for_each_nonzero(nd, len_n, tid, [&](int o, bool ok) {
         if (!ok) err |= GI_MOL_VALUE;
         const int i = o / Fn, f = o - i * Fn;
         atomicOr(&nbits[i * W + (f >> 5)], 1u << (31 - (f & 31)));
         atomicOr(&present[i >> 5], 1u << (i & 31));
     });
-    for_each_nonzero(ed, len_e, tid, [&](int o, bool ok) {
+    gi_for_each_nonzero(ed, len_e, tid, [&](int o, bool ok) {
         if (!ok) err |= GI_MOL_VALUE;
         const int e = o / Fe, t = o - e * Fe, i = e / N, j = e - i * N;
         atomicOr(&adj[(t * N + i) * 4 + (j >> 5)], 1u << (j & 31));
@@ -174,7 +136,7 @@ __global__ __launch_bounds__(NT) void mol_canon_kernel(const T* __restrict__ nod
     __syncthreads();
     int n;
     if (n_nodes) {
-        const long long c = load_count(n_nodes, nn_bytes, g);
+        const long long c = gi_load_count(n_nodes, nn_bytes, g);
         if (c < 0 || c > N) err |= GI_MOL_NODE_PAST_N;
         n = (int)(c < 0 ? 0 : c > N ? N : c);
     } else {                                                 // the leading rows with a set entry
@@ -182,13 +144,13 @@ __global__ __launch_bounds__(NT) void mol_canon_kernel(const T* __restrict__ nod
         while (n < 4 && present[n] == ~0u) ++n;
         n = n == 4 ? 128 : 32 * n + __builtin_ctz(~present[n]);
     }
-    if (tid < 4 && (present[tid] & ~below_word(n, tid))) err |= GI_MOL_NODE_PAST_N;
+    if (tid < 4 && (present[tid] & ~gi_below_word(n, tid))) err |= GI_MOL_NODE_PAST_N;
     for (int idx = tid; idx < Fe * N; idx += NT) {           // row (t, i): inside n, and mirrored
         const int t = idx / N, i = idx - t * N;
         for (int w = 0; w < 4; ++w) {
             unsigned bits = adj[idx * 4 + w];
             if (bits == 0) continue;
-            if (i >= n || (bits & ~below_word(n, w))) err |= GI_MOL_BOND_PAST_N;
+            if (i >= n || (bits & ~gi_below_word(n, w))) err |= GI_MOL_BOND_PAST_N;
             while (bits) {
                 const int b = __builtin_ctz(bits), j = 32 * w + b;         // j < N: it came from an offset < N N Fe
                 bits &= bits - 1;

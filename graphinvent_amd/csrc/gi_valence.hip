@@ -1,0 +1,281 @@
+// Molecule validity on the device (gfx950): which of G generated molecules pass a valence test, and how many hydrogens
+// each one takes — the part of the reference's `validity_tensor` (util.py:549-585, Analyzer.py:501-544: one
+// `SanitizeMol` per molecule on the host) that is decidable from the labelled graph with the default bond set.  THIS IS A
+// VALENCE TEST OF THE LABELLED GRAPH: no kekulisation, no aromaticity perception; the table of allowed valences is the
+// caller's (analyze.ValenceRules), not RDKit's.
+//
+// mol_valence_kernel  one 256-lane WORKGROUP per molecule, the skeleton of mol_canon_kernel (gi_canon.hip):
+//   1  all waves read the molecule once (whole 16-byte granules of the address range, single elements at the ragged
+//      ends; fp32 or int8) and check it while they read; in LDS one 128-bit adjacency row per (bond type, node), and per
+//      node and segment (atom type, formal charge, implicit H) the number of set entries and the lowest of them;
+//   2  n (given, or the leading rows with a set entry) and the well-formedness bits: GI_MOL_VALUE, _NODE_PAST_N,
+//      _BOND_PAST_N, _ASYMMETRIC, _ONEHOT, _MULTI_BOND (any of them: the molecule is malformed and nothing below is
+//      evaluated), GI_VAL_SELF_LOOP, GI_VAL_EMPTY;
+//   3  one thread per atom: o2 = sum over bond types of order2[t] * popcount(row (t, i)), x = ceil(o2 / 2), v* = the lowest
+//      allowed valence >= x of (atom type, charge), fill = v* - x; no v*: the atom is over its valence;
+//   4  components by frontier expansion over the OR of the rows; at most N rounds whatever the data holds;
+//   5  thread 0 writes the verdict and adds the molecule to the counters (integer atomics: any order, one result).
+//      The counters live in a caller-owned scratch of GI_VAL_SCRATCH words that is zero between calls: the workgroup
+//      that draws the last ticket moves them into `counts` and zeroes the scratch again, so no launch or memset is
+//      needed to clear anything (calls that share a scratch must be ordered, e.g. by one stream).
+// Integer arithmetic only.  Every index is bounded by the dims: i, j < N because they come from an offset < N N Fe, a
+// segment index < its segment's size because it comes from an offset < Fn, a charge / type / H index is used only
+// when the row is one-hot.  LDS: Fe N 16 B dynamic (<= 16 KB), ~8 KB static.
+#include "gi_common.h"
+#include "gi_molread.h"
+
+namespace {
+
+typedef signed char i8;
+
+constexpr int NT = GI_MOL_NT;
+constexpr int MAXN = GI_MAX_NODES;
+constexpr int MOL_BITS = GI_MOL_ONEHOT | GI_MOL_BOND_PAST_N | GI_MOL_VALUE | GI_MOL_MULTI_BOND | GI_MOL_ASYMMETRIC |
+                         GI_MOL_NODE_PAST_N;
+
+struct ValTables {
+    const unsigned short* allowed;                           // [A * C]: bit v = total valence v is allowed
+    const int* mass;                                         // [A] millidalton
+    const i8* order2;                                        // [Fe] twice the bond order
+    const i8* h_values;                                      // [H] the stored implicit-H counts (H > 0)
+    int A, C, H, h_type, mass_h;
+};
+
+struct ValOut {
+    float* valid;
+    int* status;
+    int* first_bad;
+    i8* atom_valence;
+    i8* atom_h;
+    int* desc;
+    int* counts;
+    int* scratch;
+};
+
+template <typename T>
+__global__ __launch_bounds__(NT) void mol_valence_kernel(const T* __restrict__ nodes, const T* __restrict__ edges,
+                                                         const void* __restrict__ n_nodes, int nn_bytes, int N, int Fn,
+                                                         int Fe, ValTables tb, const void* __restrict__ term,
+                                                         int term_dtype, int require_connected, ValOut out) {
+    extern __shared__ unsigned adj[];                        // [Fe][N][4]: bit j of row (t, i): bond t between i and j
+    __shared__ unsigned orr[MAXN][4];                        // the OR of a node's rows over the bond types
+    __shared__ int seg_cnt[3][MAXN], seg_first[3][MAXN];
+    __shared__ unsigned present[4], vis[4], front[2][4];
+    __shared__ int flags_sh, first_sh, sums[4];              // sums: fills, atoms of type H, mass, bonds
+    const int g = blockIdx.x, tid = threadIdx.x;
+    const int len_n = N * Fn, len_e = N * N * Fe;
+    const T* nd = nodes + (size_t)g * len_n;
+    const T* ed = edges + (size_t)g * len_e;
+    const int o_c = tb.A, o_h = tb.A + tb.C, o_x = tb.A + tb.C + tb.H;    // segment ends; o_x <= Fn (checked on the host)
+    for (int i = tid; i < Fe * N * 4; i += NT) adj[i] = 0u;
+    for (int i = tid; i < 3 * MAXN; i += NT) { (&seg_cnt[0][0])[i] = 0; (&seg_first[0][0])[i] = 0x7fffffff; }
+    if (tid < 4) { present[tid] = 0u; vis[tid] = 0u; front[0][tid] = 0u; front[1][tid] = 0u; }
+    if (tid < 4) sums[tid] = 0;
+    if (tid == 0) { flags_sh = 0; first_sh = 0x7fffffff; }
+    __syncthreads();
+
+    // ---- 1: read and check -------------------------------------------------------------------------------
+    int flags = 0;
+    gi_for_each_nonzero(nd, len_n, tid, [&](int o, bool ok) {
+        if (!ok) flags |= GI_MOL_VALUE;
+        const int i = o / Fn, f = o - i * Fn;                // i < N
+        atomicOr(&present[i >> 5], 1u << (i & 31));
+        if (f < o_x) {                                       // a chirality segment (f >= o_x) is not looked at
+            const int s = f < o_c ? 0 : f < o_h ? 1 : 2;
+            atomicAdd(&seg_cnt[s][i], 1);
+            atomicMin(&seg_first[s][i], f - (s == 0 ? 0 : s == 1 ? o_c : o_h));
+        }
+    });
+    gi_for_each_nonzero(ed, len_e, tid, [&](int o, bool ok) {
+        if (!ok) flags |= GI_MOL_VALUE;
+        const int e = o / Fe, t = o - e * Fe, i = e / N, j = e - i * N;
+        if (i == j) flags |= GI_VAL_SELF_LOOP;
+        atomicOr(&adj[(t * N + i) * 4 + (j >> 5)], 1u << (j & 31));
+    });
+    __syncthreads();
+
+    // ---- 2: n and the well-formedness bits ---------------------------------------------------------------
+    int n;
+    if (n_nodes) {
+        const long long c = gi_load_count(n_nodes, nn_bytes, g);
+        if (c < 0 || c > N) flags |= GI_MOL_NODE_PAST_N;
+        n = (int)(c < 0 ? 0 : c > N ? N : c);
+    } else {                                                 // the leading rows with a set entry
+        n = 0;
+        while (n < 4 && present[n] == ~0u) ++n;
+        n = n == 4 ? 128 : 32 * n + __builtin_ctz(~present[n]);
+    }
+    if (tid < 4 && (present[tid] & ~gi_below_word(n, tid))) flags |= GI_MOL_NODE_PAST_N;
+    for (int idx = tid; idx < Fe * N; idx += NT) {           // row (t, i): inside n, and mirrored
+        const int t = idx / N, i = idx - t * N;
+        for (int w = 0; w < 4; ++w) {
+            unsigned bits = adj[idx * 4 + w];
+            if (bits == 0) continue;
+            if (i >= n || (bits & ~gi_below_word(n, w))) flags |= GI_MOL_BOND_PAST_N;
+            while (bits) {
+                const int b = __builtin_ctz(bits), j = 32 * w + b;         // j < N: it came from an offset < N N Fe
+                bits &= bits - 1;
+                if (!((adj[(t * N + j) * 4 + (i >> 5)] >> (i & 31)) & 1u)) flags |= GI_MOL_ASYMMETRIC;
+            }
+        }
+    }
+    bool arom = false;
+    if (tid < N) {                                           // this thread's node: OR of its rows, several types on a pair
+        unsigned seen[4] = {0u, 0u, 0u, 0u};
+        for (int t = 0; t < Fe; ++t)
+            for (int w = 0; w < 4; ++w) {
+                const unsigned row = adj[(t * N + tid) * 4 + w];
+                const unsigned diag = (tid >> 5) == w ? 1u << (tid & 31) : 0u;
+                if (row & seen[w] & ~diag) flags |= GI_MOL_MULTI_BOND;
+                if (row && tb.order2[t] == 3) arom = true;
+                seen[w] |= row;
+            }
+        for (int w = 0; w < 4; ++w) orr[tid][w] = seen[w];
+        if (tid < n && (seg_cnt[0][tid] != 1 || seg_cnt[1][tid] != 1 || (tb.H > 0 && seg_cnt[2][tid] != 1)))
+            flags |= GI_MOL_ONEHOT;
+    }
+    if (n == 0) flags |= GI_VAL_EMPTY;
+    if (flags) atomicOr(&flags_sh, flags);
+    __syncthreads();
+    const bool sound = (flags_sh & MOL_BITS) == 0;           // uniform
+    const bool mine = sound && tid < n;                      // this thread owns atom `tid`
+
+    // ---- 3: valences and the hydrogen fill -----------------------------------------------------------------
+    int x = -1, h = -1;
+    flags = 0;
+    if (mine) {
+        int o2 = 0;
+        for (int t = 0; t < Fe; ++t) {
+            int deg = 0;
+            for (int w = 0; w < 4; ++w) deg += __popc(adj[(t * N + tid) * 4 + w]);
+            o2 += (int)tb.order2[t] * deg;                   // <= 6 * 8 * 128
+        }
+        x = (o2 + 1) >> 1;
+        const int a = seg_first[0][tid], c = seg_first[1][tid];           // a < A, c < C: the row is one-hot
+        const unsigned ok = (unsigned)tb.allowed[a * tb.C + c];
+        const unsigned at_least = x > 15 ? 0u : (ok >> x) << x;
+        if (at_least == 0u) {
+            flags |= GI_VAL_OVER;
+            atomicMin(&first_sh, tid);
+            h = 0;
+        } else {
+            h = __builtin_ctz(at_least) - x;
+            if (tb.H > 0 && (int)tb.h_values[seg_first[2][tid]] != h) flags |= GI_VAL_H_MISMATCH;
+        }
+        if (arom) flags |= GI_VAL_AROMATIC;
+        int above = 0;                                       // bonded partners of higher index
+        for (int w = 0; w < 4; ++w) above += __popc(orr[tid][w] & ~gi_below_word(tid + 1, w));
+        if (h) atomicAdd(&sums[0], h);
+        if (a == tb.h_type) atomicAdd(&sums[1], 1);
+        atomicAdd(&sums[2], tb.mass[a]);
+        if (above) atomicAdd(&sums[3], above);
+        x = min(x, 127);
+    }
+
+    // ---- 4: components ---------------------------------------------------------------------------------------
+    int comps = 0;
+    if (sound) {                                             // uniform
+        int cur = 0;
+        for (int round = 0; round < N; ++round) {
+            __syncthreads();                                 // vis and front[cur] of the round before are complete
+            bool all = true, empty = true;
+            int seed = -1;
+            for (int w = 3; w >= 0; --w) {
+                const unsigned left = gi_below_word(n, w) & ~vis[w];
+                if (left) { all = false; seed = 32 * w + __builtin_ctz(left); }
+                if (front[cur][w]) empty = false;
+            }
+            if (all) break;
+            if (empty) ++comps;                              // a new component starts at the lowest node not yet seen
+            const bool in_front = empty ? tid == seed : (tid < n && ((front[cur][tid >> 5] >> (tid & 31)) & 1u));
+            __syncthreads();                                 // everybody has read vis and front[cur]
+            if (tid < 4) front[cur ^ 1][tid] = 0u;
+            if (empty && tid == seed) atomicOr(&vis[tid >> 5], 1u << (tid & 31));
+            __syncthreads();
+            unsigned reach[4] = {0u, 0u, 0u, 0u};
+            if (in_front)
+                for (int w = 0; w < 4; ++w) reach[w] = orr[tid][w] & gi_below_word(n, w) & ~vis[w];
+            __syncthreads();                                 // vis is read before anybody adds to it
+            if (in_front)
+                for (int w = 0; w < 4; ++w)
+                    if (reach[w]) { atomicOr(&front[cur ^ 1][w], reach[w]); atomicOr(&vis[w], reach[w]); }
+            cur ^= 1;
+        }
+        if (comps > 1) flags |= GI_VAL_FRAGMENTS;
+    }
+    if (flags) atomicOr(&flags_sh, flags);
+    __syncthreads();
+
+    // ---- 5: outputs ------------------------------------------------------------------------------------------
+    for (int a = tid; a < N; a += NT) {                      // N <= 128 < NT: thread a is atom a's owner
+        out.atom_valence[(size_t)g * N + a] = (i8)x;
+        out.atom_h[(size_t)g * N + a] = (i8)h;
+    }
+    if (tid == 0) {
+        const int status = flags_sh;
+        int invalid = MOL_BITS | GI_VAL_EMPTY | GI_VAL_SELF_LOOP | GI_VAL_OVER;
+        if (require_connected) invalid |= GI_VAL_FRAGMENTS;
+        const int valid = (status & invalid) == 0;
+        out.status[g] = status;
+        out.valid[g] = valid ? 1.f : 0.f;
+        out.first_bad[g] = first_sh == 0x7fffffff ? -1 : first_sh;
+        int* d = out.desc + (size_t)g * GI_VAL_DESC;
+        const int bonds = sums[3];
+        d[0] = sound ? n : 0;
+        d[1] = sums[0] + sums[1];
+        d[2] = sums[2] + sums[0] * tb.mass_h;
+        d[3] = bonds;
+        d[4] = comps;
+        d[5] = sound ? bonds - n + comps : 0;
+        int terminated = 0;
+        if (term) terminated = term_dtype == GI_DTYPE_I8 ? ((const i8*)term)[g] != 0 : ((const float*)term)[g] != 0.f;
+        int* sc = out.scratch;
+        if (valid) atomicAdd(&sc[0], 1);
+        if (terminated) atomicAdd(&sc[1], 1);
+        if (valid && terminated) atomicAdd(&sc[2], 1);
+        __threadfence();                                     // the sums before the ticket
+        if (atomicAdd(&sc[3], 1) == (int)gridDim.x - 1) {    // the last workgroup: every sum is complete
+            __threadfence();
+            for (int k = 0; k < 3; ++k) out.counts[k] = atomicExch(&sc[k], 0);
+            out.counts[3] = (int)gridDim.x;
+            atomicExch(&sc[3], 0);                           // the scratch is zero again for the next call
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int gi_mol_valence(int G, int N, int Fn, int Fe, const void* nodes, const void* edges, int dtype,
+                              const void* n_nodes, int n_nodes_bytes, int n_types, int n_charges, int n_imp_h,
+                              const unsigned short* allowed, const int* mass, const signed char* order2,
+                              const signed char* h_values, int h_type, int mass_h, const void* termination,
+                              int term_dtype, int require_connected, float* valid, int* status, int* first_bad,
+                              signed char* atom_valence, signed char* atom_h, int* desc, int* counts, int* scratch,
+                              void* stream) {
+    (void)hipGetLastError();
+    if (G < 0 || N < 1 || Fn < 1 || Fe < 1 || N > GI_MAX_NODES || Fe > GI_MAX_GROUPS) return GI_EINVAL;
+    if (Fn > GI_ANALYZE_MAX_FN) return GI_ELIMIT;
+    if ((dtype != GI_DTYPE_F32 && dtype != GI_DTYPE_I8) ||
+        (n_nodes_bytes != 1 && n_nodes_bytes != 4 && n_nodes_bytes != 8) ||
+        (term_dtype != GI_DTYPE_F32 && term_dtype != GI_DTYPE_I8))
+        return GI_EINVAL;
+    if (n_types < 1 || n_charges < 1 || n_imp_h < 0 || (long long)n_types + n_charges + n_imp_h > Fn ||
+        h_type < -1 || h_type >= n_types)
+        return GI_EINVAL;
+    if (G == 0) return 0;
+    if (!nodes || !edges || !allowed || !mass || !order2 || (n_imp_h > 0 && !h_values) || !valid || !status ||
+        !first_bad || !atom_valence || !atom_h || !desc || !counts || !scratch)
+        return GI_EINVAL;
+    const ValTables tb = {allowed, mass, order2, h_values, n_types, n_charges, n_imp_h, h_type, mass_h};
+    const ValOut out = {valid, status, first_bad, atom_valence, atom_h, desc, counts, scratch};
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t lds = (size_t)Fe * N * 4 * sizeof(unsigned);                                      // <= 16 KB
+    if (dtype == GI_DTYPE_F32)
+        hipLaunchKernelGGL(mol_valence_kernel<float>, dim3(G), dim3(NT), lds, st, (const float*)nodes,
+                           (const float*)edges, n_nodes, n_nodes_bytes, N, Fn, Fe, tb, termination, term_dtype,
+                           require_connected, out);
+    else
+        hipLaunchKernelGGL(mol_valence_kernel<i8>, dim3(G), dim3(NT), lds, st, (const i8*)nodes, (const i8*)edges,
+                           n_nodes, n_nodes_bytes, N, Fn, Fe, tb, termination, term_dtype, require_connected, out);
+    return gi_launch_status();
+}

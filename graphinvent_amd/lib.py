@@ -155,6 +155,9 @@ ANALYZE_MAX_FN, ANALYZE_MAX_HIST, ANALYZE_EDGE_BINS = 512, 1024, 10      # GI_AN
 MOL_ONEHOT, MOL_BOND_PAST_N, MOL_OVERFLOW, MOL_VALUE, MOL_MULTI_BOND = 1, 2, 4, 8, 16   # GI_MOL_*
 MOL_ASYMMETRIC, MOL_NODE_PAST_N = 32, 64                # GI_MOL_* of gi_mol_canon
 MOL_COUNTS, SEEN_FULL = 3, 1                            # GI_MOL_COUNTS, GI_SEEN_FULL
+(VAL_EMPTY, VAL_SELF_LOOP, VAL_OVER, VAL_FRAGMENTS, VAL_AROMATIC,
+ VAL_H_MISMATCH) = 128, 256, 512, 1024, 2048, 4096      # GI_VAL_* of gi_mol_valence
+VAL_DESC, VAL_COUNTS, VAL_SCRATCH = 6, 4, 4             # GI_VAL_DESC, GI_VAL_COUNTS, GI_VAL_SCRATCH
 
 
 class RouteDims(C.Structure):
@@ -283,6 +286,8 @@ SIGNATURES = {
     "gi_mol_unique_ws_bytes": (cll, [ci]),
     "gi_mol_unique": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "gi_mol_seen_add": (ci, [ci, vp, vp, vp, vp, cll, vp, vp, vp]),
+    "gi_mol_valence": (ci, [ci, ci, ci, ci, vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp, ci, ci, vp, ci, ci,
+                            vp, vp, vp, vp, vp, vp, vp, vp, vp]),
 }
 FUSE_GATES_V4, FUSE_DH_SCATTER, FUSE_TIER2_DSELU, FUSE_SLOTS = 1, 2, 4, 8  # GI_FUSE_*
 

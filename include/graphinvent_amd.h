@@ -1149,6 +1149,53 @@ int gi_mol_unique(int G, int N, int Fn, int Fe, const unsigned long long* key, c
 int gi_mol_seen_add(int G, const unsigned long long* key, const int* status, const int* rep,
                     unsigned long long* table, long long capacity, int* info, int* is_new, void* stream);
 
+/* Molecule validity (gi_valence.hip): a valence test of the labelled graph and the hydrogen fill, the part of the
+ * reference's validity_tensor (util.py:549-585, Analyzer.py:501-544; one SanitizeMol per molecule on the host) that the
+ * tensors decide for the bond set single / double / triple.  NOT RDKit: no kekulisation and no aromaticity perception
+ * is done, and the table of allowed valences is the caller's.  nodes / edges / n_nodes / dtype as for gi_mol_canon
+ * (n_nodes = NULL: the number of LEADING node rows with a set entry).
+ *
+ * gi_mol_valence, one launch.  A node row is [ atom type n_types | formal charge n_charges | implicit H n_imp_h (may be
+ * 0) | anything else (chirality; never looked at beyond "the row has a set entry") ], n_types + n_charges + n_imp_h <=
+ * Fn.  Device tables: allowed [n_types * n_charges] (16 bits each: bit v set = total valence v is allowed for that
+ * atom type and charge), mass [n_types] (int32, millidalton), order2 [Fe] (int8, twice the bond order), h_values
+ * [n_imp_h] (int8, the hydrogen count every entry of the implicit-H segment stands for; NULL if n_imp_h = 0).  h_type:
+ * the atom type that is hydrogen (-1: none), mass_h: its mass.  termination [G] (GI_DTYPE_I8 or _F32; NULL: nothing
+ * is terminated).
+ *
+ * status [G]: a molecule with one of GI_MOL_VALUE, _NODE_PAST_N, _BOND_PAST_N, _ASYMMETRIC (as gi_mol_canon),
+ * GI_MOL_ONEHOT (a row < n without exactly one non-zero entry in the type, charge or implicit-H segment) or
+ * GI_MOL_MULTI_BOND (some pair i != j carries several bond types) is MALFORMED: it is invalid, atom_valence / atom_h
+ * are -1 for all N slots, first_bad is -1, desc is zero and no GI_VAL_* bit other than _EMPTY and _SELF_LOOP is
+ * evaluated.  Otherwise, per atom i < n, in integers:
+ *   o2 = sum over t of order2[t] * #{j : edges[i, j, t]},  x = ceil(o2 / 2),
+ *   v* = the smallest allowed valence >= x; none: the atom is OVER (fill 0); else the fill is h = v* - x.
+ * atom_valence [G, N] int8 = min(x, 127), atom_h [G, N] int8 = the fill, both -1 at i >= n; first_bad [G] = the
+ * lowest atom that is over, -1 if none; desc [G, GI_VAL_DESC] int32 = n_atoms, n_h (the fills plus the atoms of type
+ * h_type), mass_mda (sum of mass[type] + fills * mass_h), n_bonds (pairs i < j with a bond), n_components, n_rings =
+ * n_bonds - n_atoms + n_components.  valid [G] fp32 = 1 unless a GI_MOL_* bit above, GI_VAL_EMPTY, _SELF_LOOP or _OVER
+ * is set (or _FRAGMENTS, with require_connected != 0).  counts [GI_VAL_COUNTS] int32: valid molecules, terminated
+ * ones, valid and terminated ones, G; integer sums, so every output is deterministic.  scratch [GI_VAL_SCRATCH] int32:
+ * owned by the caller, ZERO before its first use and left zero by every completed call (the workgroup that finishes
+ * last moves the sums into counts and clears it, so nothing has to be cleared by a launch or a memset); calls that
+ * share a scratch must be ordered, e.g. issued on one stream.  G = 0 returns 0 and touches nothing.  Every loop is
+ * bounded by the dims whatever the data holds (components: at most N rounds). */
+#define GI_VAL_EMPTY 128            /* n == 0 (the reference's mol = None ends at validity 0) */
+#define GI_VAL_SELF_LOOP 256        /* edges[i, i, t] is set (AddBond refuses it) */
+#define GI_VAL_OVER 512             /* some atom exceeds every allowed valence of its type and charge */
+#define GI_VAL_FRAGMENTS 1024       /* more than one component (invalid only with require_connected) */
+#define GI_VAL_AROMATIC 2048        /* a bond of order 1.5 is present: counted 3 per 2, no kekulisation (informational) */
+#define GI_VAL_H_MISMATCH 4096      /* an atom's stored implicit-H count differs from its fill (informational) */
+#define GI_VAL_DESC 6
+#define GI_VAL_COUNTS 4
+#define GI_VAL_SCRATCH 4
+int gi_mol_valence(int G, int N, int Fn, int Fe, const void* nodes, const void* edges, int dtype,
+                   const void* n_nodes, int n_nodes_bytes, int n_types, int n_charges, int n_imp_h,
+                   const unsigned short* allowed, const int* mass, const signed char* order2,
+                   const signed char* h_values, int h_type, int mass_h, const void* termination, int term_dtype,
+                   int require_connected, float* valid, int* status, int* first_bad, signed char* atom_valence,
+                   signed char* atom_h, int* desc, int* counts, int* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
