@@ -35,6 +35,8 @@ integers (rounded once to fp32), which is deliberately not the reference's resul
 from __future__ import annotations
 
 import ctypes as C
+import functools
+import math
 from typing import Iterator, Optional, Sequence
 
 import numpy as np
@@ -106,6 +108,92 @@ def _check_inputs(what: str, nodes, edges, n_nodes, groups: Sequence[int], need_
     return G, N, Fn, Fe, dtype, n_nodes, nn_bytes, groups
 
 
+def _check_termination(what: str, termination, G: int, dev):
+    """-> (termination as contiguous int8 or fp32 (or None), its dtype code)."""
+    if termination is None:
+        return None, L.DTYPE_I8
+    if not isinstance(termination, torch.Tensor) or not termination.is_cuda or termination.device != dev:
+        raise RuntimeError(f"{what}: termination must be a CUDA tensor on {dev} (no CPU fallback)")
+    if tuple(termination.shape) != (G,):
+        raise ValueError(f"{what}: termination has shape {tuple(termination.shape)}, expected ({G},)")
+    if termination.dtype == torch.int8:
+        return termination.contiguous(), L.DTYPE_I8
+    return termination.float().contiguous(), L.DTYPE_F32
+
+
+_ITEMSIZE = {"int8": 1, "int16": 2, "int32": 4, "int64": 8, "float32": 4}
+
+
+def _pack(*arrays) -> dict:
+    """``(name, dtype name, shape), ...`` in byte order -> ``name -> (byte offset, bytes, dtype name, shape)``."""
+    table, off = {}, 0
+    for name, dtype, shape in arrays:
+        item = _ITEMSIZE[dtype]
+        assert off % item == 0, name                        # every array is aligned to its element size
+        table[name] = (off, item * math.prod(shape), dtype, shape)
+        off += table[name][1]
+    return table
+
+
+class _ResultBuffer:
+    """The outputs of one launch as arrays inside ONE byte buffer on the device, so that ``host()`` needs one copy.
+    A subclass declares ``layout(*dims)`` (a ``_pack`` table, kept per dims: a launch-bound call cannot afford to
+    rebuild it) and what ``host()`` returns (``_host_result``).  The device views are attributes made when first
+    asked for (a caller that wants one does not pay for all, and the launch takes its pointers from ``_ptrs()``,
+    without a view); ``_HOST_DTYPE`` names the arrays whose numpy dtype differs from the device's."""
+
+    _HOST_DTYPE: dict = {}
+
+    def __init__(self, buf: torch.Tensor, G: int, *dims: int):
+        self._buf, self._layout, self._host, self._pinned = buf, self.layout(G, *dims), None, None
+        self.G = G
+
+    @classmethod
+    def nbytes(cls, *dims: int) -> int:
+        off, size, _, _ = next(reversed(cls.layout(*dims).values()))          # the last array ends the buffer
+        return off + size
+
+    @classmethod
+    def empty(cls, dev, *dims: int, **kw):
+        return cls(torch.empty(cls.nbytes(*dims), dtype=torch.uint8, device=dev), *dims, **kw)
+
+    def _ptrs(self) -> dict:
+        base = self._buf.data_ptr()
+        return {name: base + entry[0] for name, entry in self._layout.items()}
+
+    def _view(self, name, buf, xp):
+        off, size, dtype, shape = self._layout[name]
+        if xp is np:
+            dtype = self._HOST_DTYPE.get(name, dtype)
+        return buf[off:off + size].view(getattr(xp, dtype)).reshape(shape)
+
+    def __getattr__(self, name):
+        if name in self.__dict__.get("_layout", ()):
+            view = self.__dict__[name] = self._view(name, self._buf, torch)
+            return view
+        raise AttributeError(name)
+
+    def host(self):
+        """All arrays as numpy arrays on the host: ONE asynchronous copy of the buffer into pinned memory and ONE
+        synchronisation (of the current stream), done once and kept."""
+        if self._host is None:
+            dev = self._buf.device
+            with _host_sync_allowed():                  # the read-out's one wait, under a caller's sync debug mode
+                pinned = torch.empty(self._buf.numel(), dtype=torch.uint8, pin_memory=True)
+                if pinned.numel() > 0:
+                    stream = torch.cuda.current_stream(dev)
+                    with torch.cuda.device(dev):
+                        pinned.copy_(self._buf, non_blocking=True)
+                    stream.synchronize()
+            self._pinned = pinned                       # the arrays are views of it
+            host = pinned.numpy()
+            self._host = self._host_result({name: self._view(name, host, np) for name in self._layout})
+        return self._host
+
+    def __len__(self):
+        return self.G
+
+
 def molecular_properties(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Optional[torch.Tensor],
                          groups: Sequence[int], *, termination: Optional[torch.Tensor] = None,
                          epoch_key: Optional[str] = None, max_n_nodes: Optional[int] = None,
@@ -151,17 +239,8 @@ def molecular_properties(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Opti
             raise ValueError(f"{what}: three groups hold exactly one of implicit H and chirality")
     else:
         use_imp_H = use_chirality = len(groups) == 4
-    term_dtype = L.DTYPE_I8
-    if termination is not None:
-        if not isinstance(termination, torch.Tensor) or not termination.is_cuda or termination.device != nodes.device:
-            raise RuntimeError(f"{what}: termination must be a CUDA tensor on {nodes.device} (no CPU fallback)")
-        if tuple(termination.shape) != (G,):
-            raise ValueError(f"{what}: termination has shape {tuple(termination.shape)}, expected ({G},)")
-        if termination.dtype != torch.int8:
-            termination = termination.float()
-            term_dtype = L.DTYPE_F32
-        termination = termination.contiguous()
     dev = nodes.device
+    termination, term_dtype = _check_termination(what, termination, G, dev)
     nb = H + Fn + L.ANALYZE_EDGE_BINS + Fe
     out = torch.zeros(nb + 3, dtype=torch.float32, device=dev)
     if G > 0:
@@ -194,41 +273,23 @@ def molecular_properties(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Opti
     return props
 
 
-class DecodedMolecules:
+class DecodedMolecules(_ResultBuffer):
     """What ``decode`` wrote, on the device: ``atoms`` [G, N, S] int8, ``bonds`` [G, max_bonds, 3] int16, ``n_bonds``
-    [G] int32 and ``status`` [G] int32, views of one byte buffer so that ``host()`` needs one copy."""
+    [G] int32 and ``status`` [G] int32; ``host()`` -> numpy ``(atoms, bonds, n_bonds, status)``."""
 
     def __init__(self, buf: torch.Tensor, G: int, N: int, S: int, max_bonds: int):
-        self._buf, self._host, self._pinned = buf, None, None
-        self.G, self.N, self.S, self.max_bonds = G, N, S, max_bonds
-        self.atoms, self.bonds, self.n_bonds, self.status = self._views(buf, torch)
+        super().__init__(buf, G, N, S, max_bonds)
+        self.N, self.S, self.max_bonds = N, S, max_bonds
 
     @staticmethod
-    def nbytes(G: int, N: int, S: int, max_bonds: int) -> int:
-        return 8 * G + 6 * G * max_bonds + G * N * S        # status | n_bonds | bonds | atoms: each aligned to itself
+    @functools.lru_cache(maxsize=64)
+    def layout(G: int, N: int, S: int, max_bonds: int) -> dict:
+        return _pack(("status", "int32", (G,)), ("n_bonds", "int32", (G,)), ("bonds", "int16", (G, max_bonds, 3)),
+                     ("atoms", "int8", (G, N, S)))
 
-    def _views(self, buf, xp):
-        G, N, S, mb = self.G, self.N, self.S, self.max_bonds
-        o_n, o_b, o_a = 4 * G, 8 * G, 8 * G + 6 * G * mb
-        status, n_bonds = buf[:o_n].view(xp.int32), buf[o_n:o_b].view(xp.int32)
-        bonds, atoms = buf[o_b:o_a].view(xp.int16).reshape(G, mb, 3), buf[o_a:].view(xp.int8).reshape(G, N, S)
-        return atoms, bonds, n_bonds, status
-
-    def host(self):
-        """-> numpy ``(atoms, bonds, n_bonds, status)``: ONE asynchronous copy of all four arrays into pinned memory
-        and ONE synchronisation (of the current stream), done once and kept."""
-        if self._host is None:
-            dev = self._buf.device
-            with _host_sync_allowed():                  # the read-out's one wait, under a caller's sync debug mode
-                pinned = torch.empty(self._buf.numel(), dtype=torch.uint8, pin_memory=True)
-                if self.G > 0:
-                    stream = torch.cuda.current_stream(dev)
-                    with torch.cuda.device(dev):
-                        pinned.copy_(self._buf, non_blocking=True)
-                    stream.synchronize()
-            self._pinned = pinned                       # the arrays are views of it
-            self._host = self._views(pinned.numpy(), np)
-        return self._host
+    @staticmethod
+    def _host_result(a):
+        return a["atoms"], a["bonds"], a["n_bonds"], a["status"]
 
     def molecule(self, i: int):
         """-> ``(atoms [n, S], bonds [min(n_bonds, max_bonds), 3], status)`` of graph ``i`` on the host, ``n`` being
@@ -238,9 +299,6 @@ class DecodedMolecules:
         live = np.flatnonzero((a >= 0).any(axis=1))
         n = int(live[-1]) + 1 if live.size else 0
         return a[:n], bonds[i, :min(int(n_bonds[i]), self.max_bonds)], int(status[i])
-
-    def __len__(self):
-        return self.G
 
 
 def decode(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: torch.Tensor, groups: Sequence[int], *,
@@ -270,14 +328,13 @@ def decode(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: torch.Tensor, grou
         raise ValueError(f"{what}: max_bonds must be in [1, 2**20]")
     S = len(groups)
     dev = nodes.device
-    res = DecodedMolecules(torch.empty(DecodedMolecules.nbytes(G, N, S, mb), dtype=torch.uint8, device=dev),
-                           G, N, S, mb)
+    res = DecodedMolecules.empty(dev, G, N, S, mb)
     if G > 0:
-        seg = (C.c_int * S)(*groups)
+        seg, out = (C.c_int * S)(*groups), res._ptrs()
         with torch.cuda.device(dev):
             L.check(L.load().gi_mol_decode(
                 G, N, Fn, Fe, nodes.data_ptr(), edges.data_ptr(), dtype, n_nodes.data_ptr(), nn_bytes, S, seg, mb,
-                res.atoms.data_ptr(), res.bonds.data_ptr(), res.n_bonds.data_ptr(), res.status.data_ptr(),
+                out["atoms"], out["bonds"], out["n_bonds"], out["status"],
                 torch.cuda.current_stream(dev).cuda_stream), "gi_mol_decode")
     if strict:
         status = res.host()[3]
@@ -334,46 +391,27 @@ CANON_STATUS_MESSAGES = {
 }
 
 
-class CanonicalMolecules:
+class CanonicalMolecules(_ResultBuffer):
     """What ``canonical`` wrote, on the device: ``order`` / ``rank`` [G, N] int32, ``key`` [G, 2] int64 (the two
-    64-bit words of the key, as torch has no uint64 arithmetic; ``host()`` gives uint64), ``status`` [G] int32 — views
-    of one byte buffer so that ``host()`` needs one copy — and, if asked for, ``nodes`` [G, N, Fn] / ``edges``
+    64-bit words of the key, as torch has no uint64 arithmetic; ``host()`` gives uint64), ``status`` [G] int32;
+    ``host()`` -> numpy ``(order, rank, key, status)``.  And, if asked for, ``nodes`` [G, N, Fn] / ``edges``
     [G, N, N, Fe] int8, the canonical molecules (``None`` otherwise; not part of ``host()``)."""
 
+    _HOST_DTYPE = {"key": "uint64"}
+
     def __init__(self, buf: torch.Tensor, G: int, N: int, nodes=None, edges=None):
-        self._buf, self._host, self._pinned = buf, None, None
-        self.G, self.N, self.nodes, self.edges = G, N, nodes, edges
-        self.order, self.rank, self.key, self.status = self._views(buf, torch)
+        super().__init__(buf, G, N)
+        self.N, self.nodes, self.edges = N, nodes, edges
 
     @staticmethod
-    def nbytes(G: int, N: int) -> int:
-        return 16 * G + 8 * G * N + 4 * G                   # key | order | rank | status: each aligned to itself
+    @functools.lru_cache(maxsize=64)
+    def layout(G: int, N: int) -> dict:
+        return _pack(("key", "int64", (G, 2)), ("order", "int32", (G, N)), ("rank", "int32", (G, N)),
+                     ("status", "int32", (G,)))
 
-    def _views(self, buf, xp):
-        G, N = self.G, self.N
-        o_o, o_r, o_s = 16 * G, 16 * G + 4 * G * N, 16 * G + 8 * G * N
-        key = buf[:o_o].view(xp.int64 if xp is torch else xp.uint64).reshape(G, 2)
-        order, rank = buf[o_o:o_r].view(xp.int32).reshape(G, N), buf[o_r:o_s].view(xp.int32).reshape(G, N)
-        return order, rank, key, buf[o_s:].view(xp.int32)
-
-    def host(self):
-        """-> numpy ``(order, rank, key, status)``, ``key`` as uint64: ONE asynchronous copy into pinned memory and
-        ONE synchronisation (of the current stream), done once and kept."""
-        if self._host is None:
-            dev = self._buf.device
-            with _host_sync_allowed():
-                pinned = torch.empty(self._buf.numel(), dtype=torch.uint8, pin_memory=True)
-                if self.G > 0:
-                    stream = torch.cuda.current_stream(dev)
-                    with torch.cuda.device(dev):
-                        pinned.copy_(self._buf, non_blocking=True)
-                    stream.synchronize()
-            self._pinned = pinned
-            self._host = self._views(pinned.numpy(), np)
-        return self._host
-
-    def __len__(self):
-        return self.G
+    @staticmethod
+    def _host_result(a):
+        return a["order"], a["rank"], a["key"], a["status"]
 
 
 def canonical(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Optional[torch.Tensor] = None, *,
@@ -406,13 +444,14 @@ def canonical(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Optional[torch.
     if want_molecules:
         cn = torch.empty((G, N, Fn), dtype=torch.int8, device=dev)
         ce = torch.empty((G, N, N, Fe), dtype=torch.int8, device=dev)
-    res = CanonicalMolecules(torch.empty(CanonicalMolecules.nbytes(G, N), dtype=torch.uint8, device=dev), G, N, cn, ce)
+    res = CanonicalMolecules.empty(dev, G, N, nodes=cn, edges=ce)
     if G > 0:
+        out = res._ptrs()
         with torch.cuda.device(dev):
             L.check(L.load().gi_mol_canon(
                 G, N, Fn, Fe, nodes.data_ptr(), edges.data_ptr(), dtype,
-                None if n_nodes is None else n_nodes.data_ptr(), nn_bytes, res.order.data_ptr(), res.rank.data_ptr(),
-                res.key.data_ptr(), res.status.data_ptr(), None if cn is None else cn.data_ptr(),
+                None if n_nodes is None else n_nodes.data_ptr(), nn_bytes, out["order"], out["rank"], out["key"],
+                out["status"], None if cn is None else cn.data_ptr(),
                 None if ce is None else ce.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "gi_mol_canon")
     return res
 
@@ -671,62 +710,28 @@ class ValenceRules:
         return self._order2[Fe]
 
 
-class MoleculeValidity:
+class MoleculeValidity(_ResultBuffer):
     """What ``validity`` wrote, on the device: ``valid`` [G] fp32, ``status`` / ``first_bad`` [G] int32,
     ``atom_valence`` / ``atom_h`` [G, N] int8, ``desc`` [G, 6] int32 (``DESC_NAMES``) and ``counts`` [4] int32 (valid,
-    terminated, valid and terminated, G) — views of one byte buffer (made when first asked for) so that ``host()`` needs
-    one copy."""
+    terminated, valid and terminated, G); ``host()`` -> ``{name: numpy array}`` of all seven."""
 
     DESC_NAMES = ("n_atoms", "n_h", "mass_mda", "n_bonds", "n_components", "n_rings")
-    _NAMES = ("valid", "status", "first_bad", "atom_valence", "atom_h", "desc", "counts")
 
     def __init__(self, buf: torch.Tensor, G: int, N: int):
-        self._buf, self._host, self._pinned = buf, None, None
-        self.G, self.N = G, N
+        super().__init__(buf, G, N)
+        self.N = N
 
     @staticmethod
-    def nbytes(G: int, N: int) -> int:
-        return 16 + 36 * G + 2 * G * N       # counts | status | first_bad | valid | desc | atom_valence | atom_h
-
-    @staticmethod
+    @functools.lru_cache(maxsize=64)
     def layout(G: int, N: int) -> dict:
         """name -> (byte offset, bytes, dtype name, shape) inside the buffer; every array is aligned to itself."""
-        return {"counts": (0, 16, "int32", (L.VAL_COUNTS,)), "status": (16, 4 * G, "int32", (G,)),
-                "first_bad": (16 + 4 * G, 4 * G, "int32", (G,)), "valid": (16 + 8 * G, 4 * G, "float32", (G,)),
-                "desc": (16 + 12 * G, 24 * G, "int32", (G, L.VAL_DESC)),
-                "atom_valence": (16 + 36 * G, G * N, "int8", (G, N)),
-                "atom_h": (16 + 36 * G + G * N, G * N, "int8", (G, N))}
+        return _pack(("counts", "int32", (L.VAL_COUNTS,)), ("status", "int32", (G,)), ("first_bad", "int32", (G,)),
+                     ("valid", "float32", (G,)), ("desc", "int32", (G, L.VAL_DESC)), ("atom_valence", "int8", (G, N)),
+                     ("atom_h", "int8", (G, N)))
 
-    def _view(self, name, buf, xp):
-        off, size, dtype, shape = self.layout(self.G, self.N)[name]
-        return buf[off:off + size].view(getattr(xp, dtype)).reshape(shape)
-
-    def __getattr__(self, name):
-        # the device views are made when first asked for: a caller that wants `valid` does not pay for seven
-        if name in MoleculeValidity._NAMES:
-            view = self._view(name, self._buf, torch)
-            self.__dict__[name] = view
-            return view
-        raise AttributeError(name)
-
-    def host(self) -> dict:
-        """-> ``{name: numpy array}`` of all seven outputs: ONE asynchronous copy into pinned memory and ONE
-        synchronisation (of the current stream), done once and kept."""
-        if self._host is None:
-            dev = self._buf.device
-            with _host_sync_allowed():
-                pinned = torch.empty(self._buf.numel(), dtype=torch.uint8, pin_memory=True)
-                stream = torch.cuda.current_stream(dev)
-                with torch.cuda.device(dev):
-                    pinned.copy_(self._buf, non_blocking=True)
-                stream.synchronize()
-            self._pinned = pinned
-            host = pinned.numpy()
-            self._host = {name: self._view(name, host, np) for name in self._NAMES}
-        return self._host
-
-    def __len__(self):
-        return self.G
+    @staticmethod
+    def _host_result(a):
+        return a
 
 
 def validity(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Optional[torch.Tensor], rules: ValenceRules, *,
@@ -770,21 +775,11 @@ def validity(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Optional[torch.T
         raise RuntimeError(f"{what}: the rules were built with device=None and hold no device tables (no CPU fallback)")
     if rules.allowed_mask.device != dev:
         raise ValueError(f"{what}: the molecules are on {dev}, the rules' tables on {rules.allowed_mask.device}")
-    term_dtype = L.DTYPE_I8
-    if termination is not None:
-        if not isinstance(termination, torch.Tensor) or not termination.is_cuda or termination.device != dev:
-            raise RuntimeError(f"{what}: termination must be a CUDA tensor on {dev} (no CPU fallback)")
-        if tuple(termination.shape) != (G,):
-            raise ValueError(f"{what}: termination has shape {tuple(termination.shape)}, expected ({G},)")
-        if termination.dtype != torch.int8:
-            termination = termination.float()
-            term_dtype = L.DTYPE_F32
-        termination = termination.contiguous()
+    termination, term_dtype = _check_termination(what, termination, G, dev)
     if G == 0:                                               # no launch: the counts are zero
         return MoleculeValidity(torch.zeros(MoleculeValidity.nbytes(0, N), dtype=torch.uint8, device=dev), 0, N)
-    res = MoleculeValidity(torch.empty(MoleculeValidity.nbytes(G, N), dtype=torch.uint8, device=dev), G, N)
-    base = res._buf.data_ptr()
-    out = {name: base + off for name, (off, _, _, _) in MoleculeValidity.layout(G, N).items()}
+    res = MoleculeValidity.empty(dev, G, N)
+    out = res._ptrs()
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
         L.check(L.load().gi_mol_valence(

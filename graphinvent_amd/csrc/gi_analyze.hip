@@ -3,8 +3,8 @@
 // nodes [G, N, Fn] / edges [G, N, N, Fe] (fp32 or int8) and n_nodes [G], which the reference walks molecule by molecule,
 // node by node and bond by bond from Python with one device-to-host synchronisation per step.
 //
-// mol_props_kernel   workgroups stride over the graphs.  Per graph every byte is read once (load_piece: whole 16-byte
-//                    granules of the ADDRESS range, single elements at the ragged ends); non-zero entries go into LDS:
+// mol_props_kernel   workgroups stride over the graphs.  Per graph every byte is read once (gi_for_each_nonzero of
+//                    gi_molread.h, the reader of all the molecule kernels); the VALUE of a non-zero entry goes to LDS:
 //                    the column sums of the node rows, the per-node degree (all N columns, all bond types), the sum per
 //                    bond type, the non-zero-row mask.  Then the graph's n_nodes and its nodes' degrees are binned.  The
 //                    bins are int32 in LDS, flushed with one 64-bit atomicAdd per non-zero bin at the end (and every
@@ -18,68 +18,18 @@
 //                    totals in LDS (the order-preserving compaction of gi_eval.hip with several entries per thread).
 // Every loop is bounded by the dims whatever the data holds, every index is checked against its buffer.
 #include "gi_common.h"
+#include "gi_molread.h"
 
 namespace {
 
 typedef signed char i8;
 typedef unsigned long long u64;
 
-constexpr int NT = 256;
+constexpr int NT = GI_MOL_NT;
 constexpr int NW = NT / 64;
 constexpr int MAXN = GI_MAX_NODES;
 constexpr int MAXF = GI_ANALYZE_MAX_FN;
 constexpr int EB = GI_ANALYZE_EDGE_BINS;
-
-__device__ __forceinline__ bool is01(float x) { return x == 0.f || x == 1.f; }
-__device__ __forceinline__ bool is01(i8 x) { return x == 0 || x == 1; }
-
-__device__ __forceinline__ int load_count(const void* p, int bytes, long long g) {
-    return bytes == 1 ? (int)((const i8*)p)[g] : bytes == 4 ? ((const int*)p)[g] : (int)((const long long*)p)[g];
-}
-
-// 16-byte granules of the address range that p[0, len) occupies
-template <typename T>
-__device__ __forceinline__ int piece_count(const T* p, int len) {
-    constexpr int E = 16 / (int)sizeof(T);
-    return ((int)(((uintptr_t)p & 15) / sizeof(T)) + len + E - 1) / E;
-}
-
-// the elements of p[0, len) inside granule q: v[0, c) = p[o0, o0 + c), c returned.  A whole granule is one 16-byte
-// load, a ragged first or last one is read element by element: nothing outside p[0, len) is touched.
-template <typename T>
-__device__ __forceinline__ int load_piece(const T* p, int len, int q, int& o0, T (&v)[16 / sizeof(T)]) {
-    constexpr int E = 16 / (int)sizeof(T);
-    const int lo = q * E - (int)(((uintptr_t)p & 15) / sizeof(T));
-    const int a = max(lo, 0), b = min(lo + E, len);
-    o0 = a;
-    if (b - a == E) {
-        const uint4 w = *reinterpret_cast<const uint4*>(p + a);
-        __builtin_memcpy(v, &w, 16);
-    } else {
-#pragma unroll
-        for (int k = 0; k < E; ++k) v[k] = k < b - a ? p[a + k] : (T)0;
-    }
-    return b - a;
-}
-
-// f(offset, value as int) for every non-zero element of p[0, len)
-template <typename T, class F>
-__device__ __forceinline__ void for_each_nonzero(const T* p, int len, int tid, F f) {
-    constexpr int E = 16 / (int)sizeof(T);
-    const int P = piece_count(p, len);
-    for (int q = tid; q < P; q += NT) {
-        T v[E];
-        int o0;
-        const int c = load_piece(p, len, q, o0, v);
-        bool any = false;
-#pragma unroll
-        for (int k = 0; k < E; ++k) any |= v[k] != (T)0;       // (the padding of a ragged granule is zero)
-        if (!any) continue;                                    // molecules are mostly zeros
-#pragma unroll
-        for (int k = 0; k < E; ++k)
-            if (k < c && v[k] != (T)0) f(o0 + k, (int)v[k]);
-    }
-}
 
 // layout of the totals (u64) and of the fp32 results: [n_nodes_hist | node columns | n_edges_hist | edge features], then
 // totals: termination sum, finished workgroups; results: avg_n_nodes, avg_n_edges, fraction_properly_terminated
@@ -122,18 +72,18 @@ __global__ __launch_bounds__(NT) void mol_props_kernel(const T* __restrict__ nod
         for (int i = tid; i < MAXN; i += NT) deg[i] = 0;
         if (tid < 4) present[tid] = 0u;
         __syncthreads();
-        for_each_nonzero(nodes + (size_t)g * len_n, len_n, tid, [&](int o, int v) {
+        gi_for_each_nonzero(nodes + (size_t)g * len_n, len_n, tid, [&](int o, T x) {
             const int i = o / Fn;
-            atomicAdd(&col[o - i * Fn], v);
+            atomicAdd(&col[o - i * Fn], (int)x);
             atomicOr(&present[i >> 5], 1u << (i & 31));
         });
-        for_each_nonzero(edges + (size_t)g * len_e, len_e, tid, [&](int o, int v) {
-            const int e = o / Fe, i = e / N;
+        gi_for_each_nonzero(edges + (size_t)g * len_e, len_e, tid, [&](int o, T x) {
+            const int e = o / Fe, i = e / N, v = (int)x;
             atomicAdd(&deg[i], v);
             atomicAdd(&ef[o - e * Fe], v);
         });
         __syncthreads();
-        const int n = n_nodes ? load_count(n_nodes, nn_bytes, g)
+        const int n = n_nodes ? (int)gi_load_count(n_nodes, nn_bytes, g)   // narrowed: a count past int wraps
                               : __popc(present[0]) + __popc(present[1]) + __popc(present[2]) + __popc(present[3]);
         if (tid == 0) {
             if (n >= 0 && n <= N && n <= max_n) hn[n] += 1;
@@ -202,7 +152,7 @@ __global__ __launch_bounds__(NT) void mol_decode_kernel(const T* __restrict__ no
     const int len_n = N * Fn, len_e = N * N * Fe, S = segs.n;
     const T* nd = nodes + (size_t)g * len_n;
     const T* ed = edges + (size_t)g * len_e;
-    const int n = min(max(load_count(n_nodes, nn_bytes, g), 0), N);
+    const int n = min(max((int)gi_load_count(n_nodes, nn_bytes, g), 0), N);
     if (tid == 0) err_sh = 0;
     int err = 0;
 
@@ -216,7 +166,7 @@ __global__ __launch_bounds__(NT) void mol_decode_kernel(const T* __restrict__ no
         for (int f = 0; f < segs.size[s]; ++f) {
             const T x = row[f];
             if (x == (T)0) continue;
-            if (!is01(x)) err |= GI_MOL_VALUE;
+            if (!gi_is01(x)) err |= GI_MOL_VALUE;
             if (first < 0) first = f;
             ++count;
         }
@@ -225,7 +175,7 @@ __global__ __launch_bounds__(NT) void mol_decode_kernel(const T* __restrict__ no
     }
 
     // ---- bonds: ordered compaction of the upper triangle's non-zero entries ---------------------------------
-    const int P = piece_count(ed, len_e);
+    const int P = gi_granule_count(ed, len_e);
     short* out = bonds + (size_t)g * max_bonds * 3;
     int base = 0;                                               // bonds of the previous chunks
     for (int c0 = 0; c0 < P; c0 += NT) {                        // uniform
@@ -234,7 +184,7 @@ __global__ __launch_bounds__(NT) void mol_decode_kernel(const T* __restrict__ no
         int o0 = 0, c = 0;
         bool any = false;
         if (q < P) {
-            c = load_piece(ed, len_e, q, o0, v);
+            c = gi_load_granule(ed, len_e, q, o0, v);
 #pragma unroll
             for (int k = 0; k < E; ++k) any |= v[k] != (T)0;
         }
@@ -245,7 +195,7 @@ __global__ __launch_bounds__(NT) void mol_decode_kernel(const T* __restrict__ no
 #pragma unroll
             for (int k = 0; k < E; ++k) {
                 if (k < c && v[k] != (T)0) {
-                    if (!is01(v[k])) err |= GI_MOL_VALUE;
+                    if (!gi_is01(v[k])) err |= GI_MOL_VALUE;
                     if (i < j) {
                         mask |= 1u << k;
                         if (j >= n) err |= GI_MOL_BOND_PAST_N;
@@ -302,12 +252,10 @@ __global__ __launch_bounds__(NT) void mol_decode_kernel(const T* __restrict__ no
     }
 }
 
-int check_dims(int G, int N, int Fn, int Fe, int dtype, int nn_bytes) {
-    if (G < 0 || N < 1 || Fn < 1 || Fe < 1 || (dtype != GI_DTYPE_F32 && dtype != GI_DTYPE_I8) ||
-        (nn_bytes != 1 && nn_bytes != 4 && nn_bytes != 8) || N > GI_MAX_NODES || Fe > GI_MAX_GROUPS)
-        return GI_EINVAL;
-    if (Fn > GI_ANALYZE_MAX_FN) return GI_ELIMIT;
-    return 0;
+// any EINVAL comes before the Fn limit
+int check_args(int G, int N, int Fn, int Fe, int dtype, int nn_bytes) {
+    if (const int rc = gi_mol_check_types(dtype, nn_bytes)) return rc;
+    return gi_mol_check_dims(G, N, Fn, Fe);
 }
 
 }  // namespace
@@ -316,7 +264,7 @@ extern "C" int gi_mol_properties(int G, int N, int Fn, int Fe, const void* nodes
                                  const void* n_nodes, int n_nodes_bytes, const void* termination, int term_dtype,
                                  int max_n_nodes, unsigned long long* totals, float* out, void* stream) {
     (void)hipGetLastError();
-    if (const int rc = check_dims(G, N, Fn, Fe, dtype, n_nodes_bytes)) return rc;
+    if (const int rc = check_args(G, N, Fn, Fe, dtype, n_nodes_bytes)) return rc;
     if (max_n_nodes < 0 || max_n_nodes > GI_ANALYZE_MAX_HIST) return GI_EINVAL;
     if (termination && term_dtype != GI_DTYPE_F32 && term_dtype != GI_DTYPE_I8) return GI_EINVAL;
     if (G == 0) return 0;
@@ -339,7 +287,7 @@ extern "C" int gi_mol_decode(int G, int N, int Fn, int Fe, const void* nodes, co
                              const void* n_nodes, int n_nodes_bytes, int n_seg, const int* seg, int max_bonds,
                              signed char* atoms, short* bonds, int* n_bonds, int* status, void* stream) {
     (void)hipGetLastError();
-    if (const int rc = check_dims(G, N, Fn, Fe, dtype, n_nodes_bytes)) return rc;
+    if (const int rc = check_args(G, N, Fn, Fe, dtype, n_nodes_bytes)) return rc;
     if (n_seg < 2 || n_seg > 4 || !seg || max_bonds < 1 || max_bonds > (1 << 20)) return GI_EINVAL;
     Segs segs;
     segs.n = n_seg;

@@ -7,9 +7,9 @@
 // mol_canon_kernel   one 256-lane WORKGROUP per molecule (not one wave: a molecule is up to 128 x 128 x 8 entries, and
 //                    reading it is what takes the time; the refinement rounds are short and use the workgroup barrier,
 //                    the same code for every n).
-//   1  all waves read the molecule once (whole 16-byte granules of the address range, single elements at the ragged
-//      ends; fp32 or int8), check it and build in LDS one 128-bit adjacency row per (bond type, node) and one bit row
-//      per node's feature row (feature f at bit 31 - f % 32 of word f / 32, so that comparing the words as unsigned
+//   1  all waves read the molecule once (gi_for_each_nonzero of gi_molread.h; fp32 or int8), check it
+//      (gi_mol_structure, shared with gi_valence.hip) and build in LDS one 128-bit adjacency row per (bond type,
+//      node) and one bit row per node's feature row (feature f at bit 31 - f % 32 of word f / 32, so that comparing the words as unsigned
 //      numbers compares the rows as byte strings);
 //   2  initial colour = the rank of the feature row among the molecule's n rows; one thread per node;
 //   3  rounds: h_i = sum over (t, j) with bond t between i and j of mix64(t << 32 | col_j) (commutative, so the order
@@ -18,7 +18,8 @@
 //      non-singleton cell of smallest colour r the member of lowest input index keeps r, the others get r + 1 (free,
 //      because a cell of size s owns the ranks r .. r + s - 1);
 //   4  order = nodes by ascending colour; the key: two independent 64-bit sums of per-set-entry terms of the canonical
-//      molecule with n mixed in; the canonical molecule is stored in 16-byte pieces between its ragged ends.
+//      molecule with n mixed in; the canonical molecule is stored in 16-byte pieces between its ragged ends
+//      (store_bytes of gi_molread.h).
 // LDS: Fe N 16 B of adjacency (<= 16 KB) + N ceil(Fn / 32) 4 B of feature bits (<= 8 KB) dynamic, ~3 KB static.
 // Every loop is bounded by the dims whatever the data holds: every round raises the cell count or individualises, both
 // at most n - 1 times, and the loop is cut at 2 N + 2 rounds regardless; colours stay below n, every index below N.
@@ -47,52 +48,8 @@ constexpr int MAXN = GI_MAX_NODES;
 constexpr unsigned EMPTY = 0xFFFFFFFFu;
 constexpr int NO_TARGET = 0x7fffffff;
 
-__device__ __forceinline__ u64 mix64(u64 x) {               // splitmix64 finaliser (as in gi_route.hip)
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 __device__ __forceinline__ u64 tagged(int tag, u64 x) { return mix64(((u64)tag << 40) | x); }
 __device__ __forceinline__ u64 nonzero_word(u64 x) { return x ? x : 1ull; }
-
-// bytes [0, len) at `p`, a [D0, D1, D2] array, written in 16-byte pieces between the ragged ends of the address range
-// (as store_bytes of gi_reorder.hip): src(a, b) names the source of the D2 bytes of pair (a, b) (negative: zeros) and
-// is evaluated once per pair and piece, val(s, t) is byte t of source s
-template <class S, class V>
-__device__ __forceinline__ void store_bytes(i8* p, int len, int tid, int D0, int D1, int D2, S src, V val) {
-    const int head = min(len, (int)((16 - ((uintptr_t)p & 15)) & 15));
-    const int pieces = (len - head) >> 4, tail0 = head + (pieces << 4);
-    auto one = [&](int o) {
-        const int e = o / D2, a = e / D1, s = src(a, e - a * D1);
-        p[o] = (i8)(s < 0 ? 0 : val(s, o - e * D2));
-    };
-    for (int o = tid; o < head; o += NT) one(o);
-    for (int o = tail0 + tid; o < len; o += NT) one(o);
-    for (int q = tid; q < pieces; q += NT) {
-        const int o = head + (q << 4);
-        const int e = o / D2;
-        int t = o - e * D2, a = e / D1, b = e - a * D1;
-        int s = src(a, b);
-        unsigned w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            if (s >= 0) w[k >> 2] |= (unsigned)(val(s, t) & 0xff) << ((k & 3) * 8);
-            if (++t == D2) {
-                t = 0;
-                if (++b == D1) { b = 0; ++a; }
-                s = a < D0 ? src(a, b) : -1;                 // a == D0: the piece ends with the array
-            }
-        }
-        *reinterpret_cast<uint4*>(p + o) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-}
-
-__device__ __forceinline__ u64 wave_sum64(u64 x) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) x += (u64)__shfl_xor((long long)x, s);
-    return x;
-}
 
 template <typename T>
 __global__ __launch_bounds__(NT) void mol_canon_kernel(const T* __restrict__ nodes, const T* __restrict__ edges,
@@ -122,42 +79,19 @@ __global__ __launch_bounds__(NT) void mol_canon_kernel(const T* __restrict__ nod
 
     // ---- 1: read and check -------------------------------------------------------------------------------
     int err = 0;
-    gi_for_each_nonzero(nd, len_n, tid, [&](int o, bool ok) {
-        if (!ok) err |= GI_MOL_VALUE;
+    gi_for_each_nonzero(nd, len_n, tid, [&](int o, T x) {
+        if (!gi_is01(x)) err |= GI_MOL_VALUE;
         const int i = o / Fn, f = o - i * Fn;
         atomicOr(&nbits[i * W + (f >> 5)], 1u << (31 - (f & 31)));
         atomicOr(&present[i >> 5], 1u << (i & 31));
     });
-    gi_for_each_nonzero(ed, len_e, tid, [&](int o, bool ok) {
-        if (!ok) err |= GI_MOL_VALUE;
+    gi_for_each_nonzero(ed, len_e, tid, [&](int o, T x) {
+        if (!gi_is01(x)) err |= GI_MOL_VALUE;
         const int e = o / Fe, t = o - e * Fe, i = e / N, j = e - i * N;
         atomicOr(&adj[(t * N + i) * 4 + (j >> 5)], 1u << (j & 31));
     });
     __syncthreads();
-    int n;
-    if (n_nodes) {
-        const long long c = gi_load_count(n_nodes, nn_bytes, g);
-        if (c < 0 || c > N) err |= GI_MOL_NODE_PAST_N;
-        n = (int)(c < 0 ? 0 : c > N ? N : c);
-    } else {                                                 // the leading rows with a set entry
-        n = 0;
-        while (n < 4 && present[n] == ~0u) ++n;
-        n = n == 4 ? 128 : 32 * n + __builtin_ctz(~present[n]);
-    }
-    if (tid < 4 && (present[tid] & ~gi_below_word(n, tid))) err |= GI_MOL_NODE_PAST_N;
-    for (int idx = tid; idx < Fe * N; idx += NT) {           // row (t, i): inside n, and mirrored
-        const int t = idx / N, i = idx - t * N;
-        for (int w = 0; w < 4; ++w) {
-            unsigned bits = adj[idx * 4 + w];
-            if (bits == 0) continue;
-            if (i >= n || (bits & ~gi_below_word(n, w))) err |= GI_MOL_BOND_PAST_N;
-            while (bits) {
-                const int b = __builtin_ctz(bits), j = 32 * w + b;         // j < N: it came from an offset < N N Fe
-                bits &= bits - 1;
-                if (!((adj[(t * N + j) * 4 + (i >> 5)] >> (i & 31)) & 1u)) err |= GI_MOL_ASYMMETRIC;
-            }
-        }
-    }
+    const int n = gi_mol_structure(adj, present, n_nodes, nn_bytes, g, N, Fe, tid, err);
     if (err) atomicOr(&err_sh, err);
     __syncthreads();
     const int status = err_sh;                               // uniform; not written again
@@ -402,22 +336,14 @@ UniqueWs unique_layout(int G) {
 
 constexpr int MAX_UNIQUE = 1 << 29;                          // 2 G must fit the 32-bit table index
 
-int check_dims(int G, int N, int Fn, int Fe) {
-    if (G < 0 || N < 1 || Fn < 1 || Fe < 1 || N > GI_MAX_NODES || Fe > GI_MAX_GROUPS) return GI_EINVAL;
-    if (Fn > GI_ANALYZE_MAX_FN) return GI_ELIMIT;
-    return 0;
-}
-
 }  // namespace
 
 extern "C" int gi_mol_canon(int G, int N, int Fn, int Fe, const void* nodes, const void* edges, int dtype,
                             const void* n_nodes, int n_nodes_bytes, int* order, int* rank, unsigned long long* key,
                             int* status, signed char* out_nodes, signed char* out_edges, void* stream) {
     (void)hipGetLastError();
-    if (const int rc = check_dims(G, N, Fn, Fe)) return rc;
-    if ((dtype != GI_DTYPE_F32 && dtype != GI_DTYPE_I8) ||
-        (n_nodes_bytes != 1 && n_nodes_bytes != 4 && n_nodes_bytes != 8))
-        return GI_EINVAL;
+    if (const int rc = gi_mol_check_dims(G, N, Fn, Fe)) return rc;
+    if (const int rc = gi_mol_check_types(dtype, n_nodes_bytes)) return rc;
     if (G == 0) return 0;
     if (!nodes || !edges || !order || !rank || !key || !status) return GI_EINVAL;
     if ((const void*)out_nodes == nodes || (const void*)out_edges == edges) return GI_EINVAL;      // not in place
@@ -443,7 +369,7 @@ extern "C" int gi_mol_unique(int G, int N, int Fn, int Fe, const unsigned long l
                              const signed char* canon_nodes, const signed char* canon_edges, const int* status,
                              const signed char* mask, void* ws, int* rep, float* unique, int* counts, void* stream) {
     (void)hipGetLastError();
-    if (const int rc = check_dims(G, N, Fn, Fe)) return rc;
+    if (const int rc = gi_mol_check_dims(G, N, Fn, Fe)) return rc;
     if (G > MAX_UNIQUE) return GI_ELIMIT;
     if (!counts) return GI_EINVAL;
     const hipStream_t st = (hipStream_t)stream;

@@ -1,10 +1,34 @@
-// The molecule reader shared by gi_canon.hip and gi_valence.hip (one 256-lane workgroup per molecule): every byte of a
-// [G, N, Fn] / [G, N, N, Fe] tensor of fp32 or int8 is read once, in 16-byte pieces between ragged ends, at any element
-// alignment.  (gi_analyze.hip keeps a reader of its own: it hands the VALUE of every entry to its statistics.)
+// Molecule I/O of the kernels that take a whole molecule (nodes [G, N, Fn] / edges [G, N, N, Fe], fp32 or int8), one
+// 256-lane workgroup per molecule: gi_analyze.hip, gi_canon.hip, gi_valence.hip, gi_reorder.hip (and the hash and
+// wave helpers of gi_route.hip).  Here, once each:
+//   the granule reader   every byte of p[0, len) is read once, at any element alignment: whole 16-byte granules of the
+//                        ADDRESS range in one load, a ragged first or last granule element by element, nothing outside
+//                        p[0, len) touched (gi_granule_count / gi_load_granule, gi_for_each_nonzero on top of them);
+//   store_bytes          the same split for writing an int8 [D0, D1, D2] array;
+//   gi_mol_structure     n (given or derived) and the GI_MOL_* structure bits from the adjacency rows in LDS;
+//   mix64, the wave reductions, gi_is01, gi_load_count, gi_below_word, and the host-side argument checks.
 #pragma once
 #include "gi_common.h"
 
 constexpr int GI_MOL_NT = 256;                               // lanes of a workgroup that reads a molecule
+
+__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {      // splitmix64 finaliser
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
+__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long x) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) x += (unsigned long long)__shfl_xor((long long)x, s);
+    return x;
+}
+__device__ __forceinline__ int wave_max(int x) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) x = max(x, __shfl_xor(x, s));
+    return x;
+}
 
 __device__ __forceinline__ bool gi_is01(float x) { return x == 0.f || x == 1.f; }
 __device__ __forceinline__ bool gi_is01(signed char x) { return x == 0 || x == 1; }
@@ -14,33 +38,131 @@ __device__ __forceinline__ long long gi_load_count(const void* p, int bytes, lon
                                                                            : ((const long long*)p)[g];
 }
 
-// f(offset, is the value 1) for every non-zero element of p[0, len): whole 16-byte granules of the ADDRESS range are one
-// load each, a ragged first or last granule is read element by element; nothing outside p[0, len) is touched
-template <typename T, class F>
-__device__ __forceinline__ void gi_for_each_nonzero(const T* p, int len, int tid, F f) {
-    constexpr int E = 16 / (int)sizeof(T);
-    const int shift = (int)(((uintptr_t)p & 15) / sizeof(T));
-    const int P = (shift + len + E - 1) / E;
-    for (int q = tid; q < P; q += GI_MOL_NT) {
-        const int lo = q * E - shift;
-        const int a = max(lo, 0), b = min(lo + E, len);
-        T v[E];
-        if (b - a == E) {
-            const uint4 w = *reinterpret_cast<const uint4*>(p + a);
-            if ((w.x | w.y | w.z | w.w) == 0) continue;     // molecules are mostly zeros (+0.f is all zero bits)
-            __builtin_memcpy(v, &w, 16);
-        } else {
-#pragma unroll
-            for (int k = 0; k < E; ++k) v[k] = k < b - a ? p[a + k] : (T)0;
-        }
-#pragma unroll
-        for (int k = 0; k < E; ++k)
-            if (k < b - a && !(v[k] == (T)0)) f(a + k, gi_is01(v[k]));
-    }
-}
-
 // bits [0, k) set, 0 <= k <= 128, as four 32-bit words
 __device__ __forceinline__ unsigned gi_below_word(int k, int w) {
     const int r = k - 32 * w;
     return r <= 0 ? 0u : r >= 32 ? ~0u : (1u << r) - 1u;
+}
+
+// 16-byte granules of the address range that p[0, len) occupies
+template <typename T>
+__device__ __forceinline__ int gi_granule_count(const T* p, int len) {
+    constexpr int E = 16 / (int)sizeof(T);
+    return ((int)(((uintptr_t)p & 15) / sizeof(T)) + len + E - 1) / E;
+}
+
+// the elements of p[0, len) inside granule q: v[0, c) = p[o0, o0 + c), v[c, E) = 0, c returned.  A whole granule is one
+// 16-byte load, a ragged first or last one is read element by element: nothing outside p[0, len) is touched.
+template <typename T>
+__device__ __forceinline__ int gi_load_granule(const T* p, int len, int q, int& o0, T (&v)[16 / sizeof(T)]) {
+    constexpr int E = 16 / (int)sizeof(T);
+    const int lo = q * E - (int)(((uintptr_t)p & 15) / sizeof(T));
+    const int a = max(lo, 0), b = min(lo + E, len);
+    o0 = a;
+    if (b - a == E) {
+        const uint4 w = *reinterpret_cast<const uint4*>(p + a);
+        __builtin_memcpy(v, &w, 16);
+    } else {
+#pragma unroll
+        for (int k = 0; k < E; ++k) v[k] = k < b - a ? p[a + k] : (T)0;
+    }
+    return b - a;
+}
+
+// f(offset, value) for every non-zero element of p[0, len), the workgroup's lanes striding over the granules
+template <typename T, class F>
+__device__ __forceinline__ void gi_for_each_nonzero(const T* p, int len, int tid, F f) {
+    constexpr int E = 16 / (int)sizeof(T);
+    const int P = gi_granule_count(p, len);
+    for (int q = tid; q < P; q += GI_MOL_NT) {
+        T v[E];
+        int o0;
+        const int c = gi_load_granule(p, len, q, o0, v);
+        uint4 w;
+        __builtin_memcpy(&w, v, 16);
+        if ((w.x | w.y | w.z | w.w) == 0) continue;         // molecules are mostly zeros (+0.f is all zero bits)
+#pragma unroll
+        for (int k = 0; k < E; ++k)
+            if (k < c && !(v[k] == (T)0)) f(o0 + k, v[k]);
+    }
+}
+
+// bytes [0, len) at `p`, a [D0, D1, D2] array, written in 16-byte pieces between the ragged ends of the address range:
+// src(a, b) names the source of the D2 bytes of pair (a, b) (negative: zeros) and is evaluated once per pair and piece,
+// val(s, t) is byte t of source s
+template <class S, class V>
+__device__ __forceinline__ void store_bytes(signed char* p, int len, int tid, int D0, int D1, int D2, S src, V val) {
+    const int head = min(len, (int)((16 - ((uintptr_t)p & 15)) & 15));
+    const int pieces = (len - head) >> 4, tail0 = head + (pieces << 4);
+    auto one = [&](int o) {
+        const int e = o / D2, a = e / D1, s = src(a, e - a * D1);
+        p[o] = (signed char)(s < 0 ? 0 : val(s, o - e * D2));
+    };
+    for (int o = tid; o < head; o += GI_MOL_NT) one(o);
+    for (int o = tail0 + tid; o < len; o += GI_MOL_NT) one(o);
+    for (int q = tid; q < pieces; q += GI_MOL_NT) {
+        const int o = head + (q << 4);
+        const int e = o / D2;
+        int t = o - e * D2, a = e / D1, b = e - a * D1;
+        int s = src(a, b);
+        unsigned w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            if (s >= 0) w[k >> 2] |= (unsigned)(val(s, t) & 0xff) << ((k & 3) * 8);
+            if (++t == D2) {
+                t = 0;
+                if (++b == D1) { b = 0; ++a; }
+                s = a < D0 ? src(a, b) : -1;                 // a == D0: the piece ends with the array
+            }
+        }
+        *reinterpret_cast<uint4*>(p + o) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+}
+
+// The structure check of a molecule whose rows are complete in LDS (call it behind the barrier that ends the reading):
+// adj [Fe][N][4], bit j of row (t, i) = bond t between i and j; present, bit i = node row i has a set entry.  Returns
+// n: n_nodes[g] clamped to [0, N], or without n_nodes the number of LEADING rows with a set entry.  ORs into `err`
+// GI_MOL_NODE_PAST_N (n_nodes[g] outside [0, N], or a set entry in a row >= n), GI_MOL_BOND_PAST_N (a bond that touches
+// a node >= n) and GI_MOL_ASYMMETRIC (bond t from i to j without its mirror image), each in some lane of the workgroup.
+__device__ __forceinline__ int gi_mol_structure(const unsigned* adj, const unsigned* present, const void* n_nodes,
+                                                int nn_bytes, int g, int N, int Fe, int tid, int& err) {
+    int n;
+    if (n_nodes) {
+        const long long c = gi_load_count(n_nodes, nn_bytes, g);
+        if (c < 0 || c > N) err |= GI_MOL_NODE_PAST_N;
+        n = (int)(c < 0 ? 0 : c > N ? N : c);
+    } else {
+        n = 0;
+        while (n < 4 && present[n] == ~0u) ++n;
+        n = n == 4 ? 128 : 32 * n + __builtin_ctz(~present[n]);
+    }
+    if (tid < 4 && (present[tid] & ~gi_below_word(n, tid))) err |= GI_MOL_NODE_PAST_N;
+    for (int idx = tid; idx < Fe * N; idx += GI_MOL_NT) {    // row (t, i): inside n, and mirrored
+        const int t = idx / N, i = idx - t * N;
+        for (int w = 0; w < 4; ++w) {
+            unsigned bits = adj[idx * 4 + w];
+            if (bits == 0) continue;
+            if (i >= n || (bits & ~gi_below_word(n, w))) err |= GI_MOL_BOND_PAST_N;
+            while (bits) {
+                const int b = __builtin_ctz(bits), j = 32 * w + b;         // j < N: it came from an offset < N N Fe
+                bits &= bits - 1;
+                if (!((adj[(t * N + j) * 4 + (i >> 5)] >> (i & 31)) & 1u)) err |= GI_MOL_ASYMMETRIC;
+            }
+        }
+    }
+    return n;
+}
+
+// The argument checks common to the gi_mol_* entry points, in two parts because the entry points order them
+// differently and the first that fires decides the code: the dims and limits ...
+static inline int gi_mol_check_dims(int G, int N, int Fn, int Fe) {
+    if (G < 0 || N < 1 || Fn < 1 || Fe < 1 || N > GI_MAX_NODES || Fe > GI_MAX_GROUPS) return GI_EINVAL;
+    if (Fn > GI_ANALYZE_MAX_FN) return GI_ELIMIT;
+    return 0;
+}
+// ... and the molecules' dtype and the width of an n_nodes entry
+static inline int gi_mol_check_types(int dtype, int nn_bytes) {
+    if ((dtype != GI_DTYPE_F32 && dtype != GI_DTYPE_I8) || (nn_bytes != 1 && nn_bytes != 4 && nn_bytes != 8))
+        return GI_EINVAL;
+    return 0;
 }

@@ -4,8 +4,9 @@
 // loader can draw a fresh decoding route per molecule per epoch in front of gi_route_plan / gi_route_expand.
 //
 // route_reorder_kernel, one 256-lane workgroup per molecule:
-//   1  all waves read the molecule (16-byte pieces where the address allows, bytes at the ragged ends), check it and
-//      build the adjacency ("any bond type set") as N bit rows of 128 bits in LDS;
+//   1  all waves read the molecule (gi_for_each_nonzero of gi_molread.h: 16-byte granules where the address allows,
+//      bytes at the ragged ends), check it and build the adjacency ("any bond type set") as N bit rows of 128 bits
+//      in LDS;
 //   2  the ranking: the caller's (checked to be a permutation of 0..n-1) or drawn from (seed, epoch, molecule id):
 //      key_i = mix64(s ^ (id << 8 | i)), rank_i = #{j : (key_j, j) < (key_i, i)};
 //   3  wave 0 searches with `visited` and the frontier as wave-uniform 128-bit masks.
@@ -18,26 +19,20 @@
 //      `visited` only grows, so a position found without candidates stays so: a mask of the still-live positions
 //      lets the backward step jump to the next live one instead of re-testing the dead ones;
 //   4  all waves gather nodes' = nodes[order], edges' = edges[order][:, order] (zero padded) and store them, again in
-//      16-byte pieces between the ragged ends of the molecule's byte range.
+//      16-byte pieces between the ragged ends of the molecule's byte range (store_bytes of gi_molread.h).
 // Every loop is bounded by the dims whatever the data holds: BFS runs at most N levels, DFS at most 2 N steps (each
 // step appends a node or retires a position), every index is < N.  A molecule that fails a check is copied through
 // unchanged with its GI_ROUTE_ERR_* bits in mol_err[m] and the identity in order[m].
 #include "gi_common.h"
+#include "gi_molread.h"
 
 namespace {
 
 typedef signed char i8;
 typedef unsigned long long u64;
 
-constexpr int NT = 256;
+constexpr int NT = GI_MOL_NT;
 constexpr int MAXN = GI_MAX_NODES;                          // 128: a bit row is two 64-bit words
-
-__device__ __forceinline__ u64 mix64(u64 x) {               // splitmix64 finaliser (as in gi_route.hip)
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 
 struct Mask {                                               // 128 bits
     u64 lo, hi;
@@ -68,63 +63,6 @@ __device__ __forceinline__ Mask wave_or(Mask x) {
     }
     return x;
 }
-__device__ __forceinline__ int wave_max(int x) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) x = max(x, __shfl_xor(x, s));
-    return x;
-}
-
-// bytes [0, len) at `p`, visited as f(offset, value): single bytes up to the first 16-byte boundary of the ADDRESS and
-// after the last one, whole uint4 loads between
-template <class F>
-__device__ __forceinline__ void for_each_byte(const i8* p, int len, int tid, F f) {
-    const int head = min(len, (int)((16 - ((uintptr_t)p & 15)) & 15));
-    const int pieces = (len - head) >> 4, tail0 = head + (pieces << 4);
-    for (int o = tid; o < head; o += NT) f(o, (int)p[o]);
-    for (int o = tail0 + tid; o < len; o += NT) f(o, (int)p[o]);
-    for (int q = tid; q < pieces; q += NT) {
-        const int o = head + (q << 4);
-        const uint4 v = *reinterpret_cast<const uint4*>(p + o);
-        const unsigned w[4] = {v.x, v.y, v.z, v.w};
-        if ((w[0] | w[1] | w[2] | w[3]) == 0) continue;      // molecules are mostly zeros
-#pragma unroll
-        for (int b = 0; b < 16; ++b) {
-            const int x = (int)(i8)((w[b >> 2] >> ((b & 3) * 8)) & 0xff);
-            if (x) f(o + b, x);
-        }
-    }
-}
-
-// bytes [0, len) at `p`, a [D0, D1, D2] array, written with the same split: src(a, b) names the source of the D2 bytes
-// of pair (a, b) (negative: zeros) and is evaluated once per pair and piece, val(s, t) reads byte t of source s
-template <class S, class V>
-__device__ __forceinline__ void store_bytes(i8* p, int len, int tid, int D0, int D1, int D2, S src, V val) {
-    const int head = min(len, (int)((16 - ((uintptr_t)p & 15)) & 15));
-    const int pieces = (len - head) >> 4, tail0 = head + (pieces << 4);
-    auto one = [&](int o) {
-        const int e = o / D2, a = e / D1, s = src(a, e - a * D1);
-        p[o] = (i8)(s < 0 ? 0 : val(s, o - e * D2));
-    };
-    for (int o = tid; o < head; o += NT) one(o);
-    for (int o = tail0 + tid; o < len; o += NT) one(o);
-    for (int q = tid; q < pieces; q += NT) {
-        const int o = head + (q << 4);
-        const int e = o / D2;
-        int t = o - e * D2, a = e / D1, b = e - a * D1;
-        int s = src(a, b);
-        unsigned w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            if (s >= 0) w[k >> 2] |= (unsigned)(val(s, t) & 0xff) << ((k & 3) * 8);
-            if (++t == D2) {
-                t = 0;
-                if (++b == D1) { b = 0; ++a; }
-                s = a < D0 ? src(a, b) : -1;                 // a == D0: the piece ends with the array
-            }
-        }
-        *reinterpret_cast<uint4*>(p + o) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-}
 
 template <int MODE>                                         // GI_ROUTE_BFS / GI_ROUTE_DFS
 __global__ __launch_bounds__(NT) void route_reorder_kernel(const i8* __restrict__ nodes, const i8* __restrict__ edges,
@@ -148,14 +86,12 @@ __global__ __launch_bounds__(NT) void route_reorder_kernel(const i8* __restrict_
 
     // ---- 1: read and check -------------------------------------------------------------------------------
     int err = 0;
-    for_each_byte(nd, len_n, tid, [&](int o, int v) {
-        if (v == 0) return;
+    gi_for_each_nonzero(nd, len_n, tid, [&](int o, i8 v) {
         if (v != 1) err |= GI_ROUTE_ERR_VALUE;
         const int i = o / Fn;
         atomicOr(&present[i >> 5], 1u << (i & 31));
     });
-    for_each_byte(ed, len_e, tid, [&](int o, int v) {
-        if (v == 0) return;
+    gi_for_each_nonzero(ed, len_e, tid, [&](int o, i8 v) {
         if (v != 1) err |= GI_ROUTE_ERR_VALUE;
         const int e = o / Fe, t = o - e * Fe, i = e / N, j = e - i * N;
         if (ed[((size_t)j * N + i) * Fe + t] != v) err |= GI_ROUTE_ERR_ASYMMETRIC;   // every mismatch has a set side

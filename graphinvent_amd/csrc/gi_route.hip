@@ -25,7 +25,9 @@
 // compare, its surviving row is the minimum row index, its position comes from an ordered scan, and the APD sums are
 // sums of ones (exact in int8 up to 127 and in fp32 up to 2^24, whatever the order).
 // Invalid molecules get route length 0 and error bits; every index is bounded by the dims, whatever the data holds.
+// mix64 and the wave reductions are gi_molread.h's.
 #include "gi_common.h"
+#include "gi_molread.h"
 
 namespace {
 
@@ -39,13 +41,6 @@ constexpr unsigned EMPTY = 0xFFFFFFFFu;
 constexpr u64 EDGE_SALT = 0x9E3779B97F4A7C15ull;
 
 struct Segs { int n; int size[4]; int prod; };
-
-__device__ __forceinline__ u64 mix64(u64 x) {               // splitmix64 finaliser
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 
 __host__ __device__ __forceinline__ size_t r16(size_t x) { return (x + 15) & ~(size_t)15; }
 
@@ -183,17 +178,6 @@ __global__ __launch_bounds__(SCAN_NT) void route_scan_kernel(const int* __restri
         for (int w = 0; w < NW; ++w) base += wsum[w];
     }
     if (tid == 0) { out[n] = base; *total = base; }
-}
-
-__device__ __forceinline__ u64 wave_sum64(u64 x) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) x += (u64)__shfl_xor((long long)x, s);
-    return x;
-}
-__device__ __forceinline__ int wave_max(int x) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) x = max(x, __shfl_xor(x, s));
-    return x;
 }
 
 __global__ __launch_bounds__(256) void route_rows_kernel(const i8* __restrict__ nodes, int M, int N, int Fn, int Fe,

@@ -4,13 +4,13 @@
 // VALENCE TEST OF THE LABELLED GRAPH: no kekulisation, no aromaticity perception; the table of allowed valences is the
 // caller's (analyze.ValenceRules), not RDKit's.
 //
-// mol_valence_kernel  one 256-lane WORKGROUP per molecule, the skeleton of mol_canon_kernel (gi_canon.hip):
-//   1  all waves read the molecule once (whole 16-byte granules of the address range, single elements at the ragged
-//      ends; fp32 or int8) and check it while they read; in LDS one 128-bit adjacency row per (bond type, node), and per
-//      node and segment (atom type, formal charge, implicit H) the number of set entries and the lowest of them;
+// mol_valence_kernel  one 256-lane WORKGROUP per molecule:
+//   1  all waves read the molecule once (gi_for_each_nonzero of gi_molread.h; fp32 or int8) and check it while they
+//      read; in LDS one 128-bit adjacency row per (bond type, node), and per node and segment (atom type, formal
+//      charge, implicit H) the number of set entries and the lowest of them;
 //   2  n (given, or the leading rows with a set entry) and the well-formedness bits: GI_MOL_VALUE, _NODE_PAST_N,
-//      _BOND_PAST_N, _ASYMMETRIC, _ONEHOT, _MULTI_BOND (any of them: the molecule is malformed and nothing below is
-//      evaluated), GI_VAL_SELF_LOOP, GI_VAL_EMPTY;
+//      _BOND_PAST_N, _ASYMMETRIC (gi_mol_structure, shared with gi_canon.hip), _ONEHOT, _MULTI_BOND (any of them:
+//      the molecule is malformed and nothing below is evaluated), GI_VAL_SELF_LOOP, GI_VAL_EMPTY;
 //   3  one thread per atom: o2 = sum over bond types of order2[t] * popcount(row (t, i)), x = ceil(o2 / 2), v* = the lowest
 //      allowed valence >= x of (atom type, charge), fill = v* - x; no v*: the atom is over its valence;
 //   4  components by frontier expansion over the OR of the rows; at most N rounds whatever the data holds;
@@ -76,8 +76,8 @@ __global__ __launch_bounds__(NT) void mol_valence_kernel(const T* __restrict__ n
 
     // ---- 1: read and check -------------------------------------------------------------------------------
     int flags = 0;
-    gi_for_each_nonzero(nd, len_n, tid, [&](int o, bool ok) {
-        if (!ok) flags |= GI_MOL_VALUE;
+    gi_for_each_nonzero(nd, len_n, tid, [&](int o, T v) {
+        if (!gi_is01(v)) flags |= GI_MOL_VALUE;
         const int i = o / Fn, f = o - i * Fn;                // i < N
         atomicOr(&present[i >> 5], 1u << (i & 31));
         if (f < o_x) {                                       // a chirality segment (f >= o_x) is not looked at
@@ -86,8 +86,8 @@ __global__ __launch_bounds__(NT) void mol_valence_kernel(const T* __restrict__ n
             atomicMin(&seg_first[s][i], f - (s == 0 ? 0 : s == 1 ? o_c : o_h));
         }
     });
-    gi_for_each_nonzero(ed, len_e, tid, [&](int o, bool ok) {
-        if (!ok) flags |= GI_MOL_VALUE;
+    gi_for_each_nonzero(ed, len_e, tid, [&](int o, T v) {
+        if (!gi_is01(v)) flags |= GI_MOL_VALUE;
         const int e = o / Fe, t = o - e * Fe, i = e / N, j = e - i * N;
         if (i == j) flags |= GI_VAL_SELF_LOOP;
         atomicOr(&adj[(t * N + i) * 4 + (j >> 5)], 1u << (j & 31));
@@ -95,30 +95,7 @@ __global__ __launch_bounds__(NT) void mol_valence_kernel(const T* __restrict__ n
     __syncthreads();
 
     // ---- 2: n and the well-formedness bits ---------------------------------------------------------------
-    int n;
-    if (n_nodes) {
-        const long long c = gi_load_count(n_nodes, nn_bytes, g);
-        if (c < 0 || c > N) flags |= GI_MOL_NODE_PAST_N;
-        n = (int)(c < 0 ? 0 : c > N ? N : c);
-    } else {                                                 // the leading rows with a set entry
-        n = 0;
-        while (n < 4 && present[n] == ~0u) ++n;
-        n = n == 4 ? 128 : 32 * n + __builtin_ctz(~present[n]);
-    }
-    if (tid < 4 && (present[tid] & ~gi_below_word(n, tid))) flags |= GI_MOL_NODE_PAST_N;
-    for (int idx = tid; idx < Fe * N; idx += NT) {           // row (t, i): inside n, and mirrored
-        const int t = idx / N, i = idx - t * N;
-        for (int w = 0; w < 4; ++w) {
-            unsigned bits = adj[idx * 4 + w];
-            if (bits == 0) continue;
-            if (i >= n || (bits & ~gi_below_word(n, w))) flags |= GI_MOL_BOND_PAST_N;
-            while (bits) {
-                const int b = __builtin_ctz(bits), j = 32 * w + b;         // j < N: it came from an offset < N N Fe
-                bits &= bits - 1;
-                if (!((adj[(t * N + j) * 4 + (i >> 5)] >> (i & 31)) & 1u)) flags |= GI_MOL_ASYMMETRIC;
-            }
-        }
-    }
+    const int n = gi_mol_structure(adj, present, n_nodes, nn_bytes, g, N, Fe, tid, flags);
     bool arom = false;
     if (tid < N) {                                           // this thread's node: OR of its rows, several types on a pair
         unsigned seen[4] = {0u, 0u, 0u, 0u};
@@ -253,12 +230,9 @@ extern "C" int gi_mol_valence(int G, int N, int Fn, int Fe, const void* nodes, c
                               signed char* atom_valence, signed char* atom_h, int* desc, int* counts, int* scratch,
                               void* stream) {
     (void)hipGetLastError();
-    if (G < 0 || N < 1 || Fn < 1 || Fe < 1 || N > GI_MAX_NODES || Fe > GI_MAX_GROUPS) return GI_EINVAL;
-    if (Fn > GI_ANALYZE_MAX_FN) return GI_ELIMIT;
-    if ((dtype != GI_DTYPE_F32 && dtype != GI_DTYPE_I8) ||
-        (n_nodes_bytes != 1 && n_nodes_bytes != 4 && n_nodes_bytes != 8) ||
-        (term_dtype != GI_DTYPE_F32 && term_dtype != GI_DTYPE_I8))
-        return GI_EINVAL;
+    if (const int rc = gi_mol_check_dims(G, N, Fn, Fe)) return rc;
+    if (const int rc = gi_mol_check_types(dtype, n_nodes_bytes)) return rc;
+    if (term_dtype != GI_DTYPE_F32 && term_dtype != GI_DTYPE_I8) return GI_EINVAL;
     if (n_types < 1 || n_charges < 1 || n_imp_h < 0 || (long long)n_types + n_charges + n_imp_h > Fn ||
         h_type < -1 || h_type >= n_types)
         return GI_EINVAL;

@@ -14,23 +14,18 @@ import torch
 from graphinvent_amd import analyze
 from graphinvent_amd import lib as L
 from tests import analyze_model as AM
+from tests import molio
 from tests.test_analyze_cpu import PROPS, assert_props_equal, load_case
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 DTYPES = [torch.float32, torch.int8]
-NP_OF = {torch.float32: np.float32, torch.int8: np.int8}
 
 
 def to_dev(x, dtype, misalign=3):
-    """x on the device as `dtype`, contiguous, its first byte `misalign` elements past an aligned allocation: no
-    graph of the batch then starts on a 16-byte boundary by accident."""
-    x = np.ascontiguousarray(x)
-    buf = torch.zeros(x.size + misalign, dtype=dtype, device=DEV)
-    view = buf[misalign:].view(x.shape)
-    view.copy_(torch.from_numpy(x.astype(NP_OF[dtype])))
-    assert view.is_contiguous()
-    return view
+    """tests.molio.to_dev three elements past an aligned allocation: no graph of the batch then starts on a 16-byte
+    boundary by accident."""
+    return molio.to_dev(x, dtype, misalign)
 
 
 def host_props(props: dict) -> dict:

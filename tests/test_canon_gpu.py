@@ -12,23 +12,12 @@ from graphinvent_amd import analyze
 from graphinvent_amd import lib as L
 from tests import canon_model as CM
 from tests import rl_callers
+from tests.molio import to_dev
 from tests.test_canon_cpu import CONFIGS, fixture_set, golden, mixed_batch, model_of, permuted_copies
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 DTYPES = [torch.float32, torch.int8]
-NP_OF = {torch.float32: np.float32, torch.int8: np.int8}
-
-
-def to_dev(x, dtype=torch.int8, misalign=1):
-    """x on the device as `dtype`, contiguous, its first byte `misalign` elements past an aligned allocation (int8:
-    one byte), so that the 16-byte pieces start and end raggedly."""
-    x = np.ascontiguousarray(x)
-    buf = torch.zeros(x.size + misalign, dtype=dtype, device=DEV)
-    view = buf[misalign:].view(x.shape)
-    view.copy_(torch.from_numpy(x.astype(NP_OF[dtype])))
-    assert view.is_contiguous()
-    return view
 
 
 def assert_same_canon(can, want, what=""):

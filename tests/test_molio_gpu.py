@@ -1,0 +1,201 @@
+"""-m gpu: the one molecule reader of csrc/gi_molread.h at every alignment, through every entry point that uses it —
+``analyze.molecular_properties``, ``decode``, ``canonical(want_molecules=True)``, ``validity`` and ``routes.reorder``.
+
+An alignment sweep at the smallest shapes where the ragged-granule arithmetic can go wrong: int8 molecules at all 16
+byte offsets of a 16-byte granule, fp32 molecules at element offsets 0 to 3 (``routes.reorder`` takes int8 only).  Every
+comparison is exact, against the numpy models tests/analyze_model.py, canon_model.py, valence_model.py and
+reorder_model.py; a shape's models are computed once and shared by all alignments.
+
+Each case runs G = 3 molecules, so that the middle one has a neighbour on both sides, inside an allocation that holds
+1 everywhere else (tests/molio.py), in two batches:
+    whole   three well-formed molecules (n = N, n = max(N - 1, 1), n = N); the first ends on a set node entry, the
+            last begins with one.  A read outside a molecule's range finds a set entry that no model has.
+    edged   the middle one between two molecules whose FIRST and LAST node and edge entries are set (which makes them
+            self-bonded: ``routes.reorder`` copies them through with ROUTE_ERR_PADDING, ``validity`` flags
+            VAL_SELF_LOOP), so that the middle one's neighbours are non-zero right up to its range.
+
+Shapes (N, Fn, Fe), by the bytes of an int8 molecule's nodes and edges:
+    (1, 1, 1)    one element: first and last granule are the same ragged granule
+    (2, 3, 1)    6 and 4
+    (3, 5, 1)    15 and 9: below one granule at every offset
+    (4, 4, 1)    16 and 16: exactly one whole granule at offset 0, two ragged ones otherwise
+    (5, 3, 3)    15 and 75
+    (13, 8, 3)   104 and 507: the fixtures' pitches
+Left out: (1, 1, 1) for ``molecular_properties`` and ``decode`` (``groups`` needs at least two segments, so Fn >= 2)
+and for ``validity`` (its rules need an atom-type and a formal-charge segment)."""
+import numpy as np
+import pytest
+import torch
+
+from graphinvent_amd import analyze
+from graphinvent_amd import lib as L
+from graphinvent_amd import routes
+from tests import analyze_model as AM
+from tests import canon_model as CM
+from tests import molio
+from tests import reorder_model as OM
+from tests import valence_model as VM
+
+pytestmark = pytest.mark.gpu
+DEV = molio.DEV
+SHAPES = [(1, 1, 1), (2, 3, 1), (3, 5, 1), (4, 4, 1), (5, 3, 3), (13, 8, 3)]
+GROUPS = {1: None, 3: [2, 1], 4: [2, 2], 5: [3, 2], 8: [5, 3]}           # Fn -> (atom types, formal charges)
+ALIGNMENTS = [(torch.int8, a) for a in range(16)] + [(torch.float32, a) for a in range(4)]
+BOND_ORDERS = {1: (1,), 3: (1, 2, 3)}
+_SHARED = {}                                                              # batches and models, computed once
+
+
+def segments(Fn):
+    return GROUPS[Fn] or [Fn]
+
+
+def molecule(N, Fn, Fe, n, shift, end_set=False, edged=False):
+    """n atoms (one set entry per segment) on a tree, every bond mirrored.  `shift` 0 begins with a set node entry,
+    `end_set` (n == N) ends on one, `edged` sets the first and last entries of both arrays."""
+    nodes, edges = np.zeros((N, Fn), np.int8), np.zeros((N, N, Fe), np.int8)
+    for i in range(n):
+        off = 0
+        for size in segments(Fn):
+            nodes[i, off + (i + shift) % size] = 1
+            off += size
+    for i in range(1, n):
+        j, t = (i - 1) // 2, (i + shift) % Fe
+        edges[i, j, t] = edges[j, i, t] = 1
+    if end_set or edged:
+        assert n == N
+        nodes[N - 1, Fn - segments(Fn)[-1]:] = 0
+        nodes[N - 1, Fn - 1] = 1
+    if edged:
+        assert shift == 0
+        edges[0, 0, 0] = edges[N - 1, N - 1, Fe - 1] = 1
+    return nodes, edges
+
+
+def batches(shape):
+    """kind -> (nodes [3, N, Fn], edges [3, N, N, Fe], n_nodes [3] int8)."""
+    if ("batch", shape) not in _SHARED:
+        N = shape[0]
+        mid = molecule(*shape, n=max(N - 1, 1), shift=2 if N > 1 else 0)
+        edge = molecule(*shape, n=N, shift=0, edged=True)
+        out = {}
+        whole = [molecule(*shape, n=N, shift=1, end_set=True), mid, molecule(*shape, n=N, shift=0)]
+        for kind, mols in (("whole", whole), ("edged", [edge, mid, edge])):
+            nodes, edges = np.stack([a for a, _ in mols]), np.stack([b for _, b in mols])
+            assert nodes[0, -1, -1] == 1 and nodes[2, 0, 0] == 1
+            out[kind] = (nodes, edges, nodes.any(axis=2).sum(axis=1).astype(np.int8))
+        _SHARED[("batch", shape)] = out
+    return _SHARED[("batch", shape)]
+
+
+def shared(key, make):
+    if key not in _SHARED:
+        _SHARED[key] = make()
+    return _SHARED[key]
+
+
+def sweep(shape, dtypes=(torch.int8, torch.float32)):
+    """Every (kind, batch on the host, (dtype, offset), nodes and edges on the device); afterwards, that all ran."""
+    runs = 0
+    for kind, (nodes, edges, n) in batches(shape).items():
+        for dtype, a in ALIGNMENTS:
+            if dtype not in dtypes:
+                continue
+            dn, de = molio.to_dev(nodes, dtype, a), molio.to_dev(edges, dtype, a)
+            assert dn.data_ptr() % 16 == a * dn.element_size()
+            yield kind, (nodes, edges, n), (dtype, a), dn, de
+            assert molio.padding_intact(dn) and molio.padding_intact(de), (kind, dtype, a)
+            runs += 1
+    assert runs == 2 * (16 * (torch.int8 in dtypes) + 4 * (torch.float32 in dtypes))
+
+
+def n_given(n):
+    return {"given": torch.from_numpy(n).to(DEV), "derived": None}
+
+
+def assert_equal(got, want, what):
+    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, got.shape, want.dtype, want.shape)
+    assert np.array_equal(got, want), (what, got, want)
+
+
+@pytest.mark.parametrize("shape", SHAPES[1:], ids=str)
+def test_molecular_properties_at_every_alignment(shape):
+    groups = GROUPS[shape[1]]
+    for kind, (nodes, edges, n), at, dn, de in sweep(shape):
+        for mode, nn in n_given(n).items():
+            want = shared(("props", shape, kind, mode), lambda: AM.properties(
+                nodes, edges, n if mode == "given" else None, groups))
+            got = analyze.molecular_properties(dn, de, nn, groups)
+            assert set(got) == set(want)
+            for k, w in want.items():
+                if isinstance(w, list):
+                    assert got[k] == w, (kind, at, mode, k)
+                else:
+                    g = got[k].cpu().numpy()
+                    assert g.dtype == np.float32 and g.tobytes() == np.asarray(w, np.float32).tobytes(), \
+                        (kind, at, mode, k, g, w)
+
+
+@pytest.mark.parametrize("shape", SHAPES[1:], ids=str)
+def test_decode_at_every_alignment(shape):
+    groups = GROUPS[shape[1]]
+    for kind, (nodes, edges, n), at, dn, de in sweep(shape):
+        want = shared(("decode", shape, kind), lambda: AM.decode(nodes, edges, n, groups))
+        got = analyze.decode(dn, de, torch.from_numpy(n).to(DEV), groups).host()
+        for name, g, w in zip(("atoms", "bonds", "n_bonds", "status"), got, want):
+            assert_equal(g, w, (kind, at, name))
+    assert not shared(("decode", shape, "whole"), None)[3].any()              # the whole molecules are well-formed
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=str)
+def test_canonical_at_every_alignment(shape):
+    for kind, (nodes, edges, n), at, dn, de in sweep(shape):
+        for mode, nn in n_given(n).items():
+            want = shared(("canon", shape, kind, mode), lambda: CM.canonical(
+                nodes, edges, n if mode == "given" else None))
+            can = analyze.canonical(dn, de, nn, want_molecules=True)
+            order, rank, key, status = can.host()
+            for name, g in (("status", status), ("order", order), ("rank", rank), ("key", key),
+                            ("nodes", can.nodes.cpu().numpy()), ("edges", can.edges.cpu().numpy())):
+                assert_equal(g, want[name], (kind, at, mode, name))
+    assert not shared(("canon", shape, "whole", "given"), None)["status"].any()
+
+
+@pytest.mark.parametrize("shape", SHAPES[1:], ids=str)
+def test_validity_at_every_alignment(shape):
+    A, C = GROUPS[shape[1]]
+    args = dict(atom_types=list("CNOFS")[:A], formal_charge=[0, 1, -1][:C], bond_orders=BOND_ORDERS[shape[2]])
+    rules, model_rules = analyze.ValenceRules(**args), VM.Rules(**args)
+    for kind, (nodes, edges, n), at, dn, de in sweep(shape):
+        for mode, nn in n_given(n).items():
+            want = shared(("valid", shape, kind, mode), lambda: VM.validity(
+                nodes, edges, n if mode == "given" else None, model_rules))
+            got = analyze.validity(dn, de, nn, rules).host()
+            for name, w in want.items():
+                assert_equal(got[name], w, (kind, at, mode, name))
+    whole, edged = (shared(("valid", shape, k, "given"), None)["status"] for k in ("whole", "edged"))
+    assert not (whole & analyze.MALFORMED_BITS).any()
+    assert (edged & L.VAL_SELF_LOOP != 0).tolist() == [True, False, True]
+
+
+@pytest.mark.parametrize("route", ["bfs", "dfs"])
+@pytest.mark.parametrize("shape", SHAPES, ids=str)
+def test_reorder_at_every_alignment(shape, route):
+    N = shape[0]
+    for kind, (nodes, edges, n), at, dn, de in sweep(shape, dtypes=(torch.int8,)):
+        def model():
+            """The model on the well-formed molecules; a self-bonded one comes back unchanged with its bit."""
+            rank = np.zeros((3, N), np.int32)
+            for m, k in enumerate(n):
+                rank[m, :k] = np.arange(k)[::-1]
+            ok = [0, 1, 2] if kind == "whole" else [1]
+            out_n, out_e = nodes.copy(), edges.copy()
+            order = np.tile(np.arange(N, dtype=np.int32), (3, 1))
+            out_n[ok], out_e[ok], order[ok] = OM.reorder(nodes[ok], edges[ok], route, rank=rank[ok])
+            err = np.full(3, L.ROUTE_ERR_PADDING, np.int32)
+            err[ok] = 0
+            return rank, (out_n, out_e, order, err)
+
+        rank, want = shared(("reorder", shape, kind, route), model)
+        got = routes.reorder(dn, de, route=route, rank=rank, return_order=True, invalid="skip")
+        for name, g, w in zip(("nodes", "edges", "order", "err"), got, want):
+            assert_equal(g.cpu().numpy(), w, (kind, at, name))

@@ -10,6 +10,7 @@ import torch
 
 from graphinvent_amd import lib as L
 from graphinvent_amd import routes
+from tests import molio
 from tests import reorder_model as OM
 from tests import routes_model as RM
 
@@ -108,7 +109,13 @@ def test_unaligned_views_of_a_larger_buffer():
     dn, de = _dev(mn, me)
     for lo in (1, 2, 3, 5):
         out = routes.reorder(dn[lo:lo + 9], de[lo:lo + 9], route="dfs", rank=rank[lo:lo + 9], return_order=True)
-        _assert_equals_model(out, OM.reorder(mn[lo:lo + 9], me[lo:lo + 9], "dfs", rank=rank[lo:lo + 9]))
+        want = OM.reorder(mn[lo:lo + 9], me[lo:lo + 9], "dfs", rank=rank[lo:lo + 9])
+        _assert_equals_model(out, want)
+        # the same molecules `lo` bytes into an allocation that holds 1 everywhere else: a read past either end of
+        # the batch meets a set entry
+        pn, pe = molio.to_dev(mn[lo:lo + 9], misalign=lo), molio.to_dev(me[lo:lo + 9], misalign=lo)
+        _assert_equals_model(routes.reorder(pn, pe, route="dfs", rank=rank[lo:lo + 9], return_order=True), want)
+        assert molio.padding_intact(pn) and molio.padding_intact(pe)
 
 
 # ---- the device-drawn ranking ------------------------------------------------------------------------------

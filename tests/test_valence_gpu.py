@@ -12,13 +12,13 @@ from graphinvent_amd import analyze
 from graphinvent_amd import lib as L
 from tests import rl_callers
 from tests import valence_model as VM
+from tests.molio import to_dev
 from tests.test_valence_cpu import (RULE_ARGS, aromatic_and_h_cases, chemistry_table, model_of, model_rules, shipped,
                                     status_cases, stored_set)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 DTYPES = [torch.float32, torch.int8]
-NP_OF = {torch.float32: np.float32, torch.int8: np.int8}
 NAMES = ("valid", "status", "first_bad", "atom_valence", "atom_h", "desc", "counts")
 _RULES = {}
 
@@ -29,16 +29,6 @@ def dev_rules(name, **kw):
     if name not in _RULES:
         _RULES[name] = analyze.ValenceRules(**RULE_ARGS[name])
     return _RULES[name]
-
-
-def to_dev(x, dtype=torch.int8, misalign=1):
-    """x on the device as `dtype`, contiguous, its first byte `misalign` elements past an aligned allocation."""
-    x = np.ascontiguousarray(x)
-    buf = torch.zeros(x.size + misalign, dtype=dtype, device=DEV)
-    view = buf[misalign:].view(x.shape)
-    view.copy_(torch.from_numpy(x.astype(NP_OF[dtype])))
-    assert view.is_contiguous()
-    return view
 
 
 def assert_same(res, want, what=""):
