@@ -54,6 +54,13 @@ bool gi_gru_fused_ok(int H, int M, int lda, int ldh, int ldg);
 int gi_gru_fused_fwd(const float* agg, int lda, const float* hx, int ldh, const float* Wih, const float* Whh,
                      const float* bih, const float* bhh, float* gi, float* gh, int ldg, float* hx_new,
                      const int* seg_off, int rows, const int* rows_dev, int H, int M, void* stream);
+// ... with gi_seg_sum_n(vals, ldv, perm, seg_off, rows, M, agg, lda, 0, rows_dev) inside the launch (GI_GLUE_GRU_AGG)
+bool gi_gru_fused_agg_ok(int H, int M, int lda, int ldh, int ldg, int ldv);
+bool gi_gru_fused_agg_pays(int rows, int H);      // no more workgroups than CUs: its LDS allows one per CU
+int gi_gru_fused_agg_fwd(const float* vals, int ldv, const int* perm, float* agg, int lda, const float* hx, int ldh,
+                         const float* Wih, const float* Whh, const float* bih, const float* bhh, float* gi, float* gh,
+                         int ldg, float* hx_new, const int* seg_off, int rows, const int* rows_dev, int H, int M,
+                         void* stream);
 
 // gi_gemm_batch hands launches whose problems all carry GI_GEMM_BF3 to gi_gemm_bf3.hip
 int gi_gemm_bf3_launch(const gi_gemm_params* probs, int n, void* stream);

@@ -18,6 +18,8 @@
 // take elements (4q, 4q + 2) and (4q + 1, 4q + 3) of a 4-group, so that a lane's fragment is one ds_read_b64.
 #include <stdlib.h>
 
+#include <atomic>
+
 #include "gi_common.h"
 #include "gi_mfma.h"
 
@@ -41,6 +43,8 @@ struct GruArgs {
     const int* seg_off;                     // [R + 1]: incoming-edge CSR offsets (node mask)
     int rows; const int* rows_dev;          // rows_dev != NULL: the real row count lives on the device (bounded forward)
     int H, M;
+    // AGG variant: agg = sum of the rows vals[perm[k]], k in [seg_off[row], seg_off[row + 1]), built by the kernel
+    const float* vals; int ldv; const int* perm; float* agg_out;
 };
 
 // 512 threads = TWO groups of 2 x 2 waves: group 0 accumulates the input projection (agg W_ih^T, reduction over M), group 1
@@ -48,7 +52,17 @@ struct GruArgs {
 // their LDS / barrier / load latencies overlap (one group alone: 35 us per launch for 12 us of MFMA time, measured).
 // Group 1 hands its three accumulators to group 0 through LDS (over the staging buffers, which are dead by then), and
 // group 0 applies the gates.
+//
+// AGG (GI_GLUE_GRU_AGG): the aggregation of the incoming messages, gi_seg_sum's launch in front of this one, happens
+// here.  A workgroup needs agg only for its own 64 rows: all 512 threads build that 64 x M tile in LDS (dynamic:
+// 64 x (M + 16) floats — rows 16 floats apart in the banks, so that the eight lanes of a 128-byte read phase, two rows
+// x four float4, do not collide), every float4 summed in seg_sum_kernel's order (zero, first pair, further pairs, tail;
+// four outputs per thread travel through the dependent loads together, as in seg_sum_kernel<4>); the workgroups of the
+// first unit tile also write it to agg_out for the backward.  Group 0 then stages its A chunks from the tile; group 1
+// has requested its first two chunks before the aggregation and depends on nothing in it.
+template <bool AGG>
 __global__ __launch_bounds__(512) void gru_fused_fwd_kernel(const GruArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float agg_s[];     // AGG only: [GU_TM][M + 16]
     constexpr int A_FL = 2 * GU_TM * GU_LD, W_FL = 2 * 3 * GU_TN * GU_LD, G_FL = A_FL + W_FL;     // floats per group
     __shared__ __attribute__((aligned(16))) float lds[2 * G_FL > 3 * 16 * 256 ? 2 * G_FL : 3 * 16 * 256];
     __shared__ int live_s[GU_TM];
@@ -90,8 +104,12 @@ __global__ __launch_bounds__(512) void gru_fused_fwd_kernel(const GruArgs a) {
 #pragma unroll
         for (int i = 0; i < GU_NA; ++i) {
             const int idx = tg + 256 * i, ar = idx / GU_QPR, aq = idx % GU_QPR;
-            const long long row = min(row0 + ar, rows - 1);
-            ra_[set][i] = *(const v4f*)(Abase + row * lda_ + min(kc0 + 4 * aq, K - 4));
+            if (AGG && grp == 0) {
+                ra_[set][i] = *(const v4f*)(agg_s + ar * (M + 16) + min(kc0 + 4 * aq, K - 4));
+            } else {
+                const long long row = min(row0 + ar, rows - 1);
+                ra_[set][i] = *(const v4f*)(Abase + row * lda_ + min(kc0 + 4 * aq, K - 4));
+            }
         }
 #pragma unroll
         for (int i = 0; i < GU_NW; ++i) {
@@ -140,8 +158,68 @@ __global__ __launch_bounds__(512) void gru_fused_fwd_kernel(const GruArgs a) {
     // Pipeline (chunk c is in LDS buffer c & 1, chunk c + 1 in register set (c + 1) & 1, chunk c + 2 being loaded into set
     // c & 1): request c + 2, multiply c, write c + 1 into the other buffer (its readers finished a barrier ago), barrier.
     // Both groups run the same number of iterations (the shorter reduction idles through the barriers).
-    gload(0, 0);
-    gload(1, 1);
+    if (!AGG || grp == 1) {
+        gload(0, 0);
+        gload(1, 1);
+    }
+    if (AGG) {
+        constexpr int AU = 4;
+        const int c4n = M >> 2, n_out = GU_TM * c4n, TS = M + 16;
+        const float* __restrict__ vals = a.vals;
+        const int* __restrict__ perm = a.perm;
+        const int* __restrict__ off = a.seg_off;
+        const int ldv = a.ldv;
+        for (int base = 0; base < n_out; base += 512 * AU) {
+            int t[AU], c[AU], q[AU], lo[AU], hi[AU];
+            bool ok[AU];
+#pragma unroll
+            for (int u = 0; u < AU; ++u) {
+                t[u] = base + u * 512 + tid;
+                c[u] = t[u] / c4n; q[u] = t[u] - c[u] * c4n;
+                ok[u] = t[u] < n_out && row0 + c[u] < rows;
+                lo[u] = ok[u] ? off[row0 + c[u]] : 0;
+                hi[u] = ok[u] ? off[row0 + c[u] + 1] : 0;
+            }
+            int p0[AU], p1[AU];
+#pragma unroll
+            for (int u = 0; u < AU; ++u) {                       // the first pair of every output: all loads in flight together
+                p0[u] = lo[u] < hi[u] ? perm[lo[u]] : -1;
+                p1[u] = lo[u] + 1 < hi[u] ? perm[lo[u] + 1] : -1;
+            }
+            v4f x0[AU], x1[AU], acc[AU];
+#pragma unroll
+            for (int u = 0; u < AU; ++u) {
+                x0[u] = p0[u] >= 0 ? *(const v4f*)(vals + (long long)p0[u] * ldv + 4 * q[u]) : v4f{0.f, 0.f, 0.f, 0.f};
+                x1[u] = p1[u] >= 0 ? *(const v4f*)(vals + (long long)p1[u] * ldv + 4 * q[u]) : v4f{0.f, 0.f, 0.f, 0.f};
+            }
+#pragma unroll
+            for (int u = 0; u < AU; ++u) {
+                acc[u] = v4f{0.f, 0.f, 0.f, 0.f};
+                if (p0[u] >= 0) acc[u] += x0[u];
+                if (p1[u] >= 0) acc[u] += x1[u];
+                int k = lo[u] + 2;
+                for (; k + 1 < hi[u]; k += 2) {
+                    const int r0 = perm[k], r1 = perm[k + 1];
+                    const v4f x = *(const v4f*)(vals + (long long)r0 * ldv + 4 * q[u]);
+                    const v4f y = *(const v4f*)(vals + (long long)r1 * ldv + 4 * q[u]);
+                    acc[u] += x;
+                    acc[u] += y;
+                }
+                if (k < hi[u]) acc[u] += *(const v4f*)(vals + (long long)perm[k] * ldv + 4 * q[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < AU; ++u) {
+                if (t[u] >= n_out) continue;
+                *(v4f*)(agg_s + c[u] * TS + 4 * q[u]) = acc[u];          // (rows past the end: zeros, never stored)
+                if (ok[u] && blockIdx.y == 0) *(v4f*)(a.agg_out + (long long)(row0 + c[u]) * a.lda + 4 * q[u]) = acc[u];
+            }
+        }
+        __syncthreads();
+        if (grp == 0) {
+            gload(0, 0);
+            gload(1, 1);
+        }
+    }
     sstore(0, 0);
     __syncthreads();
     for (int c = 0; c < nc; c += 2) {                            // (unrolled by two: the register sets are compile-time;
@@ -217,13 +295,62 @@ int gi_gru_fused_fwd(const float* agg, int lda, const float* hx, int ldh, const 
     if (!agg || !hx || !Wih || !Whh || !bih || !bhh || !gi || !gh || !hx_new || !seg_off) return GI_EINVAL;
     if (!gi_gru_fused_ok(H, M, lda, ldh, ldg)) return GI_EINVAL;
     if ((((uintptr_t)agg | (uintptr_t)hx | (uintptr_t)hx_new) & 15) != 0) return GI_EINVAL;
-    GruArgs a{agg, lda, hx, ldh, Wih, Whh, bih, bhh, gi, gh, ldg, hx_new, seg_off, rows, rows_dev, H, M};
+    GruArgs a{agg, lda, hx, ldh, Wih, Whh, bih, bhh, gi, gh, ldg, hx_new, seg_off, rows, rows_dev, H, M,
+              nullptr, 0, nullptr, nullptr};
     hipStream_t st = (hipStream_t)stream;
     GiProfScope prof(st, GI_PROF_GEMM, 2.0 * (double)rows * 3.0 * H * ((double)M + H));
     // (static LDS only: padding the launch with unused dynamic LDS to force one workgroup per CU was measured and not
     // adopted, tools/experiments/README.md "Retired switches")
-    hipLaunchKernelGGL(gru_fused_fwd_kernel, dim3(gi_cdiv(rows, GU_TM), gi_cdiv(H, GU_TN)), dim3(512), 0, st, a);
+    hipLaunchKernelGGL(gru_fused_fwd_kernel<false>, dim3(gi_cdiv(rows, GU_TM), gi_cdiv(H, GU_TN)), dim3(512), 0, st, a);
     return gi_launch_status();
+}
+
+// The update with the aggregation inside (GI_GLUE_GRU_AGG): gi_seg_sum_n(vals, ldv, perm, seg_off, rows, M, agg, lda, 0,
+// rows_dev) + gi_gru_fused_fwd(agg, ...) in one launch, bit for bit.
+bool gi_gru_fused_agg_ok(int H, int M, int lda, int ldh, int ldg, int ldv) {
+    // (static + dynamic LDS of the kernel: 72 KB + 64 (M + 16) floats, inside the 160 KB of a gfx950 CU up to M = 320)
+    return gi_gru_fused_ok(H, M, lda, ldh, ldg) && (ldv & 3) == 0 && ldv >= M && M <= 320;
+}
+// Its LDS leaves room for ONE workgroup per CU (the plain kernel: two), so it pays only where the launch has no more
+// workgroups than the device has CUs — the headline batch: 230 on 256.  Measured at the ZINC shape (about 700
+// workgroups): 3.72 ms per step against 3.67 with the aggregation in its own launch (profiles/glue/README.md).
+bool gi_gru_fused_agg_pays(int rows, int H) {
+    static std::atomic<int> cus[64];                              // per device ordinal, 0 = not asked yet
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return false; }
+    int n = cus[dev].load(std::memory_order_relaxed);
+    if (n == 0) {
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
+            (void)hipGetLastError();
+            return false;
+        }
+        cus[dev].store(n, std::memory_order_relaxed);
+    }
+    return (long long)gi_cdiv(rows, GU_TM) * gi_cdiv(H, GU_TN) <= n;
+}
+int gi_gru_fused_agg_fwd(const float* vals, int ldv, const int* perm, float* agg, int lda, const float* hx, int ldh,
+                         const float* Wih, const float* Whh, const float* bih, const float* bhh, float* gi, float* gh,
+                         int ldg, float* hx_new, const int* seg_off, int rows, const int* rows_dev, int H, int M,
+                         void* stream) {
+    (void)hipGetLastError();
+    if (rows <= 0) return 0;
+    if (!vals || !agg || !hx || !Wih || !Whh || !bih || !bhh || !gi || !gh || !hx_new || !seg_off) return GI_EINVAL;
+    if (!gi_gru_fused_agg_ok(H, M, lda, ldh, ldg, ldv)) return GI_EINVAL;
+    if ((((uintptr_t)vals | (uintptr_t)agg | (uintptr_t)hx | (uintptr_t)hx_new) & 15) != 0) return GI_EINVAL;
+    GruArgs a{agg, lda, hx, ldh, Wih, Whh, bih, bhh, gi, gh, ldg, hx_new, seg_off, rows, rows_dev, H, M,
+              vals, ldv, perm, agg};
+    hipStream_t st = (hipStream_t)stream;
+    GiProfScope prof(st, GI_PROF_GEMM, 2.0 * (double)rows * 3.0 * H * ((double)M + H));
+    hipLaunchKernelGGL(gru_fused_fwd_kernel<true>, dim3(gi_cdiv(rows, GU_TM), gi_cdiv(H, GU_TN)), dim3(512),
+                       sizeof(float) * GU_TM * (M + 16), st, a);
+    return gi_launch_status();
+}
+extern "C" int gi_gru_forward_agg(const float* vals, int ldv, const int* perm, float* agg, int lda, const float* hx,
+                                  int ldh, const float* Wih, const float* Whh, const float* bih, const float* bhh,
+                                  float* gi, float* gh, int ldg, float* hx_new, const int* seg_off, int rows,
+                                  const int* rows_dev, int H, int M, void* stream) {
+    return gi_gru_fused_agg_fwd(vals, ldv, perm, agg, lda, hx, ldh, Wih, Whh, bih, bhh, gi, gh, ldg, hx_new, seg_off,
+                                rows, rows_dev, H, M, stream);
 }
 
 // C ABI (include/graphinvent_amd.h): the fused update by itself (tests; gi_ggnn_forward calls the function above)

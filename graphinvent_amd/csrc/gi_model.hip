@@ -2122,7 +2122,16 @@ extern "C" int gi_ggnn_forward_ex(const gi_ggnn_dims* dp, const float* const* pa
             if (E > 0)   // m_u = MLP_type(u)(h_src(u)), gnn/mpnn.py:284-294, once per message row
                 mlp_forward(r, ws, m.msg, bytype, hx, w.ldhx, u_src, U, w.eact[p], w.ldEh,
                             ws + w.m[p], w.ldM);
-            // a_v = sum of incoming messages (:141)
+            // a_v = sum of incoming messages (:141): inside the GRU update's launch (GI_GLUE_GRU_AGG) ...
+            if ((gi_glue_flags() & GI_GLUE_GRU_AGG) && gi_gru_fused_agg_ok(d.H, d.M, w.ldM, w.ldhx, w.ld3H, w.ldM) &&
+                gi_gru_fused_agg_pays(R, d.H)) {
+                r.chk(gi_gru_fused_agg_fwd(ws + w.m[p], w.ldM, in_perm, ws + w.agg[p], w.ldM, hx, w.ldhx,
+                                           params[m.gru_wih], params[m.gru_whh], params[m.gru_bih], params[m.gru_bhh],
+                                           ws + w.gi[p], ws + w.gh[p], w.ld3H, ws + w.hx[p + 1], seg_off, R, r.dims,
+                                           d.H, d.M, r.st));
+                continue;
+            }
+            // ... or in a launch of its own
             r.chk(gi_seg_sum_n(ws + w.m[p], w.ldM, in_perm, seg_off, R, d.M, ws + w.agg[p], w.ldM, 0, r.dims,
                                r.st));
         }
@@ -2158,15 +2167,22 @@ extern "C" int gi_ggnn_forward_ex(const gi_ggnn_dims* dp, const float* const* pa
         jobs[3] = {&m.emb, hx, w.ldhx, R, w.emb_act, w.ldEmb, ws + w.embo, w.ldG};
         mlp_jobs_forward(r, ws, jobs, 4);
     }
-    r.chk(gi_gather_readout_fwd(ws + w.en, ws + w.embo, w.ldG, cidx, mask, d.B, d.N, d.G,
-                                d.big_positive, ws + w.cat_add + m.NA, w.ldCA,
-                                ws + w.cat_conn + m.NC, w.ldCC, ws + w.gemb, w.ldG, r.st));
-    if (gi_fuse_flags() & GI_FUSE_SLOTS) {
-        r.chk(gi_expand_slots2(ws + w.add1o, w.ldA, d.A, ws + w.cat_add, w.ldCA, ws + w.conn1o, w.ldC, d.C,
-                               ws + w.cat_conn, w.ldCC, cidx, d.B, d.N, r.st));
+    if (gi_glue_flags() & GI_GLUE_READOUT_FWD) {     // gather + tier-1 expansion in one launch
+        r.chk(gi_readout_glue_fwd(ws + w.en, ws + w.embo, w.ldG, cidx, mask, d.B, d.N, d.G, d.big_positive,
+                                  ws + w.cat_add + m.NA, w.ldCA, ws + w.cat_conn + m.NC, w.ldCC, ws + w.gemb, w.ldG,
+                                  ws + w.add1o, w.ldA, d.A, ws + w.cat_add, w.ldCA, ws + w.conn1o, w.ldC, d.C,
+                                  ws + w.cat_conn, w.ldCC, r.st));
     } else {
-        r.chk(gi_expand_slots(ws + w.add1o, w.ldA, cidx, d.B, d.N, d.A, ws + w.cat_add, w.ldCA, r.st));
-        r.chk(gi_expand_slots(ws + w.conn1o, w.ldC, cidx, d.B, d.N, d.C, ws + w.cat_conn, w.ldCC, r.st));
+        r.chk(gi_gather_readout_fwd(ws + w.en, ws + w.embo, w.ldG, cidx, mask, d.B, d.N, d.G,
+                                    d.big_positive, ws + w.cat_add + m.NA, w.ldCA,
+                                    ws + w.cat_conn + m.NC, w.ldCC, ws + w.gemb, w.ldG, r.st));
+        if (gi_fuse_flags() & GI_FUSE_SLOTS) {
+            r.chk(gi_expand_slots2(ws + w.add1o, w.ldA, d.A, ws + w.cat_add, w.ldCA, ws + w.conn1o, w.ldC, d.C,
+                                   ws + w.cat_conn, w.ldCC, cidx, d.B, d.N, r.st));
+        } else {
+            r.chk(gi_expand_slots(ws + w.add1o, w.ldA, cidx, d.B, d.N, d.A, ws + w.cat_add, w.ldCA, r.st));
+            r.chk(gi_expand_slots(ws + w.conn1o, w.ldC, cidx, d.B, d.N, d.C, ws + w.cat_conn, w.ldCC, r.st));
+        }
     }
     {   // the three graph-level stacks write straight into the logits
         MlpJob jobs[3] = {};
@@ -2346,18 +2362,26 @@ extern "C" int gi_ggnn_backward_phase(const gi_ggnn_dims* dp, const float* const
         mlp_jobs_backward(r, ws, sp, slabs, dq, jobs, 3);
     }
     // ---- gather + tier-1 glue: dZ of the last att/emb/add1/conn1 layers, in place ----------------
-    r.chk(gi_gather_readout_bwd_f(ws + w.en, ws + w.embo, w.ldG, cidx, mask, d.B, d.N, d.G, S,
-                                  d.big_positive, ws + w.dgemb, w.ldG, ws + w.dcat_add + NA, w.ldCA,
-                                  ws + w.dcat_conn + NC, w.ldCC, ws + w.zpart_g, r.fshift, r.st));
-    if (gi_fuse_flags() & GI_FUSE_SLOTS) {
-        r.chk(gi_compress_slots2_f(ws + w.add1o, w.ldA, d.A, ws + w.dcat_add, w.ldCA, ws + w.zpart_a, w.ldA,
-                                   ws + w.conn1o, w.ldC, d.C, ws + w.dcat_conn, w.ldCC, ws + w.zpart_c,
-                                   w.ldC, cidx, d.B, d.N, S, r.fshift, r.st));
+    if (gi_glue_flags() & GI_GLUE_READOUT_BWD) {     // both in one launch
+        r.chk(gi_readout_glue_bwd_f(ws + w.en, ws + w.embo, w.ldG, cidx, mask, d.B, d.N, d.G, S, d.big_positive,
+                                    ws + w.dgemb, w.ldG, ws + w.dcat_add + NA, w.ldCA, ws + w.dcat_conn + NC, w.ldCC,
+                                    ws + w.zpart_g, ws + w.add1o, w.ldA, d.A, ws + w.dcat_add, w.ldCA, ws + w.zpart_a,
+                                    w.ldA, ws + w.conn1o, w.ldC, d.C, ws + w.dcat_conn, w.ldCC, ws + w.zpart_c, w.ldC,
+                                    r.fshift, r.st));
     } else {
-        r.chk(gi_compress_slots_f(ws + w.add1o, w.ldA, cidx, d.B, d.N, d.A, S, ws + w.dcat_add, w.ldCA,
-                                  ws + w.zpart_a, w.ldA, r.fshift, r.st));
-        r.chk(gi_compress_slots_f(ws + w.conn1o, w.ldC, cidx, d.B, d.N, d.C, S, ws + w.dcat_conn, w.ldCC,
-                                  ws + w.zpart_c, w.ldC, r.fshift, r.st));
+        r.chk(gi_gather_readout_bwd_f(ws + w.en, ws + w.embo, w.ldG, cidx, mask, d.B, d.N, d.G, S,
+                                      d.big_positive, ws + w.dgemb, w.ldG, ws + w.dcat_add + NA, w.ldCA,
+                                      ws + w.dcat_conn + NC, w.ldCC, ws + w.zpart_g, r.fshift, r.st));
+        if (gi_fuse_flags() & GI_FUSE_SLOTS) {
+            r.chk(gi_compress_slots2_f(ws + w.add1o, w.ldA, d.A, ws + w.dcat_add, w.ldCA, ws + w.zpart_a, w.ldA,
+                                       ws + w.conn1o, w.ldC, d.C, ws + w.dcat_conn, w.ldCC, ws + w.zpart_c,
+                                       w.ldC, cidx, d.B, d.N, S, r.fshift, r.st));
+        } else {
+            r.chk(gi_compress_slots_f(ws + w.add1o, w.ldA, cidx, d.B, d.N, d.A, S, ws + w.dcat_add, w.ldCA,
+                                      ws + w.zpart_a, w.ldA, r.fshift, r.st));
+            r.chk(gi_compress_slots_f(ws + w.conn1o, w.ldC, cidx, d.B, d.N, d.C, S, ws + w.dcat_conn, w.ldCC,
+                                      ws + w.zpart_c, w.ldC, r.fshift, r.st));
+        }
     }
     {   // zero-row gradients of the four stacks: per-graph partial sums -> row S, one launch
         float* en_z = ws + w.en + (long long)S * w.ldG;

@@ -5,6 +5,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <atomic>
 
 #include <string.h>
 
@@ -454,17 +455,16 @@ __global__ __launch_bounds__(256) void gru_gates_bwd_v4_kernel(
 // order as before (a thread used to walk the N rows three times through global memory with one load
 // in flight: 38 us per launch at N = 88, latency bound).  Dynamic LDS: 2 * N * GC floats (GC = 64
 // columns per workgroup, 32 for N > 112: at most 56 KB).
+// (the bodies are device functions of (graph b, first column g0): the readout-glue launches below run them too)
 template <int GI_GATHER_GC>
-__global__ __launch_bounds__(GI_GATHER_GC) void gather_fwd_kernel(
+__device__ __forceinline__ void gather_fwd_body(
+    const int b, const int g0, float* gather_lds, int* c_s, float* pen_s,
     const float* __restrict__ en, const float* __restrict__ emb, int ld,
     const int* __restrict__ cidx, const int* __restrict__ mask, int N, int G, float big,
     float* out0, int ld0, float* out1, int ld1, float* out2, int ld2) {
-    extern __shared__ float gather_lds[];
-    __shared__ int c_s[GI_MAX_NODES];
-    __shared__ float pen_s[GI_MAX_NODES];
     float* e_s = gather_lds;                               // [N][GC] energies minus the mask penalty
     float* m_s = gather_lds + N * GI_GATHER_GC;            // [N][GC] embeddings
-    const int b = blockIdx.x, g0 = blockIdx.y * GI_GATHER_GC, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     for (int n = tid; n < N; n += GI_GATHER_GC) {
         c_s[n] = cidx[b * N + n];
         pen_s[n] = mask[b * N + n] ? 0.f : big;       // (node_mask == 0) * big_positive, modules.py:46
@@ -492,17 +492,27 @@ __global__ __launch_bounds__(GI_GATHER_GC) void gather_fwd_kernel(
 }
 
 template <int GI_GATHER_GC>
-__global__ __launch_bounds__(GI_GATHER_GC) void gather_bwd_kernel(
+__global__ __launch_bounds__(GI_GATHER_GC) void gather_fwd_kernel(
+    const float* __restrict__ en, const float* __restrict__ emb, int ld,
+    const int* __restrict__ cidx, const int* __restrict__ mask, int N, int G, float big,
+    float* out0, int ld0, float* out1, int ld1, float* out2, int ld2) {
+    extern __shared__ float gather_lds[];
+    __shared__ int c_s[GI_MAX_NODES];
+    __shared__ float pen_s[GI_MAX_NODES];
+    gather_fwd_body<GI_GATHER_GC>(blockIdx.x, blockIdx.y * GI_GATHER_GC, gather_lds, c_s, pen_s, en, emb, ld, cidx,
+                                  mask, N, G, big, out0, ld0, out1, ld1, out2, ld2);
+}
+
+template <int GI_GATHER_GC>
+__device__ __forceinline__ void gather_bwd_body(
+    const int b, const int g0, float* gather_lds, int* c_s, float* pen_s,
     float* en, float* emb, int ld, const int* __restrict__ cidx, const int* __restrict__ mask,
     int N, int G, int S, float big, const float* __restrict__ dg0, int ld0,
     const float* __restrict__ dg1, int ld1, const float* __restrict__ dg2, int ld2,
     float* __restrict__ zpart, long long fshift) {
-    extern __shared__ float gather_lds[];
-    __shared__ int c_s[GI_MAX_NODES];
-    __shared__ float pen_s[GI_MAX_NODES];
     float* e_s = gather_lds;                               // raw energies
     float* m_s = gather_lds + N * GI_GATHER_GC;
-    const int b = blockIdx.x, g0 = blockIdx.y * GI_GATHER_GC, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     for (int n = tid; n < N; n += GI_GATHER_GC) {
         c_s[n] = cidx[b * N + n];
         pen_s[n] = mask[b * N + n] ? 0.f : big;
@@ -551,6 +561,19 @@ __global__ __launch_bounds__(GI_GATHER_GC) void gather_bwd_kernel(
     zpart[(long long)b * ldz + G + g] = zemb;
 }
 
+template <int GI_GATHER_GC>
+__global__ __launch_bounds__(GI_GATHER_GC) void gather_bwd_kernel(
+    float* en, float* emb, int ld, const int* __restrict__ cidx, const int* __restrict__ mask,
+    int N, int G, int S, float big, const float* __restrict__ dg0, int ld0,
+    const float* __restrict__ dg1, int ld1, const float* __restrict__ dg2, int ld2,
+    float* __restrict__ zpart, long long fshift) {
+    extern __shared__ float gather_lds[];
+    __shared__ int c_s[GI_MAX_NODES];
+    __shared__ float pen_s[GI_MAX_NODES];
+    gather_bwd_body<GI_GATHER_GC>(blockIdx.x, blockIdx.y * GI_GATHER_GC, gather_lds, c_s, pen_s, en, emb, ld, cidx,
+                                  mask, N, G, S, big, dg0, ld0, dg1, ld1, dg2, ld2, zpart, fshift);
+}
+
 // ---- tier-1 <-> tier-2 glue ------------------------------------------------------------------
 __global__ __launch_bounds__(256) void expand_slots_kernel(
     const float* __restrict__ t1, int ldt, const int* __restrict__ cidx, int NW, int W,
@@ -566,9 +589,8 @@ __global__ __launch_bounds__(256) void expand_slots_kernel(
 // both tier-1 outputs (fAddNet1 / fConnNet1) in one launch: elements [0, total_a) belong to problem a
 struct ExpandPair { const float* t1[2]; int ldt[2]; int W[2]; float* cat[2]; int ldc[2]; };
 
-__global__ __launch_bounds__(256) void expand_slots2_kernel(const ExpandPair a, const int* __restrict__ cidx,
-                                                            int N, long long total_a, long long total) {
-    long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void expand_slots2_elem(const ExpandPair& a, const int* __restrict__ cidx, int N,
+                                                   long long total_a, long long total, long long t) {
     if (t >= total) return;
     const int k = t >= total_a ? 1 : 0;
     t -= k ? total_a : 0;
@@ -576,6 +598,40 @@ __global__ __launch_bounds__(256) void expand_slots2_kernel(const ExpandPair a, 
     const int b = (int)(t / NW), r = (int)(t - (long long)b * NW);
     const int n = r / W, w = r - n * W;
     a.cat[k][(long long)b * a.ldc[k] + r] = a.t1[k][(long long)cidx[b * N + n] * a.ldt[k] + w];
+}
+
+__global__ __launch_bounds__(256) void expand_slots2_kernel(const ExpandPair a, const int* __restrict__ cidx,
+                                                            int N, long long total_a, long long total) {
+    expand_slots2_elem(a, cidx, N, total_a, total, (long long)blockIdx.x * 256 + threadIdx.x);
+}
+
+// Forward readout glue in ONE launch (GI_GLUE_READOUT_FWD): the gather workgroups (graph b, column chunk: b runs
+// fastest, as in the two-dimensional grid of gather_fwd_kernel) followed by the expand workgroups, 256 elements each
+// whatever the block size.  Both bodies read only the tier-1 outputs and write disjoint parts of the tier-2 inputs, so
+// every output is the one the two launches write.
+struct GatherFwdArgs {
+    const float* en; const float* emb; int ld; const int* mask; int N, G; float big;
+    float* out0; int ld0; float* out1; int ld1; float* out2; int ld2;
+};
+
+template <int GI_GATHER_GC>
+__global__ __launch_bounds__(GI_GATHER_GC) void readout_glue_fwd_kernel(const GatherFwdArgs g, const ExpandPair a,
+                                                                        const int* __restrict__ cidx, int B,
+                                                                        int n_gather, long long total_a,
+                                                                        long long total) {
+    extern __shared__ float gather_lds[];
+    __shared__ int c_s[GI_MAX_NODES];
+    __shared__ float pen_s[GI_MAX_NODES];
+    const int id = blockIdx.x;
+    if (id < n_gather) {                                   // block-uniform
+        const int chunk = id / B, b = id - chunk * B;
+        gather_fwd_body<GI_GATHER_GC>(b, chunk * GI_GATHER_GC, gather_lds, c_s, pen_s, g.en, g.emb, g.ld, cidx, g.mask,
+                                      g.N, g.G, g.big, g.out0, g.ld0, g.out1, g.ld1, g.out2, g.ld2);
+        return;
+    }
+    const long long base = (long long)(id - n_gather) * 256 + threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < 256; i += GI_GATHER_GC) expand_slots2_elem(a, cidx, g.N, total_a, total, base + i);
 }
 
 // One workgroup per (graph, quarter of its N*W elements): the slots that own a compact row are
@@ -611,20 +667,22 @@ __global__ __launch_bounds__(256) void compress_slots_kernel(
 // the same for the two tier-1 stacks in one launch (blockIdx.z = problem)
 struct CompressPair { float* t1[2]; int ldt[2]; int W[2]; const float* dcat[2]; int ldc[2]; float* zpart[2]; int ldz[2]; };
 
-__global__ __launch_bounds__(256) void compress_slots2_kernel(const CompressPair a, const int* __restrict__ cidx,
-                                                              int N, int S, long long fshift) {
-    __shared__ int c_s[GI_MAX_NODES];
-    const int k = blockIdx.z;
+// (workgroup `part` of `parts` of graph b, problem k, NT threads: how the elements are dealt to workgroups and threads
+// does not enter any result)
+template <int NT>
+__device__ __forceinline__ void compress_slots2_body(const CompressPair& a, const int* __restrict__ cidx, int N, int S,
+                                                     long long fshift, int* c_s, const int b, const int part,
+                                                     const int parts, const int k) {
     float* t1 = a.t1[k];
     const float* __restrict__ dcat = a.dcat[k];
     float* __restrict__ zpart = a.zpart[k];
     const int ldt = a.ldt[k], W = a.W[k], ldc = a.ldc[k], ldz = a.ldz[k];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    for (int n = tid; n < N; n += 256) c_s[n] = cidx[b * N + n];
+    const int tid = threadIdx.x;
+    for (int n = tid; n < N; n += NT) c_s[n] = cidx[b * N + n];
     __syncthreads();
-    const int total = N * W, chunk = (total + gridDim.y - 1) / gridDim.y;
-    const int lo = blockIdx.y * chunk, hi = min(lo + chunk, total);
-    for (int idx = lo + tid; idx < hi; idx += 256) {
+    const int total = N * W, chunk = (total + parts - 1) / parts;
+    const int lo = part * chunk, hi = min(lo + chunk, total);
+    for (int idx = lo + tid; idx < hi; idx += NT) {
         const int n = idx / W, w = idx - n * W;
         const int c = c_s[n];
         if (c < S) {
@@ -632,13 +690,45 @@ __global__ __launch_bounds__(256) void compress_slots2_kernel(const CompressPair
             *p = dcat[(long long)b * ldc + idx] * gi_dact(p, fshift);
         }
     }
-    if (blockIdx.y == 0)
-        for (int w = tid; w < W; w += 256) {
+    if (part == 0)
+        for (int w = tid; w < W; w += NT) {
             float z = 0.f;
             for (int n = 0; n < N; ++n)
                 if (c_s[n] >= S) z += dcat[(long long)b * ldc + n * W + w];
             zpart[(long long)b * ldz + w] = z;
         }
+}
+
+__global__ __launch_bounds__(256) void compress_slots2_kernel(const CompressPair a, const int* __restrict__ cidx,
+                                                              int N, int S, long long fshift) {
+    __shared__ int c_s[GI_MAX_NODES];
+    compress_slots2_body<256>(a, cidx, N, S, fshift, c_s, blockIdx.x, blockIdx.y, gridDim.y, blockIdx.z);
+}
+
+// Backward readout glue in ONE launch (GI_GLUE_READOUT_BWD): the gather workgroups, then the compress workgroups
+// (graph b fastest, then the part, then the problem).  They write disjoint rows and disjoint partial-sum buffers.
+struct GatherBwdArgs {
+    float* en; float* emb; int ld; const int* mask; int N, G, S; float big;
+    const float* dg0; int ld0; const float* dg1; int ld1; const float* dg2; int ld2; float* zpart;
+};
+
+template <int GI_GATHER_GC>
+__global__ __launch_bounds__(GI_GATHER_GC) void readout_glue_bwd_kernel(const GatherBwdArgs g, const CompressPair a,
+                                                                        const int* __restrict__ cidx, int B,
+                                                                        int n_gather, int parts, long long fshift) {
+    extern __shared__ float gather_lds[];
+    __shared__ int c_s[GI_MAX_NODES];
+    __shared__ float pen_s[GI_MAX_NODES];
+    int id = blockIdx.x;
+    if (id < n_gather) {                                   // block-uniform
+        const int chunk = id / B, b = id - chunk * B;
+        gather_bwd_body<GI_GATHER_GC>(b, chunk * GI_GATHER_GC, gather_lds, c_s, pen_s, g.en, g.emb, g.ld, cidx, g.mask,
+                                      g.N, g.G, g.S, g.big, g.dg0, g.ld0, g.dg1, g.ld1, g.dg2, g.ld2, g.zpart, fshift);
+        return;
+    }
+    id -= n_gather;
+    const int b = id % B, rest = id / B;
+    compress_slots2_body<GI_GATHER_GC>(a, cidx, g.N, g.S, fshift, c_s, b, rest % parts, parts, rest / parts);
 }
 
 // out[c] = (sum_r part[r, c]) * selu'(y[c]); 64 columns per block, 16 row groups, fixed tree.
@@ -766,15 +856,30 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 }
 
 // ---- KL-divergence training loss (Workflow.py:850-858), forward + gradient in one pass ----------
+// Ticket words of gi_kl_loss_mean: two rings of GI_KL_TICKETS zero-initialised words per device (a __device__ array:
+// each device has its own copy).  A call takes the next word of its ring; the kernel leaves it zero again.  Eager calls
+// and calls recorded into a graph draw from different rings, so a replayed graph never shares a word with an eager call
+// on another stream.
+#define GI_KL_TICKETS 64
+__device__ unsigned g_kl_tickets[2 * GI_KL_TICKETS];
+
 // one workgroup per graph: t = target / sum(target); logp = log_softmax(out);
 // row_loss = sum_j xlogy(t_j, t_j) - t_j * logp_j;  d_out_j = (softmax_j * sum(t) - t_j) / B
-template <typename T, int NT>
+// MEAN (GI_GLUE_LOSS_MEAN, gi_kl_loss_mean): the batch mean in the same launch.  Every workgroup publishes its row loss
+// and takes a ticket from word `slot` of g_kl_tickets (zero, and nobody else's while the launch runs); the holder of the
+// last one sees every row loss and runs mean_rows_kernel's reduction on its first 256 threads — the same strided sums,
+// shuffle tree and (r0 + r1) + (r2 + r3) — then leaves the word zero again.  Nobody waits: a workgroup that is not last
+// exits.  Measured slower than the two launches (29 against 8 us back to back at B = 1000: a device-scope release per
+// workgroup and 1000 tickets on one word, profiles/glue/README.md), so the switch is off by default.
+template <typename T, int NT, bool MEAN>
 __global__ __launch_bounds__(NT) void kl_loss_kernel(const float* __restrict__ out, int ldo,
                                                       const T* __restrict__ tgt, int ldt,
                                                       int width, float inv_b,
-                                                      float* __restrict__ row_loss,
-                                                      float* __restrict__ d_out, int ldd) {
+                                                      float* row_loss,
+                                                      float* __restrict__ d_out, int ldd,
+                                                      int slot, float* loss_mean) {
     __shared__ float red[NT / 64];
+    __shared__ int last_s;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const float* o = out + (long long)b * ldo;
     const T* t = tgt + (long long)b * ldt;
@@ -812,6 +917,29 @@ __global__ __launch_bounds__(NT) void kl_loss_kernel(const float* __restrict__ o
     }
     loss = block_reduce(loss, false);
     if (tid == 0) row_loss[b] = loss;
+    if (!MEAN) return;
+    if (tid == 0) {
+        unsigned* ticket = g_kl_tickets + slot;
+        // release: the row loss is visible device-wide before the ticket is; acquire: so are the earlier holders' rows
+        const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        const int last = t == gridDim.x - 1;
+        if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // every ticket is taken
+        last_s = last;
+    }
+    __syncthreads();
+    if (!last_s) return;                                   // block-uniform
+    if (tid < 256) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // (the other threads did not take the ticket themselves)
+        const int B = gridDim.x;
+        float acc = 0.f;
+        for (int i = tid; i < B; i += 256)
+            acc += __hip_atomic_load(row_loss + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) acc += __shfl_xor(acc, s);
+        if (lane == 0) red[wid] = acc;
+    }
+    __syncthreads();
+    if (tid == 0) *loss_mean = ((red[0] + red[1]) + (red[2] + red[3])) * inv_b;
 }
 
 // loss = (sum_b row_loss[b]) * inv_b in a fixed order (one workgroup; deterministic)
@@ -1309,6 +1437,78 @@ extern "C" int gi_compress_slots2_f(float* t1a, int ldta, int Wa, const float* d
     return gi_launch_status();
 }
 
+// ---- small launches taken off the step's single-queue path (GI_GLUE) -------------------------------------------------
+// Bit mask like GI_FUSE with a word of its own (environment GI_GLUE=<int>, default GI_GLUE_DEFAULT; gi_glue_set
+// overrides it at run time: the tests compare both settings in one process).
+static std::atomic<int> g_glue_override{-1};
+extern "C" int gi_glue_flags(void) {
+    static const int v = getenv("GI_GLUE") ? atoi(getenv("GI_GLUE")) : GI_GLUE_DEFAULT;
+    const int o = g_glue_override.load(std::memory_order_relaxed);
+    return o >= 0 ? o : v;
+}
+extern "C" int gi_glue_set(int mask) {
+    g_glue_override.store(mask < 0 ? -1 : mask, std::memory_order_relaxed);
+    return gi_glue_flags();
+}
+
+extern "C" int gi_readout_glue_fwd(const float* en, const float* emb, int ld, const int* cidx, const int* node_mask,
+                                   int B, int N, int G, float big, float* out0, int ld0, float* out1, int ld1,
+                                   float* out2, int ld2, const float* t1a, int ldta, int Wa, float* cata, int ldca,
+                                   const float* t1b, int ldtb, int Wb, float* catb, int ldcb, void* stream) {
+    (void)hipGetLastError();   // drop stale errors of earlier, unrelated runtime calls
+    if (B <= 0) return 0;
+    if (!en || !emb || !cidx || !node_mask || N <= 0 || N > GI_MAX_NODES || G <= 0 || ld < G) return GI_EINVAL;
+    if (!t1a || !t1b || !cata || !catb || Wa <= 0 || Wb <= 0 || ldta < Wa || ldtb < Wb || ldca < N * Wa ||
+        ldcb < N * Wb)
+        return GI_EINVAL;
+    const GatherFwdArgs g{en, emb, ld, node_mask, N, G, big, out0, ld0, out1, ld1, out2, ld2};
+    ExpandPair a;
+    a.t1[0] = t1a; a.t1[1] = t1b; a.ldt[0] = ldta; a.ldt[1] = ldtb; a.W[0] = Wa; a.W[1] = Wb;
+    a.cat[0] = cata; a.cat[1] = catb; a.ldc[0] = ldca; a.ldc[1] = ldcb;
+    const long long total_a = (long long)B * N * Wa, total = total_a + (long long)B * N * Wb;
+    const int GC = N > 112 ? 32 : 64;
+    const long long n_gather = (long long)B * gi_cdiv(G, GC), blocks = n_gather + (total + 255) / 256;
+    if (blocks > 0x7fffffffLL) return GI_ELIMIT;
+    if (GC == 32)
+        hipLaunchKernelGGL(readout_glue_fwd_kernel<32>, dim3((unsigned)blocks), dim3(32), sizeof(float) * 2 * N * 32,
+                           (hipStream_t)stream, g, a, cidx, B, (int)n_gather, total_a, total);
+    else
+        hipLaunchKernelGGL(readout_glue_fwd_kernel<64>, dim3((unsigned)blocks), dim3(64), sizeof(float) * 2 * N * 64,
+                           (hipStream_t)stream, g, a, cidx, B, (int)n_gather, total_a, total);
+    return gi_launch_status();
+}
+
+extern "C" int gi_readout_glue_bwd_f(float* en, float* emb, int ld, const int* cidx, const int* node_mask, int B,
+                                     int N, int G, int S, float big, const float* dg0, int ld0, const float* dg1,
+                                     int ld1, const float* dg2, int ld2, float* zpart, float* t1a, int ldta, int Wa,
+                                     const float* dcata, int ldca, float* zparta, int ldza, float* t1b, int ldtb,
+                                     int Wb, const float* dcatb, int ldcb, float* zpartb, int ldzb, long long fshift,
+                                     void* stream) {
+    (void)hipGetLastError();   // drop stale errors of earlier, unrelated runtime calls
+    if (B <= 0) return 0;
+    if (!en || !emb || !cidx || !node_mask || !zpart || N <= 0 || N > GI_MAX_NODES || G <= 0) return GI_EINVAL;
+    if (!t1a || !t1b || !dcata || !dcatb || !zparta || !zpartb || Wa <= 0 || Wb <= 0 || ldza < Wa || ldzb < Wb)
+        return GI_EINVAL;
+    const GatherBwdArgs g{en, emb, ld, node_mask, N, G, S, big, dg0, ld0, dg1, ld1, dg2, ld2, zpart};
+    CompressPair a;
+    a.t1[0] = t1a; a.t1[1] = t1b; a.ldt[0] = ldta; a.ldt[1] = ldtb; a.W[0] = Wa; a.W[1] = Wb;
+    a.dcat[0] = dcata; a.dcat[1] = dcatb; a.ldc[0] = ldca; a.ldc[1] = ldcb;
+    a.zpart[0] = zparta; a.zpart[1] = zpartb; a.ldz[0] = ldza; a.ldz[1] = ldzb;
+    const int GC = N > 112 ? 32 : 64;
+    const int Wmax = Wa > Wb ? Wa : Wb;
+    // the elements a 256-thread workgroup of gi_compress_slots2_f takes, over 256 / GC workgroups of GC threads
+    const int parts = ((long long)N * Wmax >= 4096 ? 4 : 1) * (256 / GC);
+    const long long n_gather = (long long)B * gi_cdiv(G, GC), blocks = n_gather + 2LL * B * parts;
+    if (blocks > 0x7fffffffLL) return GI_ELIMIT;
+    if (GC == 32)
+        hipLaunchKernelGGL(readout_glue_bwd_kernel<32>, dim3((unsigned)blocks), dim3(32), sizeof(float) * 2 * N * 32,
+                           (hipStream_t)stream, g, a, cidx, B, (int)n_gather, parts, fshift);
+    else
+        hipLaunchKernelGGL(readout_glue_bwd_kernel<64>, dim3((unsigned)blocks), dim3(64), sizeof(float) * 2 * N * 64,
+                           (hipStream_t)stream, g, a, cidx, B, (int)n_gather, parts, fshift);
+    return gi_launch_status();
+}
+
 extern "C" int gi_colsum(const float* part, int ldp, int rows, int cols, const float* y,
                          float* out, void* stream) {
     (void)hipGetLastError();   // drop stale errors of earlier, unrelated runtime calls
@@ -1401,15 +1601,16 @@ extern "C" int gi_kl_loss(const float* out, int ldo, const void* target, int tgt
     if (!out || !target || !row_loss || width <= 0 || ldo < width || ldt < width) return GI_EINVAL;
     const hipStream_t st = (hipStream_t)stream;
     // rows wider than 2048 logits (ZINC / ChEMBL shapes: 4 k - 10 k) get 1024 threads each
-#define GI_KL_LAUNCH(T_, NT_)                                                                     \
-    hipLaunchKernelGGL((kl_loss_kernel<T_, NT_>), dim3(B), dim3(NT_), 0, st, out, ldo,            \
-                       (const T_*)target, ldt, width, 1.f / (float)B, row_loss, d_out, ldd)
+#define GI_KL_LAUNCH(T_, NT_, MEAN_, TICKET_, LOSS_)                                              \
+    hipLaunchKernelGGL((kl_loss_kernel<T_, NT_, MEAN_>), dim3(B), dim3(NT_), 0, st, out, ldo,     \
+                       (const T_*)target, ldt, width, 1.f / (float)B, row_loss, d_out, ldd, TICKET_, LOSS_)
     if (tgt_dtype == GI_DTYPE_F32) {
-        if (width > 2048) GI_KL_LAUNCH(float, 1024); else GI_KL_LAUNCH(float, 256);
+        if (width > 2048) GI_KL_LAUNCH(float, 1024, false, 0, nullptr);
+        else GI_KL_LAUNCH(float, 256, false, 0, nullptr);
     } else if (tgt_dtype == GI_DTYPE_I8) {
-        if (width > 2048) GI_KL_LAUNCH(signed char, 1024); else GI_KL_LAUNCH(signed char, 256);
+        if (width > 2048) GI_KL_LAUNCH(signed char, 1024, false, 0, nullptr);
+        else GI_KL_LAUNCH(signed char, 256, false, 0, nullptr);
     }
-#undef GI_KL_LAUNCH
     else
         return GI_EINVAL;
     if (loss_mean)       // the batch mean right behind the row kernel, fixed summation order
@@ -1417,6 +1618,31 @@ extern "C" int gi_kl_loss(const float* out, int ldo, const void* target, int tgt
                            loss_mean);
     return gi_launch_status();
 }
+
+extern "C" int gi_kl_loss_mean(const float* out, int ldo, const void* target, int tgt_dtype, int ldt, int B,
+                               int width, float* row_loss, float* d_out, int ldd, float* loss_mean,
+                               void* stream) {
+    (void)hipGetLastError();
+    if (B <= 0) return 0;
+    if (!out || !target || !row_loss || !loss_mean || width <= 0 || ldo < width || ldt < width) return GI_EINVAL;
+    const hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
+    const int ring = cap == hipStreamCaptureStatusActive ? 1 : 0;
+    static std::atomic<unsigned> next[2];
+    const int ticket = ring * GI_KL_TICKETS + (int)(next[ring].fetch_add(1u) % GI_KL_TICKETS);
+    if (tgt_dtype == GI_DTYPE_F32) {
+        if (width > 2048) GI_KL_LAUNCH(float, 1024, true, ticket, loss_mean);
+        else GI_KL_LAUNCH(float, 256, true, ticket, loss_mean);
+    } else if (tgt_dtype == GI_DTYPE_I8) {
+        if (width > 2048) GI_KL_LAUNCH(signed char, 1024, true, ticket, loss_mean);
+        else GI_KL_LAUNCH(signed char, 256, true, ticket, loss_mean);
+    }
+    else
+        return GI_EINVAL;
+    return gi_launch_status();
+}
+#undef GI_KL_LAUNCH
 
 
 // ---- largest magnitude of several tensors (the weights of the fp16x2 GEMM launches, gi_x2.h) -----------------------

@@ -270,6 +270,15 @@ SIGNATURES = {
     "gi_expand_slots2": (ci, [vp, ci, ci, vp, ci, vp, ci, ci, vp, ci, vp, ci, ci, vp]),
     "gi_compress_slots2_f": (ci, [vp, ci, ci, vp, ci, vp, ci, vp, ci, ci, vp, ci, vp, ci, vp, ci, ci, ci,
                                   cll, vp]),
+    "gi_glue_flags": (ci, []),
+    "gi_glue_set": (ci, [ci]),
+    "gi_readout_glue_fwd": (ci, [vp, vp, ci, vp, vp, ci, ci, ci, C.c_float, vp, ci, vp, ci, vp, ci,
+                                 vp, ci, ci, vp, ci, vp, ci, ci, vp, ci, vp]),
+    "gi_readout_glue_bwd_f": (ci, [vp, vp, ci, vp, vp, ci, ci, ci, ci, C.c_float, vp, ci, vp, ci, vp, ci, vp,
+                                   vp, ci, ci, vp, ci, vp, ci, vp, ci, ci, vp, ci, vp, ci, cll, vp]),
+    "gi_kl_loss_mean": (ci, [vp, ci, vp, ci, ci, ci, ci, vp, vp, ci, vp, vp]),
+    "gi_gru_forward_agg": (ci, [vp, ci, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, ci, ci,
+                                vp]),
     "gi_route_plan_ws_bytes": (cll, [C.POINTER(RouteDims)]),
     "gi_route_rows_ws_bytes": (cll, [ci, ci]),
     "gi_route_plan": (ci, [C.POINTER(RouteDims), vp, vp, vp, vp, vp, vp, vp]),
@@ -290,6 +299,7 @@ SIGNATURES = {
                             vp, vp, vp, vp, vp, vp, vp, vp, vp]),
 }
 FUSE_GATES_V4, FUSE_DH_SCATTER, FUSE_TIER2_DSELU, FUSE_SLOTS = 1, 2, 4, 8  # GI_FUSE_*
+GLUE_READOUT_FWD, GLUE_READOUT_BWD, GLUE_LOSS_MEAN, GLUE_GRU_AGG = 1, 2, 4, 8  # GI_GLUE_*
 
 _lib = None
 

@@ -19,8 +19,10 @@ def apd_kl_loss_torch(output: torch.Tensor, target_output: torch.Tensor) -> torc
 
 
 class _FusedKL(torch.autograd.Function):
-    """Two launches forward (row kernel + fixed-order batch mean), one backward (d_out scaled in place
-    by the upstream scalar, read on the device) — no torch glue kernels on the step's critical path.
+    """Two launches forward (``gi_kl_loss``: row kernel + fixed-order batch mean) or, with the switch
+    ``GI_GLUE_LOSS_MEAN`` on (off by default: measured slower), one (``gi_kl_loss_mean``: the row kernel's
+    last workgroup to finish takes the mean in the same order, the same bits); one backward (d_out scaled in
+    place by the upstream scalar, read on the device) — no torch glue kernels on the step's critical path.
     Single backward only: the gradient buffer is consumed (a second `backward(retain_graph=True)` raises
     instead of returning a doubly scaled gradient)."""
 
@@ -40,10 +42,11 @@ class _FusedKL(torch.autograd.Function):
         buf = torch.empty(B + 1, dtype=torch.float32, device=out.device)    # row losses | mean
         need_grad = ctx.needs_input_grad[0]
         d_out = torch.empty_like(out) if need_grad else None
-        L.check(lib.gi_kl_loss(out.data_ptr(), out.stride(0), tgt.data_ptr(), tdt, tgt.stride(0), B, W,
-                               buf.data_ptr(), d_out.data_ptr() if need_grad else None,
-                               d_out.stride(0) if need_grad else 0, buf.data_ptr() + 4 * B,
-                               torch.cuda.current_stream(out.device).cuda_stream), "gi_kl_loss")
+        kl = lib.gi_kl_loss_mean if lib.gi_glue_flags() & L.GLUE_LOSS_MEAN else lib.gi_kl_loss
+        L.check(kl(out.data_ptr(), out.stride(0), tgt.data_ptr(), tdt, tgt.stride(0), B, W,
+                   buf.data_ptr(), d_out.data_ptr() if need_grad else None,
+                   d_out.stride(0) if need_grad else 0, buf.data_ptr() + 4 * B,
+                   torch.cuda.current_stream(out.device).cuda_stream), "gi_kl_loss")
         ctx.d_out = d_out
         return buf[B]
 

@@ -26,6 +26,7 @@
  *       GI_X2=0                 those launches as three bf16 planes (six products) instead of two scaled fp16 planes
  *                               (three products, GI_GEMM_X2; gi_x2_enable); also puts the chains back on fp32
  *       GI_FUSE=<mask>          launch-count reductions (gi_fuse_flags, default 15)
+ *       GI_GLUE=<mask>          small launches folded into their neighbours (gi_glue_flags, default GI_GLUE_DEFAULT)
  *       GI_B3P=0, GI_B3V=0      initial values of gi_b3p_enable / gi_b3v_enable (default 1)
  *       GI_B3P_ALL=1            forward / dgrad launches on the software-pipelined kernel whatever their tile count
  *                               (default: from 2.5 tiles per CU on; gi_b3p_enable)
@@ -551,6 +552,50 @@ int gi_compress_slots2_f(float* t1a, int ldta, int Wa, const float* dcata, int l
                          float* t1b, int ldtb, int Wb, const float* dcatb, int ldcb, float* zpartb, int ldzb,
                          const int* cidx, int B, int N, int S, long long fshift, void* stream);
 
+/* Small launches taken off the single-queue path of the training step.  gi_glue_flags() = the bit mask
+ * in use: environment GI_GLUE, default GI_GLUE_DEFAULT; a word of its own, GI_FUSE and GI_FUSE_DEFAULT are unchanged.
+ * gi_glue_set(mask) overrides it for the process (mask < 0: back to the environment's value) and returns the mask then
+ * in use.  Every variant performs the floating-point operations of the launches it replaces in the same order: results
+ * are bit for bit the same (tests/test_glue_gpu.py).
+ *   READOUT_FWD  gi_gather_readout_fwd + gi_expand_slots2 of the GGNN / AttentionGGNN forward in one launch
+ *   READOUT_BWD  gi_gather_readout_bwd_f + gi_compress_slots2_f of their backward in one launch
+ *   LOSS_MEAN    the batch mean of the KL loss inside the row kernel's launch (gi_kl_loss_mean, loss.py); measured slower
+ *                than the two launches it replaces and therefore not in the default
+ *   GRU_AGG      GGNN passes >= 1: the sum of the incoming messages (gi_seg_sum) inside the fused GRU update's launch,
+ *                where that launch has no more workgroups (64 rows x 64 hidden units) than the device has CUs */
+#define GI_GLUE_READOUT_FWD 1
+#define GI_GLUE_READOUT_BWD 2
+#define GI_GLUE_LOSS_MEAN   4
+#define GI_GLUE_GRU_AGG     8
+/* Measured on the headline step (four rounds of alternating runs, profiles/glue/README.md): 11 -> 1.765 - 1.774 ms
+ * against 1.779 - 1.788 for the parent. */
+#define GI_GLUE_DEFAULT     11
+int gi_glue_flags(void);
+int gi_glue_set(int mask);
+/* gi_gather_readout_fwd(en, ..., out2, ld2) and gi_expand_slots2(t1a, ..., catb, ldcb, cidx, B, N) in one launch: the
+ * gather's workgroups followed by the expand's (the two read only tier-1 outputs and write disjoint memory). */
+int gi_readout_glue_fwd(const float* en, const float* emb, int ld, const int* cidx, const int* node_mask,
+                        int B, int N, int G, float big, float* out0, int ld0, float* out1, int ld1,
+                        float* out2, int ld2, const float* t1a, int ldta, int Wa, float* cata, int ldca,
+                        const float* t1b, int ldtb, int Wb, float* catb, int ldcb, void* stream);
+/* gi_gather_readout_bwd_f(en, ..., zpart, fshift) and gi_compress_slots2_f(t1a, ..., zpartb, ldzb, cidx, B, N, S, fshift)
+ * in one launch (disjoint rows, disjoint partial-sum buffers; the column sums stay with gi_colsum_multi). */
+int gi_readout_glue_bwd_f(float* en, float* emb, int ld, const int* cidx, const int* node_mask, int B,
+                          int N, int G, int S, float big, const float* dg0, int ld0, const float* dg1,
+                          int ld1, const float* dg2, int ld2, float* zpart, float* t1a, int ldta, int Wa,
+                          const float* dcata, int ldca, float* zparta, int ldza, float* t1b, int ldtb,
+                          int Wb, const float* dcatb, int ldcb, float* zpartb, int ldzb, long long fshift,
+                          void* stream);
+/* gi_seg_sum(vals, ldv, perm, seg_off, rows, M, agg, lda, 0) followed by gi_gru_forward(agg, ...) in one launch: every
+ * workgroup of the fused update first sums the incoming messages of its own 64 rows into LDS, in gi_seg_sum's order;
+ * the workgroups of the first unit tile also write them to agg [rows, lda] (the backward reads it).  rows_dev (device
+ * int, or NULL): min(rows, *rows_dev) rows are processed.  Conditions of gi_gru_forward, and ldv % 4 == 0, 16-byte
+ * aligned vals; GI_EINVAL otherwise. */
+int gi_gru_forward_agg(const float* vals, int ldv, const int* perm, float* agg, int lda, const float* hx, int ldh,
+                       const float* Wih, const float* Whh, const float* bih, const float* bhh, float* gi, float* gh,
+                       int ldg, float* hx_new, const int* seg_off, int rows, const int* rows_dev, int H, int M,
+                       void* stream);
+
 /* MNN message function, aggregate first (gnn/mpnn.py:58-63 + the sum of gnn/summation_mpnn.py:141):
  *   out[c, k * Fe + t] = sum over the dst-CSR slots s in [seg_off[c], seg_off[c+1]) whose message row u = in_perm[s]
  *                        has bond type t (type_off buckets) of h[u_src[u], k],     c < rows, k < H
@@ -620,6 +665,15 @@ int gi_adam_step(float* p, const float* g, float* m, float* v, long long n, doub
  * fixed order.  All-zero target rows give NaN like the reference. */
 int gi_kl_loss(const float* out, int ldo, const void* target, int tgt_dtype, int ldt, int B,
                int width, float* row_loss, float* d_out, int ldd, float* loss_mean, void* stream);
+/* The same in ONE launch (loss_mean required): the workgroup that finishes last sums the row losses, in the order of
+ * gi_kl_loss's second launch — the same bits.  No workgroup waits for another.  The workgroups count themselves on a
+ * word owned by the library, which the last one leaves zero again.  Each call takes the next word of a ring of 64 per
+ * device; calls recorded into a graph use a second ring of 64, so a replayed graph never shares a word with an eager
+ * call.  Limit: results are undefined when two launches on the same word run at the same time, that is with more than
+ * 64 eager calls in flight on a device at once (on 65 or more streams), when more than 64 calls were recorded and two
+ * graphs 64 recordings apart replay concurrently, or when ONE recorded call replays concurrently with itself. */
+int gi_kl_loss_mean(const float* out, int ldo, const void* target, int tgt_dtype, int ldt, int B,
+                    int width, float* row_loss, float* d_out, int ldd, float* loss_mean, void* stream);
 
 /* Validation NLL of the correct actions, Analyzer.get_validation_likelihood (Analyzer.py:754-774), for one
  * batch in two launches with no host read-back.  Per row b of out [B, width] (row stride ldo) and target
