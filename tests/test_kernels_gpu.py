@@ -10,6 +10,7 @@ import torch
 from graphinvent_amd import lib as L
 from graphinvent_amd import ops, synthetic
 from tests import ref_dataflow as D
+from tests.compact_cases import _compact_case
 from tests.golden.spec import tiny_inputs
 
 pytestmark = pytest.mark.gpu
@@ -23,41 +24,6 @@ def rel(a, b):
 
 
 # ------------------------------------------------------------------------------------------------
-def _compact_case(n8, e8, H=16, nodedup=False):
-    ref = D.compact(n8, e8, nodedup=nodedup)
-    g, hx0 = ops.compact(torch.from_numpy(n8).float().to(DEV), torch.from_numpy(e8).float().to(DEV), H,
-                         class_csr=True, nodedup=nodedup)
-    if nodedup:      # every slot its own row, every edge its own message row, no pass-0 rows
-        assert (g.S, g.U, g.D0) == (n8.shape[0] * n8.shape[1], g.E, 0)
-        assert np.array_equal(g.mu_off.cpu().numpy(), np.arange(g.E + 1))
-    assert (g.S, g.E, g.U) == (ref["S"], ref["E"], ref["U"])
-    assert list(g.Ut) == np.diff(ref["type_off"]).tolist()
-    for name in ("cidx", "slot_of", "u_src", "in_perm", "mu_off", "mu_dst", "mu_slot", "out_perm",
-                 "type_off"):
-        got = getattr(g, name).cpu().numpy()
-        assert np.array_equal(got, ref[name]), name            # integer work: bit-exact
-    for name in ("seg_off", "src_off"):                        # [R + 1] = [S + 2] entries
-        assert np.array_equal(getattr(g, name).cpu().numpy(), ref[name]), name
-    # pass-0 rows: (feature class, bond type) pairs, their gather rows and the edge-count matrix
-    assert g.D0 == ref["D0"]
-    if g.D0:
-        assert np.array_equal(g.type_off0.cpu().numpy(), ref["type_off0"])
-        assert np.array_equal(g.d_src.cpu().numpy(), ref["d_src"])
-        assert np.array_equal(g.cmat.cpu().numpy()[:, :g.D0], ref["cmat"])
-        assert float(g.cmat.sum()) == g.E
-        # AttentionGGNN's pass 0: edge slot -> pass-0 row, and the row -> edge slots CSR (stable order)
-        assert g.class_csr
-        for name in ("e2d", "cls_off", "cls_edges"):
-            assert np.array_equal(getattr(g, name).cpu().numpy(), ref[name]), name
-    assert np.array_equal(g.node_mask.cpu().numpy(), ref["node_mask"].astype(np.int32))
-    B, N, Fn = n8.shape
-    x = np.zeros((g.S + 1, hx0.shape[1]), dtype=np.float32)
-    rows = n8.reshape(B * N, Fn)[ref["slot_of"]].astype(np.float32)
-    x[:g.S, :Fn] = rows
-    x[:g.S, H:H + Fn] = rows
-    assert np.array_equal(hx0.cpu().numpy(), x)
-
-
 def test_compact_tiny_edge_cases():
     n8, e8, _ = tiny_inputs()
     _compact_case(n8, e8)
