@@ -21,6 +21,13 @@ device (``gi_mol_canon``, ``gi_mol_unique``, ``gi_mol_seen_add``): the reference
 (util.py:549-585) and ``fraction_unique`` (Analyzer.py:480-499) without a SMILES string.  Identity here is isomorphism
 of the labelled graph (node feature rows, bond types), see ``canonical``.
 
+``fingerprint`` / ``FingerprintSet`` / ``similarity`` / ``KernelModel`` / ``activity`` / ``internal_diversity`` SCORE
+molecules on the device (``gi_mol_fingerprint``, ``gi_fp_compare``): the reference's ``"activity"`` score component
+(ScoringFunction.py:145-192, one RDKit Morgan fingerprint and one scikit-learn ``predict_proba`` per molecule on the
+host) over a Morgan-style fingerprint of the labelled graph — NOT RDKit's ECFP bits, see ``fingerprint`` — and
+nearest-neighbour similarity to a stored set; ``target_size_score`` / ``compute_score`` restate the rest of
+``ScoringFunction.compute_score`` in plain torch.
+
 ``decode(nodes, edges, n_nodes, groups)`` is one launch (``gi_mol_decode``) that writes what ``_graph_to_mol`` reads
 out of the tensors: per atom the index inside each one-hot segment, per graph the bond triples in
 ``torch.nonzero``'s order, and a status word for what the reference would misread or raise on.  ``.host()`` brings all
@@ -805,3 +812,339 @@ def fraction_valid(nodes, edges=None, n_nodes=None, rules=None, *, termination=N
     some = c[3] > 0
     return (torch.where(some, c[0] / c[3], zero), torch.where(c[1] > 0, c[2] / c[1], zero),
             torch.where(some, c[1] / c[3], zero))
+
+
+# ---- molecule scores: fingerprints, similarity, activity ----------------------------------------------------------
+_FP_KINDS = {"tanimoto": L.FP_TANIMOTO, "rbf": L.FP_RBF, "linear": L.FP_LINEAR}
+
+
+def _check_n_bits(what: str, n_bits) -> int:
+    if (not isinstance(n_bits, (int, np.integer)) or isinstance(n_bits, bool)
+            or not L.FP_MIN_BITS <= n_bits <= L.FP_MAX_BITS or n_bits & (n_bits - 1)):
+        raise ValueError(f"{what}: n_bits must be a power of two in [{L.FP_MIN_BITS}, {L.FP_MAX_BITS}], got {n_bits!r}")
+    return int(n_bits)
+
+
+class Fingerprints(_ResultBuffer):
+    """What ``fingerprint`` wrote, on the device: ``bits`` [G, n_bits / 32] int32 (bit b of a row is bit ``b & 31`` of
+    word ``b >> 5``), ``popcount`` / ``status`` [G] int32 and, if asked for, ``atom_id`` [G, N, 2] int32 (the low and
+    high halves of every atom's last identifier, -1 past n; ``None`` otherwise); ``host()`` -> ``{name: numpy array}``."""
+
+    def __init__(self, buf: torch.Tensor, G: int, N: int, W: int, ids: bool):
+        super().__init__(buf, G, N, W, ids)
+        self.N, self.n_bits = N, 32 * W
+        if not ids:
+            self.atom_id = None
+
+    @staticmethod
+    @functools.lru_cache(maxsize=64)
+    def layout(G: int, N: int, W: int, ids: bool) -> dict:
+        return _pack(("bits", "int32", (G, W)), ("popcount", "int32", (G,)), ("status", "int32", (G,)),
+                     *([("atom_id", "int32", (G, N, 2))] if ids else []))
+
+    @staticmethod
+    def _host_result(a):
+        return a
+
+
+def fingerprint(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Optional[torch.Tensor], rules: ValenceRules, *,
+                radius: int = 2, n_bits: int = 2048, atom_ids: bool = False) -> Fingerprints:
+    """A packed circular fingerprint of every molecule in one launch (``gi_mol_fingerprint``), with no RDKit and no
+    read-back; inputs as ``validity`` (the node row's segments and the bond orders from ``rules``).
+
+    **THIS IS A MORGAN-STYLE FINGERPRINT OF THE LABELLED GRAPH, NOT RDKit's ECFP BITS.**  The atom invariants differ (atom
+    type, formal charge, number of bonded partners, twice the bond-order sum; **no ring membership, no isotope,
+    hydrogens only through the bond-order sum**), the hash differs, **duplicate substructures are not removed and no
+    aromaticity is perceived**.  A QSAR model must be trained on THESE fingerprints, which this function produces for any
+    stored int8 molecules (``routes.molecules_from_rows``).  Guaranteed: two isomorphic labelled molecules get equal rows
+    in any node order, and two atoms get equal identifiers after round r exactly when their radius-r labelled
+    neighbourhoods are 1-WL-equivalent (up to 64-bit hash collisions).
+
+    Per atom i < n, in 64-bit wrap-around integers (``tests/fingerprint_model.py`` is the numpy specification):
+    ``id_0 = mix64(K0 + type + 256 charge + 2**16 degree + 2**24 o2)``, then for r = 1 .. ``radius`` (0 to 4)
+    ``id_r[i] = mix64(mix64(id_{r-1}[i] + r) + sum over bonds (t, j) of mix64(id_{r-1}[j] ^ K1 order2[t]))``; bit
+    ``id_r[i] & (n_bits - 1)`` of the row is set for every r and i.  ``n_bits``: a power of two in [64, 4096].
+
+    ``status`` [G]: 0, or the malformed bits of ``validity`` (``MALFORMED_BITS``), ``VAL_EMPTY``, ``VAL_SELF_LOOP``; such
+    a molecule gets an ALL-ZERO row (and scores 0 in ``activity``: the reference's ``except: pass``).  ``.host()`` is one
+    copy and one synchronisation.  G = 0 is answered without a launch."""
+    what = "fingerprint"
+    if not isinstance(rules, ValenceRules):
+        raise TypeError(f"{what}: rules must be a ValenceRules, got {type(rules).__name__}")
+    n_bits = _check_n_bits(what, n_bits)
+    if not isinstance(radius, (int, np.integer)) or isinstance(radius, bool) or not 0 <= radius <= L.FP_MAX_RADIUS:
+        raise ValueError(f"{what}: radius must be an integer in [0, {L.FP_MAX_RADIUS}], got {radius!r}")
+    G, N, Fn, Fe, dtype, n_nodes, nn_bytes, _ = _check_inputs(what, nodes, edges, n_nodes, None, False)
+    dev = nodes.device
+    A, Cn, H = rules.groups
+    if A + Cn + H > Fn:
+        raise ValueError(f"{what}: the rules' segments {rules.groups} do not fit node rows of Fn = {Fn}")
+    if rules.device is None:
+        raise RuntimeError(f"{what}: the rules were built with device=None and hold no device tables (no CPU fallback)")
+    order2 = rules.order2(Fe)
+    if order2.device != dev:
+        raise ValueError(f"{what}: the molecules are on {dev}, the rules' tables on {order2.device}")
+    W = n_bits // 32
+    res = Fingerprints.empty(dev, G, N, W, bool(atom_ids))
+    if G > 0:
+        out = res._ptrs()
+        with torch.cuda.device(dev):
+            L.check(L.load().gi_mol_fingerprint(
+                G, N, Fn, Fe, nodes.data_ptr(), edges.data_ptr(), dtype,
+                None if n_nodes is None else n_nodes.data_ptr(), nn_bytes, A, Cn, H, order2.data_ptr(), int(radius),
+                n_bits, out["bits"], out["popcount"], out["status"], out.get("atom_id"),
+                torch.cuda.current_stream(dev).cuda_stream), "gi_mol_fingerprint")
+    return res
+
+
+def _pack_bits(what: str, bits) -> torch.Tensor:
+    """Packed int32 [S, W] (kept) or a 0 / 1 array [S, n_bits] of any other dtype (packed here, on the host) ->
+    a host int32 tensor [S, W]."""
+    if isinstance(bits, torch.Tensor):
+        if bits.dtype == torch.int32:
+            arr = bits
+        else:
+            arr = bits.detach().cpu().numpy()
+    else:
+        arr = np.asarray(bits)
+    if isinstance(arr, np.ndarray):
+        if arr.dtype == np.int32:
+            arr = torch.from_numpy(np.ascontiguousarray(arr))
+        else:
+            if arr.ndim != 2:
+                raise ValueError(f"{what}: bits must be [S, n_bits] (0 / 1) or packed int32 [S, n_bits / 32]")
+            _check_n_bits(what, arr.shape[1])
+            if not np.isin(arr, (0, 1)).all():
+                raise ValueError(f"{what}: an unpacked array must hold only 0 and 1")
+            packed = np.packbits(arr != 0, axis=1, bitorder="little")
+            arr = torch.from_numpy(np.ascontiguousarray(packed).view(np.int32))
+    if arr.dim() != 2:
+        raise ValueError(f"{what}: bits must be [S, n_bits] (0 / 1) or packed int32 [S, n_bits / 32]")
+    _check_n_bits(what, 32 * arr.shape[1])
+    return arr
+
+
+class FingerprintSet:
+    """A stored set of fingerprints on the device (actives, a training set, a model's support vectors): ``bits``
+    [S, n_bits / 32] int32.  Built from packed int32 rows (a tensor or array of dtype int32, e.g. ``Fingerprints.bits``),
+    or from a 0 / 1 array [S, n_bits] of ANY OTHER dtype, which is packed on the host once.  S >= 1."""
+
+    def __init__(self, bits, device="cuda"):
+        what = "FingerprintSet"
+        if isinstance(bits, (Fingerprints, FingerprintSet)):
+            bits = bits.bits
+        rows = _pack_bits(what, bits)
+        if rows.shape[0] < 1:
+            raise ValueError(f"{what}: a set needs at least one row")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError(f"{what} needs a CUDA (ROCm) device, got {self.device}: the MI355X HIP path has no CPU "
+                               "fallback")
+        self.bits = rows.to(self.device).contiguous()
+        if self.bits.data_ptr() % 16:
+            self.bits = self.bits.clone()
+        self.n_bits = 32 * self.bits.shape[1]
+
+    @classmethod
+    def from_molecules(cls, nodes, edges, n_nodes, rules, *, radius: int = 2, n_bits: int = 2048):
+        """The fingerprints of the given molecules as a set, built on the device (rows of malformed or empty molecules
+        are all zero and are never anybody's neighbour)."""
+        return cls(fingerprint(nodes, edges, n_nodes, rules, radius=radius, n_bits=n_bits).bits, device=nodes.device)
+
+    def __len__(self):
+        return self.bits.shape[0]
+
+
+class SetComparison(_ResultBuffer):
+    """What ``similarity`` / ``activity`` wrote, on the device: ``nearest`` / ``common`` / ``union`` [G] int32,
+    ``max_sim`` [G] fp32 and, from ``activity``, ``decision`` / ``proba`` [G] fp32 (``None`` from ``similarity``);
+    ``host()`` -> ``{name: numpy array}``."""
+
+    def __init__(self, buf: torch.Tensor, G: int, scored: bool):
+        super().__init__(buf, G, scored)
+        if not scored:
+            self.decision = self.proba = None
+
+    @staticmethod
+    @functools.lru_cache(maxsize=64)
+    def layout(G: int, scored: bool) -> dict:
+        return _pack(("nearest", "int32", (G,)), ("common", "int32", (G,)), ("union", "int32", (G,)),
+                     ("max_sim", "float32", (G,)),
+                     *([("decision", "float32", (G,)), ("proba", "float32", (G,))] if scored else []))
+
+    @staticmethod
+    def _host_result(a):
+        return a
+
+
+def _compare(what: str, fp, ref: FingerprintSet, weight, kind: int, gamma, intercept, prob_a, prob_b) -> SetComparison:
+    if not isinstance(ref, FingerprintSet):
+        raise TypeError(f"{what}: the set must be a FingerprintSet, got {type(ref).__name__}")
+    query = fp.bits if isinstance(fp, (Fingerprints, FingerprintSet)) else fp
+    if not isinstance(query, torch.Tensor) or query.dtype != torch.int32 or query.dim() != 2:
+        raise TypeError(f"{what}: fp must be a Fingerprints, a FingerprintSet or a packed int32 tensor [G, n_bits / 32]")
+    if not query.is_cuda:
+        raise RuntimeError(f"{what} needs CUDA (ROCm) tensors (fp is on {query.device}): the MI355X HIP path has no CPU "
+                           "fallback")
+    if query.device != ref.bits.device:
+        raise ValueError(f"{what}: fp is on {query.device}, the set on {ref.bits.device}")
+    G, W = query.shape
+    if W != ref.bits.shape[1]:
+        raise ValueError(f"{what}: fp has {32 * W} bits, the set {ref.n_bits}")
+    if not query.is_contiguous() or query.data_ptr() % 16:
+        query = query.clone(memory_format=torch.contiguous_format)
+    dev = query.device
+    res = SetComparison.empty(dev, G, weight is not None)
+    if G > 0:
+        out = res._ptrs()
+        with torch.cuda.device(dev):
+            L.check(L.load().gi_fp_compare(
+                G, len(ref), W, ref.bits.shape[1], query.data_ptr(), ref.bits.data_ptr(),
+                None if weight is None else weight.data_ptr(), kind, gamma, intercept, prob_a, prob_b, out["nearest"],
+                out["common"], out["union"], out["max_sim"], out.get("decision"), out.get("proba"),
+                torch.cuda.current_stream(dev).cuda_stream), "gi_fp_compare")
+    return res
+
+
+def similarity(fp, ref: FingerprintSet) -> SetComparison:
+    """Every fingerprint's nearest neighbour in a stored set, by Tanimoto, in one launch (``gi_fp_compare``) with no
+    read-back.  ``fp``: ``fingerprint``'s result, a ``FingerprintSet`` or a packed int32 device tensor [G, n_bits / 32].
+    ``nearest`` [G]: the set row of the largest ``c / u`` (c the common bits, u the union; decided in integers, ties to
+    the lowest row), -1 for an all-zero fingerprint; ``common`` / ``union`` its c and u; ``max_sim`` = c / u in fp32."""
+    return _compare("similarity", fp, ref, None, L.FP_TANIMOTO, 0.0, 0.0, 0.0, 0.0)
+
+
+class KernelModel:
+    """A two-class kernel model over fingerprints (a support vector classifier): ``decision(q) = intercept + sum_s
+    dual_coef[s] K(q, support[s])`` with ``K`` = Tanimoto (``"tanimoto"``), ``exp(-gamma |q - s|**2)`` (``"rbf"``,
+    needs ``gamma``) or the common bits (``"linear"``), and ``proba = 1 / (1 + exp(prob_a decision + prob_b))``
+    (without ``prob_a`` / ``prob_b``: the plain logistic ``1 / (1 + exp(-decision))``).  **It must have been trained on
+    ``fingerprint``'s rows, not on RDKit's.**"""
+
+    def __init__(self, support: FingerprintSet, dual_coef, intercept: float, kind: str = "tanimoto", gamma=None,
+                 prob_a=None, prob_b=None):
+        what = "KernelModel"
+        if not isinstance(support, FingerprintSet):
+            raise TypeError(f"{what}: support must be a FingerprintSet, got {type(support).__name__}")
+        if kind not in _FP_KINDS:
+            raise ValueError(f"{what}: kind must be one of {sorted(_FP_KINDS)}, got {kind!r}")
+        if kind == "rbf" and gamma is None:
+            raise ValueError(f"{what}: the rbf kernel needs gamma")
+        if (prob_a is None) != (prob_b is None):
+            raise ValueError(f"{what}: give both prob_a and prob_b, or neither")
+        coef = torch.as_tensor(np.asarray(dual_coef, dtype=np.float64).reshape(-1), dtype=torch.float32)
+        if coef.numel() != len(support):
+            raise ValueError(f"{what}: {coef.numel()} coefficients for {len(support)} support rows")
+        self.support, self.kind, self.kind_code = support, kind, _FP_KINDS[kind]
+        self.dual_coef = coef.to(support.device)
+        self.intercept, self.gamma = float(intercept), 0.0 if gamma is None else float(gamma)
+        self.prob_a, self.prob_b = (-1.0, 0.0) if prob_a is None else (float(prob_a), float(prob_b))
+
+    @classmethod
+    def from_sklearn(cls, svc, support_bits=None, device="cuda"):
+        """From a fitted two-class ``sklearn.svm.SVC``, read by attribute (scikit-learn is never imported here).
+        ``kernel="rbf"`` / ``"linear"``: the support rows are ``svc.support_vectors_`` (0 / 1).  ``kernel="precomputed"``
+        is taken as a Tanimoto Gram matrix; ``support_bits`` must then hold the TRAINING fingerprints (rows
+        ``svc.support_`` of it are the support).  With ``probability=True`` the Platt parameters are taken as
+        ``prob_a = probA_``, ``prob_b = -probB_`` — the convention that reproduces ``predict_proba[:, 1]``
+        (tests/golden/make_golden_fingerprint.py asserts it) up to libsvm's own iteration tolerance: for two classes
+        libsvm does not return the Platt sigmoid itself but passes it through an iteration that stops at 0.0025, so
+        ``predict_proba`` differs from the sigmoid of ``decision_function`` by up to a few 1e-3."""
+        what = "KernelModel.from_sklearn"
+        coef = np.asarray(svc.dual_coef_, dtype=np.float64)
+        if coef.ndim != 2 or coef.shape[0] != 1:
+            raise ValueError(f"{what}: a two-class model is needed (dual_coef_ has shape {coef.shape})")
+        kernel = svc.kernel
+        if kernel == "precomputed":
+            if support_bits is None:
+                raise ValueError(f"{what}: a precomputed (Tanimoto) kernel needs support_bits, the training fingerprints")
+            rows = support_bits.bits if isinstance(support_bits, (Fingerprints, FingerprintSet)) else support_bits
+            rows = _pack_bits(what, rows)
+            rows = rows[torch.as_tensor(np.asarray(svc.support_, dtype=np.int64)).to(rows.device)]
+            kind, gamma = "tanimoto", None
+        elif kernel in ("rbf", "linear"):
+            rows, kind = np.asarray(svc.support_vectors_), kernel
+            gamma = float(svc._gamma) if kernel == "rbf" else None
+            if rows.dtype == np.int32:                       # a dense 0 / 1 matrix, whatever its dtype
+                rows = rows.astype(np.int8)
+        else:
+            raise ValueError(f"{what}: kernel {kernel!r} is not one of rbf, linear, precomputed")
+        pa, pb = np.asarray(svc.probA_).reshape(-1), np.asarray(svc.probB_).reshape(-1)
+        has = pa.size == 1 and pb.size == 1
+        return cls(FingerprintSet(rows, device=device), coef[0], float(np.asarray(svc.intercept_).reshape(-1)[0]), kind,
+                   gamma=gamma, prob_a=float(pa[0]) if has else None, prob_b=-float(pb[0]) if has else None)
+
+
+def activity(fp, model: KernelModel) -> SetComparison:
+    """The reference's ``ScoringFunction.compute_activity`` (ScoringFunction.py:162-192: a fingerprint and a
+    ``predict_proba`` per molecule on the host) for the whole batch in one launch (``gi_fp_compare``), no read-back:
+    ``proba`` [G] fp32 stands in for its result — **for a model trained on ``fingerprint``'s rows; these are not RDKit's
+    ECFP bits**.  ``proba`` is 0 for an all-zero fingerprint (an empty or malformed molecule: the reference's
+    ``except: pass``).  ``decision`` [G] is the fp32 kernel sum, made in a fixed order (equal inputs, equal bits);
+    ``nearest`` / ``max_sim`` / ``common`` / ``union`` refer to the model's support rows."""
+    if not isinstance(model, KernelModel):
+        raise TypeError(f"activity: model must be a KernelModel, got {type(model).__name__}")
+    return _compare("activity", fp, model.support, model.dual_coef, model.kind_code, model.gamma, model.intercept,
+                    model.prob_a, model.prob_b)
+
+
+def internal_diversity(fp) -> torch.Tensor:
+    """One minus the mean Tanimoto similarity over the ordered pairs i != j of the non-empty fingerprints of a batch: a
+    0-d fp32 device tensor, nothing read back (0 with fewer than two non-empty rows).  One ``gi_fp_compare`` launch of
+    the batch against itself with unit weights."""
+    what = "internal_diversity"
+    own = fp
+    if not isinstance(fp, FingerprintSet):
+        rows = fp.bits if isinstance(fp, Fingerprints) else fp
+        if not isinstance(rows, torch.Tensor):
+            raise TypeError(f"{what}: fp must be a Fingerprints, a FingerprintSet or a packed int32 tensor")
+        own = FingerprintSet(rows, device=rows.device)
+    ones = torch.ones(len(own), dtype=torch.float32, device=own.bits.device)
+    res = _compare(what, own, own, ones, L.FP_TANIMOTO, 0.0, 0.0, 0.0, 0.0)
+    live = (res.nearest >= 0).to(torch.float32)
+    m = live.sum()
+    total = (res.decision * live).sum() - m                  # every non-empty row meets itself once, at 1
+    return torch.where(m > 1, 1.0 - total / (m * (m - 1.0)).clamp_min(1.0), torch.zeros_like(m))
+
+
+def target_size_score(n_nodes: torch.Tensor, target: int, max_n_nodes: int) -> torch.Tensor:
+    """The reference's ``"target_size<k>"`` score component (ScoringFunction.py:111-129) from the ``n_nodes`` tensor:
+    ``1 - |n - target| / (max_n_nodes - target)``, fp32, plain torch on ``n_nodes``' device, no read-back.  The
+    reference's assertions become ``ValueError``; its division by zero at ``target == max_n_nodes`` is kept."""
+    target, max_n_nodes = int(target), int(max_n_nodes)
+    if not 0 < target <= max_n_nodes:
+        raise ValueError(f"target_size_score: target {target} must be in (0, max_n_nodes = {max_n_nodes}]")
+    n = n_nodes.to(torch.float32)
+    size = target * torch.ones_like(n)
+    return torch.ones_like(n) - torch.abs(n - size) / (max_n_nodes - size)
+
+
+def compute_score(contributions: Sequence[torch.Tensor], *, score_type: str, thresholds: Sequence[float],
+                  uniqueness: torch.Tensor, validity: torch.Tensor, termination: torch.Tensor) -> torch.Tensor:
+    """The reference's ``ScoringFunction.compute_score`` (ScoringFunction.py:58-91) over ready-made contributions
+    (``target_size_score``, ``activity(...).proba``, ...): plain torch on the tensors' device, no read-back, the
+    caller's tensors left untouched.  The reference's quirks are kept: a single component IGNORES ``score_type``;
+    ``"continuous"`` multiplies the components; ``"binary"`` multiplies the masks ``component > threshold`` (strict);
+    the uniqueness, validity and termination masks multiply last."""
+    contributions = list(contributions)
+    if not contributions:
+        raise ValueError("compute_score: at least one contribution is needed")
+    if len(thresholds) != len(contributions):
+        raise ValueError("compute_score: `contributions` and `thresholds` do not match")
+    if len(contributions) == 1:
+        final = contributions[0].clone()
+    elif score_type == "continuous":
+        final = contributions[0].clone()
+        for component in contributions[1:]:
+            final *= component
+    elif score_type == "binary":
+        masks = [(c > thresholds[k]).to(torch.uint8) for k, c in enumerate(contributions)]
+        final = masks[0]
+        for mask in masks[1:]:
+            final *= mask
+            final = final.float()
+    else:
+        raise NotImplementedError(f"compute_score: score_type {score_type!r}")
+    final = final * uniqueness
+    final = final * validity
+    return final * termination

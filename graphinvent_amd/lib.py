@@ -158,6 +158,8 @@ MOL_COUNTS, SEEN_FULL = 3, 1                            # GI_MOL_COUNTS, GI_SEEN
 (VAL_EMPTY, VAL_SELF_LOOP, VAL_OVER, VAL_FRAGMENTS, VAL_AROMATIC,
  VAL_H_MISMATCH) = 128, 256, 512, 1024, 2048, 4096      # GI_VAL_* of gi_mol_valence
 VAL_DESC, VAL_COUNTS, VAL_SCRATCH = 6, 4, 4             # GI_VAL_DESC, GI_VAL_COUNTS, GI_VAL_SCRATCH
+FP_MIN_BITS, FP_MAX_BITS, FP_MAX_RADIUS = 64, 4096, 4   # GI_FP_* of gi_mol_fingerprint
+FP_TANIMOTO, FP_RBF, FP_LINEAR = 0, 1, 2                # GI_FP_* kinds of gi_fp_compare
 
 
 class RouteDims(C.Structure):
@@ -297,6 +299,9 @@ SIGNATURES = {
     "gi_mol_seen_add": (ci, [ci, vp, vp, vp, vp, cll, vp, vp, vp]),
     "gi_mol_valence": (ci, [ci, ci, ci, ci, vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp, ci, ci, vp, ci, ci,
                             vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "gi_mol_fingerprint": (ci, [ci, ci, ci, ci, vp, vp, ci, vp, ci, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp]),
+    "gi_fp_compare": (ci, [ci, ci, ci, ci, vp, vp, vp, ci, C.c_double, C.c_double, C.c_double, C.c_double,
+                           vp, vp, vp, vp, vp, vp, vp]),
 }
 FUSE_GATES_V4, FUSE_DH_SCATTER, FUSE_TIER2_DSELU, FUSE_SLOTS = 1, 2, 4, 8  # GI_FUSE_*
 GLUE_READOUT_FWD, GLUE_READOUT_BWD, GLUE_LOSS_MEAN, GLUE_GRU_AGG = 1, 2, 4, 8  # GI_GLUE_*

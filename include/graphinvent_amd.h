@@ -1250,6 +1250,61 @@ int gi_mol_valence(int G, int N, int Fn, int Fe, const void* nodes, const void* 
                    int require_connected, float* valid, int* status, int* first_bad, signed char* atom_valence,
                    signed char* atom_h, int* desc, int* counts, int* scratch, void* stream);
 
+/* Molecule scores (gi_fingerprint.hip): a packed circular fingerprint per molecule, and a batch of fingerprints against
+ * a stored set — what the reference's "activity" score (ScoringFunction.py:145-192: one RDKit Morgan fingerprint and
+ * one scikit-learn predict_proba per molecule, on the host) needs, plus nearest-neighbour similarity.  THE FINGERPRINT
+ * IS A MORGAN-STYLE FINGERPRINT OF THE LABELLED GRAPH, NOT RDKit's ECFP BITS: other atom invariants (no ring
+ * membership, no isotope, hydrogens only through the bond-order sum), another hash, no removal of duplicate
+ * substructures, no aromaticity perception; a model must be trained on THESE fingerprints.  Guaranteed: isomorphic
+ * labelled molecules get equal rows in any node order, and id_r is equal for two atoms exactly when their radius-r
+ * labelled neighbourhoods are 1-WL-equivalent (up to 64-bit hash collisions).  tests/fingerprint_model.py is the numpy
+ * specification (and holds the constants K0, K1).
+ *
+ * gi_mol_fingerprint, one launch, one workgroup per molecule.  nodes / edges / n_nodes / dtype and the node row's
+ * segments n_types | n_charges | n_imp_h as for gi_mol_valence; order2 [Fe] (int8, device) twice the bond order.  A
+ * molecule is read and checked exactly as gi_mol_valence does it: with any of GI_MOL_VALUE, _NODE_PAST_N, _BOND_PAST_N,
+ * _ASYMMETRIC, _ONEHOT, _MULTI_BOND, GI_VAL_EMPTY (n == 0) or GI_VAL_SELF_LOOP its row is all zero, popcount 0, atom_id
+ * -1, status [G] holds the bits, and nothing else is evaluated.  Otherwise status is 0 and, in 64-bit wrap-around
+ * arithmetic with mix64 the splitmix64 finaliser, for the atoms i < n:
+ *   id_0[i] = mix64(K0 + a_i + 256 c_i + 2^16 deg_i + 2^24 o2_i)    a_i / c_i: the index inside the atom-type / charge
+ *             segment, deg_i: the bonded partners, o2_i = sum over t of order2[t] * #{j : edges[i, j, t]}; the
+ *             implicit-H and chirality segments do not enter;
+ *   id_r[i] = mix64(mix64(id_{r-1}[i] + r) + sum over the bonds (t, j) of i of mix64(id_{r-1}[j] ^ (K1 order2[t]))),
+ *             r = 1 .. radius, 0 <= radius <= GI_FP_MAX_RADIUS (the sum is commutative: no order enters);
+ *   bits [G, n_bits / 32] int32 (16-byte aligned): bit (id_r[i] & (n_bits - 1)) for every r <= radius and i < n; bit b
+ *             is bit b & 31 of word b >> 5; n_bits a power of two in [GI_FP_MIN_BITS, GI_FP_MAX_BITS];
+ *   popcount [G] int32 the set bits of the row; atom_id [G, N, 2] int32 (may be NULL): the low and the high half of
+ *             id_radius[i], -1 for i >= n.
+ * Integer arithmetic only: every output is deterministic.  No global atomics, no scratch; every loop is bounded by N,
+ * Fe and radius.  radius or n_bits outside their limits: GI_EINVAL.  G = 0 returns 0 and touches nothing.
+ *
+ * gi_fp_compare, one launch: G query rows against S >= 1 set rows of W = n_bits / 32 words (query [G, W_query], set
+ * [S, W_set], int32, both 16-byte aligned; W_query != W_set, a W that no n_bits gives, or S < 1: GI_EINVAL).  Per pair
+ * c = popcount(q & s), a = popcount(q), b = popcount(s), u = a + b - c.  Always: the set row of the largest Tanimoto
+ * c / u (0 / 0 := 0), decided in integers by cross-multiplication, ties to the lowest set index: nearest [G] (-1 where
+ * a == 0), common [G] = its c, uni [G] = its u (both 0 where a == 0), max_sim [G] fp32 = (float)c / (float)u, one
+ * correctly rounded division (0 where a == 0).  With weight [S] fp32 (else decision / proba may be NULL and are not
+ * written): decision [G] fp32 = intercept + sum over s of weight[s] K(q, s), K = c / u (GI_FP_TANIMOTO; 0 where
+ * u == 0), exp(-gamma (a + b - 2 c)) (GI_FP_RBF: the squared distance of 0 / 1 vectors) or c (GI_FP_LINEAR); proba
+ * [G] fp32 = 1 / (1 + exp(prob_a decision + prob_b)), and 0 where a == 0 (an empty or malformed molecule scores
+ * nothing: the reference's `except: pass`).  The fp32 sum is made in a FIXED order — each of 256 lanes adds its rows
+ * s = l, l + 256, .. in ascending order, the 64 lanes of a wave meet in a 6-level xor butterfly, the four waves are
+ * added in order, the intercept last; the longest chain of additions is ceil(S / 256) + 9 — so equal inputs give equal
+ * bits on every run.  No atomics.  G = 0 returns 0 and touches nothing. */
+#define GI_FP_MIN_BITS 64
+#define GI_FP_MAX_BITS 4096
+#define GI_FP_MAX_RADIUS 4
+#define GI_FP_TANIMOTO 0
+#define GI_FP_RBF 1
+#define GI_FP_LINEAR 2
+int gi_mol_fingerprint(int G, int N, int Fn, int Fe, const void* nodes, const void* edges, int dtype,
+                       const void* n_nodes, int n_nodes_bytes, int n_types, int n_charges, int n_imp_h,
+                       const signed char* order2, int radius, int n_bits, int* bits, int* popcount, int* status,
+                       int* atom_id, void* stream);
+int gi_fp_compare(int G, int S, int W_query, int W_set, const int* query, const int* set, const float* weight,
+                  int kind, double gamma, double intercept, double prob_a, double prob_b, int* nearest, int* common,
+                  int* uni, float* max_sim, float* decision, float* proba, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
