@@ -62,18 +62,23 @@ int gi_gru_fused_agg_fwd(const float* vals, int ldv, const int* perm, float* agg
                          int ldg, float* hx_new, const int* seg_off, int rows, const int* rows_dev, int H, int M,
                          void* stream);
 
-// gi_gemm_batch hands launches whose problems all carry GI_GEMM_BF3 to gi_gemm_bf3.hip
+// The GEMM family's launchers.  Every one of them builds its launch with gi_plan_build (gi_gemm_plan.h) from its own
+// GiGemmCaps row: the row says what the launcher accepts, gi_plan_check enforces it, and the launcher itself only
+// picks the instantiation and the grid.  gi_gemm_batch hands launches whose problems all carry GI_GEMM_BF3 to
+// gi_gemm_bf3_launch, which routes them (gi_plan_routable on the rows of the 32-deep-tile kernels):
+//   every problem GI_GEMM_T128 and b3v can run them -> gi_b3v_launch; else b3p if eligible; else b3v if eligible;
+//   else the 16-deep kernel of gi_gemm_bf3.hip, whose fp16x2 forward / dgrad epilogues (epi 1 / 2) go on to
+//   gi_x2n_launch unless GI_X2N=0.
 int gi_gemm_bf3_launch(const gi_gemm_params* probs, int n, void* stream);
-// ... and fp16x2 launches of plain fp32 operands with the forward / dgrad epilogue (epi 1 / 2) to gi_gemm_x2n.hip
 int gi_x2n_launch(const gi_gemm_params* probs, int n, int epi, void* stream);
-// ... and gi_gemm_bf3_launch those with plain fp32 operands (no images, no gathers) to gi_gemm_b3v.hip: forward,
-// dgrad (W as stored, b_major) and weight-gradient (a_major + b_major, split-K slabs) layouts on 32-deep k tiles
+// gi_gemm_b3v.hip: plain fp32 operands (no images, no gathers on A) in the forward, dgrad (W as stored, b_major) and
+// weight-gradient (a_major + b_major, split-K slabs) layouts on 32-deep k tiles
 bool gi_b3v_eligible(const gi_gemm_params* probs, int n);
 bool gi_b3v_wants(const gi_gemm_params* probs, int n);      // every problem carries GI_GEMM_T128 and the kernel can run them
 int gi_b3v_launch(const gi_gemm_params* probs, int n, void* stream);
 extern "C" int gi_b3v_enable(int on);
-// ... and forward / dgrad launches (both operands fp32 with k contiguous) to the 512-thread ping-pong kernel of
-// gi_gemm_b3p.hip (128 x 256 tiles, two wave groups alternating between the MFMA pipe and the staging work)
+// gi_gemm_b3p.hip: the same operand forms on the software-pipelined 512-thread kernel (128 x 256 tiles); forward /
+// dgrad launches only from 640 tiles on (or GI_B3P_ALL)
 bool gi_b3p_eligible(const gi_gemm_params* probs, int n);
 int gi_b3p_launch(const gi_gemm_params* probs, int n, void* stream);
 extern "C" int gi_b3p_enable(int on);

@@ -34,13 +34,12 @@
 #include <stdio.h>
 
 #include "gi_common.h"
-
+#define GI_SINK_EXTERNAL            // (the epilogue's sink stores must stay unconditional: see gi_gemm_plan.h)
+#include "gi_gemm_plan.h"
 #include "gi_mfma.h"
 #include "gi_x2.h"
 #include <type_traits>
 
-
-__device__ float gi_store_sink[256];               // where out-of-range lanes of edge tiles store
 
 // Operand addressing: block-uniform base pointer + 32-bit BYTE offset per lane (`global_load ... v_off,
 // s[base]`): one address VGPR and 32-bit integer arithmetic per access instead of a 64-bit pointer per
@@ -66,17 +65,10 @@ __device__ unsigned long long* gi_trace_buf;       // [tiles][8]
 #define GI_TRACE_HW(id) do {} while (0)
 #endif
 
-// Several independent GEMMs of the same tile/layout class in ONE launch ("horizontal fusion"):
+// Several independent GEMMs of the same tile/layout class in ONE launch ("horizontal fusion", GiGemmBatch):
 // the sibling MLPs of the readout (4 node-level stacks, 3 graph-level stacks) and the two GRU
 // projections have 16..450 workgroups each — together they fill the 256 CUs and halve the number of
-// launch ramps on the critical path.  Tile id -> (problem, x, y, z) through a prefix table.
-#define GI_GEMM_BATCH_MAX 8
-struct GemmBatch {
-    gi_gemm_params p[GI_GEMM_BATCH_MAX];
-    int start[GI_GEMM_BATCH_MAX + 1];          // first tile id of every problem
-    int gx[GI_GEMM_BATCH_MAX], gy[GI_GEMM_BATCH_MAX];
-    int n, total;
-};
+// launch ramps on the critical path.
 
 // Block-uniform description of one output tile (SGPRs) + the per-thread stored rows of a contig A
 // (the only per-thread state a tile carries: everything else is recomputed from the scalars).
@@ -100,7 +92,7 @@ struct GemmEpi {
 // compile time (forward: bias + SELU; dgrad: * selu'(act); weight-gradient slabs: plain store) — the
 // launcher picks it when every problem of the launch has exactly those flags.
 template <int TM, int TN, bool A_MAJOR, bool B_MAJOR, int EPI, bool PERSIST>
-__global__ __launch_bounds__(256) void gi_gemm_tiles_kernel(const GemmBatch b) {
+__global__ __launch_bounds__(256) void gi_gemm_tiles_kernel(const GiGemmBatch b) {
     constexpr int BM = 64 * TM, BN = 64 * TN, BK = 32;
     constexpr int A_LD = A_MAJOR ? BM + 4 : BK + 4;
     constexpr int A_ROWS = A_MAJOR ? BK : BM;
@@ -137,19 +129,15 @@ __global__ __launch_bounds__(256) void gi_gemm_tiles_kernel(const GemmBatch b) {
         t.pi = i;
         const int gx = b.gx[i], gy = b.gy[i], gxy = gx * gy;
         int local = id - b.start[i];
-        // split-K launches (weight gradients), flag bit 11: the XCD-aware order over the problem's WHOLE tile list, so
+        // split-K launches (weight gradients), GI_TILES_SLAB_ORDER: the XCD-aware order over the problem's WHOLE tile list, so
         // that one XCD walks consecutive slabs — the tiles of a slab read the SAME rows of both operands and share
         // them in one L2 (round 5; the order inside a slab, below, spreads a slab over all eight L2s)
-        const bool slab_order = (p.flags & 2048) != 0;
-        if (slab_order) {
-            const int T = b.start[i + 1] - b.start[i];
-            const int q = T >> 3, r = T & 7, xcd = local & 7, j = local >> 3;
-            local = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-        }
+        const bool slab_order = (p.flags & GI_TILES_SLAB_ORDER) != 0;
+        if (slab_order) local = gi_xcd_remap(local, b.start[i + 1] - b.start[i]);
         const int bz = local / gxy;
         int rem = local - bz * gxy;
-        // XCD-aware tile order (flag bit 5, set by the host for launches of many workgroups, see
-        // remap_min_blocks): the dispatcher deals consecutive workgroup ids round-robin to the 8 XCDs
+        // XCD-aware tile order (GI_TILES_ROW_ORDER, set by the host for launches of many workgroups, see
+        // gi_order_tiles_rows): the dispatcher deals consecutive workgroup ids round-robin to the 8 XCDs
         // (private L2 each) and a persistent workgroup's stride is a multiple of 8; the remap makes one
         // XCD walk consecutive tiles so the column tiles sharing an A row panel hit the same L2
         // (bijective for any grid size).
@@ -158,10 +146,7 @@ __global__ __launch_bounds__(256) void gi_gemm_tiles_kernel(const GemmBatch b) {
         int gxy_real = gxy;
         if (p.m_dev) gxy_real = gx * ((min(p.M, *p.m_dev) + BM - 1) / BM);
         const bool surplus = rem >= gxy_real;
-        if ((p.flags & 32) && !surplus && !slab_order) {
-            const int q = gxy_real >> 3, r = gxy_real & 7, xcd = rem & 7, j = rem >> 3;
-            rem = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-        }
+        if ((p.flags & GI_TILES_ROW_ORDER) && !surplus && !slab_order) rem = gi_xcd_remap(rem, gxy_real);
         const int by = rem / gx, bx = rem - by * gx;
         const bool splitk = (p.flags & GI_GEMM_SPLITK) != 0;
         int g = bz, s = 0, nsp = p.nsplit;
@@ -468,7 +453,7 @@ __global__ __launch_bounds__(256) void gi_gemm_tiles_kernel(const GemmBatch b) {
                         const int row = row0 + 8 * c + r;
                         const bool ok = col_ok & (row < m_end);
                         float* dst = ok ? (float*)((char*)Cp + ((unsigned)row * (unsigned)p.ldc + (unsigned)col) * 4u)
-                                        : gi_store_sink + tid;
+                                        : gi_sink + tid;
                         *dst = v[r];
                         amax = fmaxf(amax, ok ? fabsf(v[r]) : 0.f);
                     }
@@ -563,17 +548,6 @@ __global__ __launch_bounds__(256) void gi_gemm_tiles_kernel(const GemmBatch b) {
 
 }
 
-// XCD-aware tile order for launches of at least this many workgroups (0 = never): more than ~1.3
-// full rounds of 256 CUs x 4 resident workgroups.  Measured on the training step (3 A/B pairs):
-// never 2.74 ms, always 2.76-2.77 ms, >= 1300..2100 workgroups 2.70-2.71 ms.  The small launches lose
-// with the remap (an XCD's share of a 1-round launch is not balanced), the big ones win (column tiles
-// sharing an A row panel hit one L2).
-static int remap_min_blocks() { return 1350; }
-static bool want_remap(long long blocks) {
-    const int m = remap_min_blocks();
-    return m > 0 && blocks >= m;
-}
-
 // Measurement aid (tools/gemm_launch_report.py): GI_GEMM_LOG=<file> appends one line per launch
 // — layout class, workgroups, useful flops, then M,N,K,groups per problem — to correlate with a
 // rocprofv3 kernel trace.
@@ -600,54 +574,16 @@ static void log_launch(const gi_gemm_params* probs, int n, int blocks, double fl
     gi_gemm_log_launch(cls, probs, n, blocks, flops);
 }
 
-static int validate(const gi_gemm_params& p) {
-    if (p.M < 0 || p.N <= 0 || p.K < 0 || p.nsplit < 1 || p.ngroups < 0 ||
-        p.ngroups > GI_MAX_GROUPS)
-        return GI_EINVAL;
-    if ((p.a_idx && p.a_major) || (p.b_idx && !p.b_major)) return GI_EINVAL;
-    if (p.ones_col >= 0 && (!p.b_major || p.ones_col != p.N - 1)) return GI_EINVAL;
-    const bool splitk = (p.flags & GI_GEMM_SPLITK) != 0;
-    if (p.ngroups && !p.grp_off) return GI_EINVAL;
-    if (!splitk && p.nsplit != 1) return GI_EINVAL;
-    if (p.a_major && !p.b_major) return GI_EINVAL;
-    if (!((p.tm == 1 && p.tn == 1) || (p.tm == 1 && p.tn == 2) || (p.tm == 2 && p.tn == 2)))
-        return GI_EINVAL;
-    // rows narrower than one 16-byte vector must be stored padded to 4 floats
-    if (!p.a_major && p.K < 4 && p.lda < 4) return GI_EINVAL;
-    if (!p.b_major && p.K < 4 && p.ldb < 4) return GI_EINVAL;
-    if (p.a_major && p.M < 4 && p.lda < 4) return GI_EINVAL;
-    if (p.b_major && p.N < 4 && p.ldb < 4) return GI_EINVAL;
-    if (splitk && p.ngroups)
-        for (int g = 0; g < p.ngroups; ++g)
-            if (p.gsplit[g] < 1) return GI_EINVAL;
-    if ((p.m_dev || p.k_dev) && (p.ngroups || (p.flags & GI_GEMM_SPLITK))) return GI_EINVAL;
-    // 32-bit byte offsets inside every matrix (gi_load4_at)
-    const long long lim = 0xffffffffLL / 4;
-    const bool splitk2 = (p.flags & GI_GEMM_SPLITK) != 0;
-    const long long a_rows = p.a_major ? p.K : p.M, b_rows = p.b_major ? p.K : p.N;
-    if (!p.a_idx && a_rows * (long long)p.lda > lim) return GI_ELIMIT;
-    if (!p.b_idx && b_rows * (long long)p.ldb > lim) return GI_ELIMIT;
-    if ((long long)p.M * p.ldc > lim || (p.act && (long long)p.M * p.ldact > lim)) return GI_ELIMIT;
-    (void)splitk2;
-    if (p.flags & ~(GI_EPI_BIAS | GI_EPI_SELU | GI_EPI_DSELU | GI_EPI_ACCUM | GI_GEMM_SPLITK | GI_EPI_MULACT))
-        return GI_EINVAL;                               // bit 5 (tile order) is the launcher's
-    return 0;
-}
-
-// grid of one problem; x*y*z == 0 means "nothing to launch"
-static dim3 problem_grid(const gi_gemm_params& p) {
-    const bool splitk = (p.flags & GI_GEMM_SPLITK) != 0;
-    const int BM = 64 * p.tm, BN = 64 * p.tn;
-    const int rows = splitk ? p.M : (p.ngroups ? p.max_group_rows : p.M);
-    if (rows <= 0) return dim3(0, 0, 0);
-    const int groups = p.ngroups ? p.ngroups : 1;
-    int zsplit = p.nsplit;
-    if (splitk && p.ngroups) {
-        zsplit = 0;
-        for (int g = 0; g < p.ngroups; ++g) zsplit += p.gsplit[g];
-    }
-    return dim3(gi_cdiv(p.N, BN), gi_cdiv(rows, BM), splitk ? zsplit : groups);
-}
+// fp32 operands in every layout; gathers on the stored rows of a contig A and of a major B; groups with or without
+// split-K; bounded launches (m_dev, k_dev) without either.  Every matrix is addressed with 32-bit byte offsets
+// (gi_load4_at); rows narrower than one 16-byte vector must be stored padded to 4 floats.  No routing bit is stripped:
+// each is an unknown flag here (GI_EINVAL), which is what keeps GI_TILES_* free for the launcher.
+static constexpr GiGemmCaps TILES_CAPS = {
+    /*BM, BN*/ 0, 0, /*layouts*/ GI_LAY_CC | GI_LAY_CM | GI_LAY_MM, /*strip*/ 0, /*epi_classes*/ 0, /*images*/ false,
+    /*x2_layouts*/ 0, /*x2_slabs_plain*/ false, /*a_idx*/ true, /*b_idx*/ GI_BIDX_MAJOR, /*k_dev*/ true, /*m_dev*/ true, /*ones_col*/ true,
+    /*splitk_layouts*/ GI_LAY_CC | GI_LAY_CM | GI_LAY_MM, /*groups*/ GI_GROUPS_ANY, /*need_ptrs*/ false, /*need_ld*/ false,
+    /*even_major_ld*/ false, /*pad_major*/ true, /*limit_all*/ true, /*k_min*/ 0, /*order*/ GI_ORDER_TILES,
+    /*limits_last*/ true, /*flags_last*/ true, /*bidx_last*/ false};
 
 // k tiles one workgroup of the problem walks through (its run time, to first order)
 static int wg_k_tiles(const gi_gemm_params& p) {
@@ -657,7 +593,7 @@ static int wg_k_tiles(const gi_gemm_params& p) {
     return gi_cdiv(gi_cdiv(len, nsp > 0 ? nsp : 1), 32);
 }
 
-typedef void (*gi_tiles_fn)(const GemmBatch);
+typedef void (*gi_tiles_fn)(const GiGemmBatch);
 // variants: tile (3) x layout (3) x {run-time epilogue | the layout's own epilogue x {one tile per workgroup, tile stream}}
 static gi_tiles_fn tiles_kernel(int tm, int tn, bool am, bool bm, int epi, bool persist) {
 #define GI_PICK3(TMV, TNV, E, P)                                                                   \
@@ -676,11 +612,6 @@ static gi_tiles_fn tiles_kernel(int tm, int tn, bool am, bool bm, int epi, bool 
 #undef GI_PICK2
 #undef GI_PICK3
 }
-// the epilogue flags of a layout's own launch class (kernel template EPI = 1)
-static int own_epilogue(bool am, bool bm) {
-    return (!am && !bm) ? (GI_EPI_BIAS | GI_EPI_SELU) : (!am ? GI_EPI_DSELU : 0);
-}
-
 // Persistent grid: the number of workgroups of this kernel variant the device holds at once
 // (occupancy x CUs, from the runtime, cached per variant).  A launch with at least
 // persist_tenths / 10 times that many tiles runs as that many workgroups walking the tile list
@@ -715,24 +646,16 @@ static int resident_blocks(gi_tiles_fn fn, int tm, int tn, bool am, bool bm, int
     return c;
 }
 
-static int launch_tiles(GemmBatch& b, double flops, hipStream_t st) {
+// epi: 1 = every problem has the layout's own epilogue
+static int launch_tiles(GiGemmBatch& b, int epi, double flops, hipStream_t st) {
     const gi_gemm_params& p0 = b.p[0];
     const bool am = p0.a_major, bm = p0.b_major;
-    int epi = 1;                                        // every problem has the layout's own epilogue?
-    for (int i = 0; i < b.n; ++i)
-        if ((b.p[i].flags & ~GI_GEMM_SPLITK) != own_epilogue(am, bm)) epi = 0;
-    if (want_remap(b.total))
-        for (int i = 0; i < b.n; ++i) b.p[i].flags |= 32;
-    if (b.total >= 64)                                  // split-K launches: slab-per-XCD tile order
-        for (int i = 0; i < b.n; ++i)
-            if ((b.p[i].flags & GI_GEMM_SPLITK) && !b.p[i].m_dev) b.p[i].flags |= 2048;
     int grid = b.total;
     // Bounded launches (rows counted on the device, m_dev): the grid would be sized for the BOUND and its surplus
     // workgroups, though they exit at once, are dispatched at the tail of the launch at the dispatcher's rate
     // (measured: 13 000-row bound on 7 259 real rows = 44 % empty tiles, +46 % launch time).  As a tile stream
     // over the device's resident workgroups the empty tiles cost a few scalar loads each.
-    bool bounded = false;
-    for (int i = 0; i < b.n; ++i) bounded |= b.p[i].m_dev != nullptr;
+    const bool bounded = gi_plan_bounded(b);
     const bool can_stream = epi || (!am && !bm);        // the tile-stream variants that are compiled
     const int pt = (bounded && can_stream) ? 10 : (epi ? persist_tenths() : 0);
     if (pt > 0) {
@@ -752,10 +675,6 @@ extern "C" int gi_gemm_batch(const gi_gemm_params* probs, int n, void* stream) {
     int nbf3 = 0;
     for (int i = 0; i < n; ++i) nbf3 += (probs[i].flags & GI_GEMM_BF3) != 0;
     if (nbf3) return nbf3 == n ? gi_gemm_bf3_launch(probs, n, stream) : GI_EINVAL;
-    GemmBatch b;
-    memset(&b, 0, sizeof(b));
-    double flops = 0;
-    int total = 0, k = 0;
     // longest reductions first: tile ids are handed out in order, so the short tiles are the ones
     // that fill the last, partly empty round of the launch
     int order[GI_GEMM_BATCH_MAX];
@@ -764,25 +683,12 @@ extern "C" int gi_gemm_batch(const gi_gemm_params* probs, int n, void* stream) {
         for (int j = i; j > 0 && wg_k_tiles(probs[order[j]]) > wg_k_tiles(probs[order[j - 1]]); --j) {
             const int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t;
         }
-    for (int ii = 0; ii < n; ++ii) {
-        const gi_gemm_params& p = probs[order[ii]];
-        const int rc = validate(p);
-        if (rc) return rc;
-        if (p.tm != probs[0].tm || p.tn != probs[0].tn || p.a_major != probs[0].a_major ||
-            p.b_major != probs[0].b_major)
-            return GI_EINVAL;
-        const dim3 g = problem_grid(p);
-        if (g.x == 0) continue;
-        if ((long long)g.x * g.y * g.z + total > 0x3fffffff) return GI_ELIMIT;
-        b.p[k] = p; b.gx[k] = g.x; b.gy[k] = g.y; b.start[k] = total;
-        total += g.x * g.y * g.z;
-        flops += 2.0 * (double)p.M * (double)p.N * (double)p.K;
-        ++k;
-    }
-    if (k == 0) return 0;
-    b.start[k] = total;
-    b.n = k; b.total = total;
-    return launch_tiles(b, flops, (hipStream_t)stream);
+    GiGemmBatch b;
+    double flops;
+    int epi;
+    if (int rc = gi_plan_build(probs, n, TILES_CAPS, &b, &flops, &epi, order)) return rc;
+    if (b.n == 0) return 0;
+    return launch_tiles(b, epi, flops, (hipStream_t)stream);
 }
 
 extern "C" int gi_gemm(const gi_gemm_params* pp, void* stream) {

@@ -38,18 +38,15 @@
 #include <type_traits>
 
 #include "gi_common.h"
+#include "gi_gemm_plan.h"
 #include "gi_mfma.h"
 #include "gi_x2.h"
 
 typedef __bf16 gp_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 gp_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float gp_f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned gp_u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned gp_u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
-
-__device__ float gp_sink[512];                     // where out-of-range lanes of edge tiles store
 
 // tools/b3p_lab.hip (-DGI_B3P_TRACE): shader-clock stamp at every iteration start of one workgroup's waves 0 and 4
 #ifdef GI_B3P_TRACE
@@ -71,26 +68,6 @@ constexpr int GP_STAGE_X2 = 2 * (GP_PLA + GP_PLB);               // 48 KB (two f
 
 __device__ __forceinline__ unsigned gp_lds_a(int kc, int row) { return kc * GP_CHA + ((row * 16 + kc * 32) & (GP_CHA - 1)); }
 __device__ __forceinline__ unsigned gp_lds_b(int kc, int row) { return kc * GP_CHB + ((row * 16 + kc * 32) & (GP_CHB - 1)); }
-__device__ __forceinline__ unsigned gp_pk(float lo, float hi) {
-    gp_f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, gp_bf16x2));     // v_cvt_pk_bf16_f32 (RNE)
-}
-__device__ __forceinline__ float gp_lo(unsigned p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float gp_hi(unsigned p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
-// two fp32 values -> their three bf16 planes, packed pairwise (low half = x0)
-__device__ __forceinline__ void gp_split2(float x0, float x1, unsigned& p0, unsigned& p1, unsigned& p2) {
-    p0 = gp_pk(x0, x1);
-    const float r0 = x0 - gp_lo(p0), r1 = x1 - gp_hi(p0);
-    p1 = gp_pk(r0, r1);
-    p2 = gp_pk(r0 - gp_lo(p1), r1 - gp_hi(p1));
-}
-
-struct GpBatch {
-    gi_gemm_params p[8];
-    int start[9];
-    int gx[8], gy[8];
-    int n, total, remap;
-};
 
 #define GP_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
 // order inside a group of 4 MFMAs + its fillers: MFMA, 3 VALU, up to 3 LDS ops, ... then the loads, then a fence
@@ -109,7 +86,7 @@ struct GpBatch {
 // BIDX (weight-gradient layout only): the reduction rows of B are gathered through p.b_idx (the first layer of a message
 // stack reads h[u_src]) — the index of a reduction row is wave-uniform, i.e. scalar loads ahead of the row loads.
 template <bool AM, bool BMJ, int EPI, bool X2, bool BIDX = false>
-__device__ __forceinline__ void gp_tile(const GpBatch& b, const int tile_id, unsigned char* const smem) {
+__device__ __forceinline__ void gp_tile(const GiGemmBatch& b, const int tile_id, unsigned char* const smem) {
     constexpr int NP = X2 ? 2 : 3;
     constexpr int A_BYTES = NP * GP_PLA, STAGE = NP * (GP_PLA + GP_PLB);
     const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -121,37 +98,12 @@ __device__ __forceinline__ void gp_tile(const GpBatch& b, const int tile_id, uns
 
     GP_WG_STAMP(0);
     // ---- tile (block-uniform) ----------------------------------------------------------------------
-    int pi = 0;
-    while (pi < b.n - 1 && tile_id >= b.start[pi + 1]) ++pi;
-    const gi_gemm_params& p = b.p[pi];
-    int local = tile_id - b.start[pi];
-    if (b.remap) {                                  // XCD-aware tile order (gi_gemm.hip), bijective
-        const int tiles = b.start[pi + 1] - b.start[pi];
-        const int q = tiles >> 3, r = tiles & 7, xcd = local & 7, j = local >> 3;
-        local = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
-    const int gx = b.gx[pi], gxy = gx * b.gy[pi];
-    const int bz = local / gxy;
-    const int rem = local - bz * gxy;
-    const int by = rem / gx, bx = rem - by * gx;
-    const int m_end = p.m_dev ? min(p.M, *p.m_dev) : p.M;
-    const int m0 = by * GP_BM, n0 = bx * GP_BN;
+    const GiTile tile = gi_tile_decode<GP_BM, GP_BN, true>(b, tile_id);
+    const gi_gemm_params& p = b.p[tile.pi];
+    const int bx = tile.bx, m_end = tile.m_end, m0 = tile.m0, n0 = tile.n0;
     if (m0 >= m_end) return;                        // (bounded launch: beyond the rows on the device)
-    int kb = 0, ke = p.K;
-    float* Cp = p.C;
-    if (p.flags & GI_GEMM_SPLITK) {                 // reduction range of this slab
-        int g = 0, s = bz, nsp = p.nsplit;
-        if (p.ngroups) {
-            while (g < p.ngroups - 1 && s >= p.gsplit[g]) { s -= p.gsplit[g]; ++g; }
-            nsp = p.gsplit[g];
-            Cp = p.Cg[g];
-            kb = p.grp_off[g]; ke = p.grp_off[g + 1];
-        }
-        const int chunk = (((ke - kb + nsp - 1) / nsp) + 31) & ~31;
-        kb += s * chunk;
-        ke = min(kb + chunk, ke);
-        Cp += (long long)s * p.c_split_stride;
-    }
+    const int kb = tile.kb, ke = tile.ke;
+    float* const Cp = tile.Cp;
     const int nk = ke > kb ? (ke - kb + GP_BK - 1) / GP_BK : 0;
     const int n_full = ke > kb ? (ke - kb) / GP_BK : 0;
     float sa = 1.f, ia = 1.f, sb = 1.f, ib = 1.f;               // fp16x2: per-tensor power-of-two scales
@@ -269,7 +221,7 @@ __device__ __forceinline__ void gp_tile(const GpBatch& b, const int tile_id, uns
             if (X2 && !AM && isA && h == 0)
                 rowmax[u & 1] = fmaxf(fmaxf(rowmax[u & 1], fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
             if (X2) gx_split2(h ? v.z : v.x, h ? v.w : v.y, isA ? sa : sb, q0[h], q1[h]);
-            else gp_split2(h ? v.z : v.x, h ? v.w : v.y, q0[h], q1[h], q2[h]);
+            else gi_bf3_split2(h ? v.z : v.x, h ? v.w : v.y, q0[h], q1[h], q2[h]);
             if (h == 1) {
                 const unsigned w = isA ? a_w[u] : b_w[u - 2];
                 const int pb = isA ? GP_PLA : GP_PLB;
@@ -294,7 +246,7 @@ __device__ __forceinline__ void gp_tile(const GpBatch& b, const int tile_id, uns
                 }
             }
             if (X2) gx_split2(x[2 * h], x[2 * h + 1], isA ? sa : sb, q0[h], q1[h]);
-            else gp_split2(x[2 * h], x[2 * h + 1], q0[h], q1[h], q2[h]);
+            else gi_bf3_split2(x[2 * h], x[2 * h + 1], q0[h], q1[h], q2[h]);
             if (h == 3) {
                 const unsigned w = isA ? a_w[0] : b_w[col - 1];
                 const int pb = isA ? GP_PLA : GP_PLB;
@@ -429,7 +381,7 @@ __device__ __forceinline__ void gp_tile(const GpBatch& b, const int tile_id, uns
     const int ldc = p.ldc, ldact = p.ldact, Ncols = p.N;
     const float* const actp = p.act;
     const float* const biasp = p.bias;
-    float* const sink = gp_sink + tid;
+    float* const sink = gi_sink + tid;
     float amax = 0.f;
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
@@ -480,7 +432,7 @@ __device__ __forceinline__ void gp_tile(const GpBatch& b, const int tile_id, uns
 // first: gi_gemm_batch's order) — so no CU waits for a 512-thread / 144 KB workgroup to be torn down and set up
 // between two tiles.
 template <bool AM, bool BMJ, int EPI, bool X2 = false, bool BIDX = false>
-__global__ __launch_bounds__(512, 2) void gi_b3p_kernel(const GpBatch b) {
+__global__ __launch_bounds__(512, 2) void gi_b3p_kernel(const GiGemmBatch b) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];        // 2 stages
     for (int tile = blockIdx.x; tile < b.total; tile += gridDim.x) gp_tile<AM, BMJ, EPI, X2, BIDX>(b, tile, smem);
 }
@@ -488,19 +440,21 @@ __global__ __launch_bounds__(512, 2) void gi_b3p_kernel(const GpBatch b) {
 int g_b3p_enabled = -1, g_b3p_stream_cus = -1;
 bool g_b3p_attr_set[2][4][4] = {};
 
+// fp32 operands only (no pre-split images), no row gathers on A; a gathered B: the weight-gradient layout only, fp16x2
+// only, every problem of the launch alike (one kernel).  Major operands are read column by column: any leading dimension
+constexpr GiGemmCaps GP_CAPS = {
+    /*BM, BN*/ GP_BM, GP_BN, /*layouts*/ GI_LAY_CC | GI_LAY_CM | GI_LAY_MM,
+    /*strip*/ GI_GEMM_BF3 | GI_GEMM_BF3B_F32 | GI_GEMM_X2 | GI_GEMM_T128, /*epi_classes*/ 0xf, /*images*/ false,
+    /*x2_layouts*/ GI_LAY_CC | GI_LAY_CM | GI_LAY_MM, /*x2_slabs_plain*/ false, /*a_idx*/ false, /*b_idx*/ GI_BIDX_X2_SLABS,
+    /*k_dev*/ false, /*m_dev*/ true, /*ones_col*/ true, /*splitk_layouts*/ GI_LAY_MM, /*groups*/ GI_GROUPS_SLABS, /*need_ptrs*/ true,
+    /*need_ld*/ true, /*even_major_ld*/ false, /*pad_major*/ false, /*limit_all*/ false, /*k_min*/ 0,
+    /*order*/ GI_ORDER_ROWS_SLABS, /*limits_last*/ false, /*flags_last*/ false, /*bidx_last*/ true};
+
 }  // namespace
 
 // Process-wide switch (measurement aid): route eligible GI_GEMM_BF3 launches to the software-pipelined kernel of
 // this file (1; environment GI_B3P) or not (0).  on < 0 only queries; returns the previous value.
-extern "C" int gi_b3p_enable(int on) {
-    if (g_b3p_enabled < 0) {
-        const char* e = getenv("GI_B3P");
-        g_b3p_enabled = e ? (atoi(e) != 0) : 1;
-    }
-    const int prev = g_b3p_enabled;
-    if (on >= 0) g_b3p_enabled = on ? 1 : 0;
-    return prev;
-}
+extern "C" int gi_b3p_enable(int on) { return gi_env_switch(g_b3p_enabled, "GI_B3P", 1, on); }
 
 // fp32 operands only (no pre-split images), no row gathers; layouts: contig/contig, contig/major, major/major
 bool gi_b3p_eligible(const gi_gemm_params* probs, int n) {
@@ -511,89 +465,24 @@ bool gi_b3p_eligible(const gi_gemm_params* probs, int n) {
     // quantises badly below ~2.5 tiles per CU (measured at the headline batch, 348 tiles: 75 us against 70 us for the
     // three-workgroups-per-CU kernel of round 3; at 26 000 rows, 1 224 tiles: 225 against 244 us)
     if (!probs[0].a_major && tiles < 640 && !getenv("GI_B3P_ALL")) return false;
-    for (int i = 0; i < n; ++i) {
-        const gi_gemm_params& p = probs[i];
-        if (!(p.flags & GI_GEMM_BF3) || (p.flags & GI_GEMM_BF3A)) return false;
-        if (p.a_major != probs[0].a_major || p.b_major != probs[0].b_major) return false;
-        if (p.a_major && !p.b_major) return false;
-        if (!p.b_major && !(p.flags & GI_GEMM_BF3B_F32)) return false;      // contig B must be plain fp32, not an image
-        if (p.a_idx || p.k_dev) return false;
-        // a gathered B: the weight-gradient layout only, fp16x2 only, every problem of the launch alike (one kernel)
-        if (p.b_idx && !(p.a_major && p.b_major && (p.flags & GI_GEMM_X2) && (p.flags & GI_GEMM_SPLITK))) return false;
-        if ((p.b_idx != nullptr) != (probs[0].b_idx != nullptr)) return false;
-    }
-    return true;
+    return gi_plan_routable(probs, n, GP_CAPS);
 }
 
 int gi_b3p_launch(const gi_gemm_params* probs, int n, void* stream) {
-    GpBatch b;
-    memset(&b, 0, sizeof(b));
-    double flops = 0;
-    int total = 0, k = 0, epi = -1;
-    const bool am = probs[0].a_major != 0, bmj = probs[0].b_major != 0;
-    for (int i = 0; i < n; ++i) {
-        const gi_gemm_params& p = probs[i];
-        const bool splitk = (p.flags & GI_GEMM_SPLITK) != 0;
-        if (!p.A || !p.B || p.M < 0 || p.N <= 0 || p.K < 0 || p.nsplit < 1 || p.ngroups < 0 ||
-            p.ngroups > GI_MAX_GROUPS)
-            return GI_EINVAL;
-        if (!splitk && (p.nsplit != 1 || p.ngroups)) return GI_EINVAL;
-        if (p.ngroups && !p.grp_off) return GI_EINVAL;
-        if (!p.ngroups && !p.C) return GI_EINVAL;
-        if (splitk && (!am || !bmj || p.m_dev)) return GI_EINVAL;            // slabs: weight-gradient layout only
-        if (p.ones_col >= 0 && (!bmj || p.ones_col != p.N - 1)) return GI_EINVAL;
-        const int f = p.flags & ~(GI_GEMM_BF3 | GI_GEMM_BF3B_F32 | GI_GEMM_SPLITK | GI_GEMM_X2 | GI_GEMM_T128);
-        if (f & ~(GI_EPI_BIAS | GI_EPI_SELU | GI_EPI_DSELU | GI_EPI_ACCUM | GI_EPI_MULACT)) return GI_EINVAL;
-        if (((p.flags & GI_GEMM_X2) != 0) != ((probs[0].flags & GI_GEMM_X2) != 0)) return GI_EINVAL;
-        if ((p.flags & GI_GEMM_X2) && (!p.a_amax || !p.b_amax)) return GI_EINVAL;
-        if ((f & GI_EPI_BIAS) && !p.bias) return GI_EINVAL;
-        if ((f & (GI_EPI_DSELU | GI_EPI_MULACT)) && !p.act) return GI_EINVAL;
-        const long long lim = 0xffffffffLL / 4;
-        const int bcols = p.ones_col >= 0 ? p.ones_col : p.N;
-        if (!am) {
-            if (p.lda < p.K || (p.K < 4 && p.lda < 4)) return GI_EINVAL;
-            if ((long long)p.M * p.lda > lim) return GI_ELIMIT;
-        } else if (p.lda < p.M || p.M < 1) return GI_EINVAL;
-        if (!bmj) {
-            if (p.ldb < p.K || (p.K < 4 && p.ldb < 4)) return GI_EINVAL;
-            if ((long long)p.N * p.ldb > lim) return GI_ELIMIT;
-        } else if (p.ldb < bcols || bcols < 1) return GI_EINVAL;
-        const int e = splitk ? (f == 0 ? 3 : 0)
-                             : (f == (GI_EPI_BIAS | GI_EPI_SELU) ? 1 : (f == GI_EPI_DSELU ? 2 : (f == 0 ? 3 : 0)));
-        epi = (epi < 0 || epi == e) ? e : 0;
-        if (p.M == 0) continue;
-        int zs = 1;
-        if (splitk) {
-            zs = p.nsplit;
-            if (p.ngroups) { zs = 0; for (int g = 0; g < p.ngroups; ++g) { if (p.gsplit[g] < 1) return GI_EINVAL; zs += p.gsplit[g]; } }
-        }
-        b.p[k] = p; b.p[k].flags = f | (splitk ? GI_GEMM_SPLITK : 0);
-        b.gx[k] = gi_cdiv(p.N, GP_BN); b.gy[k] = gi_cdiv(p.M, GP_BM);
-        b.start[k] = total;
-        if ((long long)b.gx[k] * b.gy[k] * zs + total > 0x3fffffff) return GI_ELIMIT;
-        total += b.gx[k] * b.gy[k] * zs;
-        flops += 2.0 * (double)p.M * (double)p.N * (double)p.K;
-        ++k;
-    }
-    if (k == 0) return 0;
-    b.start[k] = total; b.n = k; b.total = total;
-    bool bounded = false;
-    for (int i = 0; i < k; ++i) bounded |= b.p[i].m_dev != nullptr;
-    b.remap = (total >= 512 && !bounded && !am) ? 1 : 0;
-    // Weight-gradient launches (split-K slabs): consecutive tile ids are the column / row tiles of ONE slab, i.e. the
-    // workgroups that read the SAME rows of both operands — dealt round-robin to the 8 XCDs each of them pulls its
-    // 128 + 256 columns of those rows through a different L2 (2.5-3.1 x the operand bytes per launch through the
-    // fabric, profiles/r04).  With the bijective remap one XCD walks consecutive ids: a slab's tiles share an L2.
-    if (am && !bounded && total >= 16) b.remap = 1;
+    GiGemmBatch b;
+    double flops;
+    int epi;
+    if (int rc = gi_plan_build(probs, n, GP_CAPS, &b, &flops, &epi)) return rc;
+    if (b.n == 0) return 0;
+    const int total = b.total, k = b.n;
+    const bool am = probs[0].a_major != 0, bmj = probs[0].b_major != 0, bounded = gi_plan_bounded(b);
     hipStream_t st = (hipStream_t)stream;
-    typedef void (*kern_t)(const GpBatch);
+    typedef void (*kern_t)(const GiGemmBatch);
     kern_t fn;
     int li;
     const bool x2 = (probs[0].flags & GI_GEMM_X2) != 0;
 #define GP_PICK(A, B, E) (x2 ? (kern_t)gi_b3p_kernel<A, B, E, true> : (kern_t)gi_b3p_kernel<A, B, E, false>)
     const bool bidx = probs[0].b_idx != nullptr;
-    for (int i = 0; i < n; ++i)
-        if ((probs[i].b_idx != nullptr) != bidx || (bidx && !(am && x2 && (probs[i].flags & GI_GEMM_SPLITK)))) return GI_EINVAL;
     if (am && bidx) { if (epi != 3) return GI_EINVAL; li = 3; fn = (kern_t)gi_b3p_kernel<true, true, 3, true, true>; }
     else if (am) { li = 2; if (epi != 3) epi = 0; fn = epi == 3 ? GP_PICK(true, true, 3) : GP_PICK(true, true, 0); }
     else if (bmj) { li = 1; if (epi != 2) epi = 0; fn = epi == 2 ? GP_PICK(false, true, 2) : GP_PICK(false, true, 0); }

@@ -28,19 +28,17 @@
 #include <type_traits>
 
 #include "gi_common.h"
+#include "gi_gemm_plan.h"
 #include "gi_mfma.h"
 #include "gi_x2.h"
 
 typedef __bf16 gv_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 gv_bf16x2 __attribute__((ext_vector_type(2)));
 typedef float gv_f32x2 __attribute__((ext_vector_type(2)));
 typedef gv_f32x2 gv_f32x2_u __attribute__((aligned(4)));
 typedef unsigned gv_u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned gv_u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
-
-__device__ float gv_sink[256];                     // where out-of-range lanes of edge tiles store
 
 constexpr int GV_BM = 128, GV_BN = 128, GV_BK = 32;
 constexpr int GV_CH = 128 * 16;                    // bytes of one k chunk (8 bf16) of all 128 rows
@@ -49,25 +47,6 @@ constexpr int GV_PLANE = 4 * GV_CH;                // 8 KB
 __device__ __forceinline__ unsigned gv_lds(int plane, int kc, int row) {
     return plane * GV_PLANE + kc * GV_CH + ((row * 16 + kc * 32) & (GV_CH - 1));
 }
-__device__ __forceinline__ unsigned gv_pk(float lo, float hi) {
-    gv_f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, gv_bf16x2));     // v_cvt_pk_bf16_f32 (RNE)
-}
-__device__ __forceinline__ float gv_lo(unsigned p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float gv_hi(unsigned p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
-__device__ __forceinline__ void gv_split2(float x0, float x1, unsigned& p0, unsigned& p1, unsigned& p2) {
-    p0 = gv_pk(x0, x1);
-    const float r0 = x0 - gv_lo(p0), r1 = x1 - gv_hi(p0);
-    p1 = gv_pk(r0, r1);
-    p2 = gv_pk(r0 - gv_lo(p1), r1 - gv_hi(p1));
-}
-
-struct GvBatch {
-    gi_gemm_params p[8];
-    int start[9];
-    int gx[8], gy[8];
-    int n, total, remap;
-};
 
 // EPI: 0 = epilogue from the run-time flags, 1 = bias + SELU (forward), 2 = * selu'(act) (dgrad), 3 = plain store
 // (weight-gradient slabs).
@@ -75,7 +54,7 @@ struct GvBatch {
 // instead of 48, 24 instead of 48 MFMAs per wave and k tile; scales from a_amax / b_amax.  BIDX (weight-gradient layout): B's reduction rows gathered
 // through p.b_idx (wave-uniform indices).
 template <bool AM, bool BMJ, int EPI, bool X2 = false, bool BIDX = false>
-__global__ __launch_bounds__(256, X2 ? 4 : 3) void gi_b3v_kernel(const GvBatch b) {
+__global__ __launch_bounds__(256, X2 ? 4 : 3) void gi_b3v_kernel(const GiGemmBatch b) {
     static_assert(!X2 || (AM && BMJ), "fp16x2: weight-gradient layout only");
     constexpr int NP = X2 ? 2 : 3;
     constexpr int OPER = NP * GV_PLANE;
@@ -86,37 +65,12 @@ __global__ __launch_bounds__(256, X2 ? 4 : 3) void gi_b3v_kernel(const GvBatch b
     const int wm = wid >> 1, wn = wid & 1, l31 = lane & 31, lhi = lane >> 5;
 
     // ---- tile (block-uniform) ----------------------------------------------------------------------
-    int pi = 0;
-    while (pi < b.n - 1 && (int)blockIdx.x >= b.start[pi + 1]) ++pi;
-    const gi_gemm_params& p = b.p[pi];
-    int local = blockIdx.x - b.start[pi];
-    if (b.remap) {                                  // XCD-aware tile order (gi_gemm.hip), bijective
-        const int tiles = b.start[pi + 1] - b.start[pi];
-        const int q = tiles >> 3, r = tiles & 7, xcd = local & 7, j = local >> 3;
-        local = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
-    const int gx = b.gx[pi], gxy = gx * b.gy[pi];
-    const int bz = local / gxy;
-    const int rem = local - bz * gxy;
-    const int by = rem / gx, bx = rem - by * gx;
-    const int m_end = p.m_dev ? min(p.M, *p.m_dev) : p.M;
-    const int m0 = by * GV_BM, n0 = bx * GV_BN;
+    const GiTile tile = gi_tile_decode<GV_BM, GV_BN, true>(b, blockIdx.x);
+    const gi_gemm_params& p = b.p[tile.pi];
+    const int m_end = tile.m_end, m0 = tile.m0, n0 = tile.n0;
     if (m0 >= m_end) return;                        // (bounded launch: beyond the rows on the device)
-    int kb = 0, ke = p.K;
-    float* Cp = p.C;
-    if (p.flags & GI_GEMM_SPLITK) {                 // reduction range of this slab
-        int g = 0, s = bz, nsp = p.nsplit;
-        if (p.ngroups) {
-            while (g < p.ngroups - 1 && s >= p.gsplit[g]) { s -= p.gsplit[g]; ++g; }
-            nsp = p.gsplit[g];
-            Cp = p.Cg[g];
-            kb = p.grp_off[g]; ke = p.grp_off[g + 1];
-        }
-        const int chunk = (((ke - kb + nsp - 1) / nsp) + 31) & ~31;
-        kb += s * chunk;
-        ke = min(kb + chunk, ke);
-        Cp += (long long)s * p.c_split_stride;
-    }
+    const int kb = tile.kb, ke = tile.ke;
+    float* const Cp = tile.Cp;
     const int nk = ke > kb ? (ke - kb + GV_BK - 1) / GV_BK : 0;
     const int n_full = ke > kb ? (ke - kb) / GV_BK : 0;
     float sa = 1.f, ia = 1.f, sb = 1.f, ib = 1.f;               // fp16x2: per-tensor power-of-two scales
@@ -209,10 +163,10 @@ __global__ __launch_bounds__(256, X2 ? 4 : 3) void gi_b3v_kernel(const GvBatch b
             gx_split2(x[0], x[1], s, a0, a1); gx_split2(x[2], x[3], s, b0, b1);
             gx_split2(x[4], x[5], s, c0, c1); gx_split2(x[6], x[7], s, d0, d1);
         } else {
-        gv_split2(x[0], x[1], a0, a1, a2);
-        gv_split2(x[2], x[3], b0, b1, b2);
-        gv_split2(x[4], x[5], c0, c1, c2);
-        gv_split2(x[6], x[7], d0, d1, d2);
+        gi_bf3_split2(x[0], x[1], a0, a1, a2);
+        gi_bf3_split2(x[2], x[3], b0, b1, b2);
+        gi_bf3_split2(x[4], x[5], c0, c1, c2);
+        gi_bf3_split2(x[6], x[7], d0, d1, d2);
         }
         q0.x = a0; q0.y = b0; q0.z = c0; q0.w = d0;
         q1.x = a1; q1.y = b1; q1.z = c1; q1.w = d1;
@@ -229,7 +183,7 @@ __global__ __launch_bounds__(256, X2 ? 4 : 3) void gi_b3v_kernel(const GvBatch b
             gv_u32x2 w0, w1, w2;
             unsigned x0, x1, x2 = 0, y0, y1, y2 = 0;
             if (X2) { gx_split2(v.x, v.y, scale, x0, x1); gx_split2(v.z, v.w, scale, y0, y1); }
-            else { gv_split2(v.x, v.y, x0, x1, x2); gv_split2(v.z, v.w, y0, y1, y2); }
+            else { gi_bf3_split2(v.x, v.y, x0, x1, x2); gi_bf3_split2(v.z, v.w, y0, y1, y2); }
             w0.x = x0; w0.y = y0; w1.x = x1; w1.y = y1; w2.x = x2; w2.y = y2;
             *reinterpret_cast<gv_u32x2*>(S + w[i]) = w0;
             *reinterpret_cast<gv_u32x2*>(S + GV_PLANE + w[i]) = w1;
@@ -380,7 +334,7 @@ __global__ __launch_bounds__(256, X2 ? 4 : 3) void gi_b3v_kernel(const GvBatch b
             for (int r = 0; r < 16; ++r) {
                 const int row = row0 + 8 * (r >> 2) + (r & 3);
                 const bool ok = col_ok & (row < m_end);
-                float* dst = ok ? Cp + (long long)row * p.ldc + col : gv_sink + tid;
+                float* dst = ok ? Cp + (long long)row * p.ldc + col : gi_sink + tid;
                 *dst = v[r];
                 amax = fmaxf(amax, ok ? fabsf(v[r]) : 0.f);
             }
@@ -395,39 +349,26 @@ __global__ __launch_bounds__(256, X2 ? 4 : 3) void gi_b3v_kernel(const GvBatch b
 
 int g_b3v_enabled = -1;
 
+// fp32 operands only (no pre-split images), no row gathers on A, even leading dimensions for major operands (8-byte
+// column pairs), 32-bit offsets for contig ones; fp16x2: the weight-gradient layout only, a gathered B with it only
+constexpr GiGemmCaps GV_CAPS = {
+    /*BM, BN*/ GV_BM, GV_BN, /*layouts*/ GI_LAY_CC | GI_LAY_CM | GI_LAY_MM,
+    /*strip*/ GI_GEMM_BF3 | GI_GEMM_BF3B_F32 | GI_GEMM_X2 | GI_GEMM_T128, /*epi_classes*/ 0xf, /*images*/ false,
+    /*x2_layouts*/ GI_LAY_MM, /*x2_slabs_plain*/ true, /*a_idx*/ false, /*b_idx*/ GI_BIDX_X2_SLABS, /*k_dev*/ false, /*m_dev*/ true, /*ones_col*/ true,
+    /*splitk_layouts*/ GI_LAY_MM, /*groups*/ GI_GROUPS_SLABS, /*need_ptrs*/ true, /*need_ld*/ true, /*even_major_ld*/ true,
+    /*pad_major*/ false, /*limit_all*/ false, /*k_min*/ 0, /*order*/ GI_ORDER_ROWS_X2SLABS,
+    /*limits_last*/ false, /*flags_last*/ false, /*bidx_last*/ false};
+
 }  // namespace
 
 // Process-wide switch (measurement aid): route eligible GI_GEMM_BF3 launches to the 32-deep-tile kernels of this
 // file (1, default; environment GI_B3V) or to the round-3 kernel (0).  on < 0 only queries; returns the previous value.
-extern "C" int gi_b3v_enable(int on) {
-    if (g_b3v_enabled < 0) {
-        const char* e = getenv("GI_B3V");
-        g_b3v_enabled = e ? (atoi(e) != 0) : 1;
-    }
-    const int prev = g_b3v_enabled;
-    if (on >= 0) g_b3v_enabled = on ? 1 : 0;
-    return prev;
-}
+extern "C" int gi_b3v_enable(int on) { return gi_env_switch(g_b3v_enabled, "GI_B3V", 1, on); }
 
 // Can this launch run here?  fp32 operands only (no pre-split images), no row gathers, even leading dimensions
 // for major operands (8-byte column pairs), 32-bit offsets for contig ones.
 bool gi_b3v_eligible(const gi_gemm_params* probs, int n) {
-    if (!gi_b3v_enable(-1)) return false;
-    for (int i = 0; i < n; ++i) {
-        const gi_gemm_params& p = probs[i];
-        if (!(p.flags & GI_GEMM_BF3) || (p.flags & GI_GEMM_BF3A)) return false;
-        // fp16x2 (round 6): the weight-gradient layout, every problem of the launch alike
-        if (((p.flags & GI_GEMM_X2) != 0) != ((probs[0].flags & GI_GEMM_X2) != 0)) return false;
-        if ((p.flags & GI_GEMM_X2) && !(p.a_amax && p.b_amax)) return false;
-        if ((p.flags & GI_GEMM_X2) && !(p.a_major && p.b_major)) return false;
-        if (p.a_major != probs[0].a_major || p.b_major != probs[0].b_major) return false;
-        if (p.a_major && !p.b_major) return false;
-        if (!p.b_major && !(p.flags & GI_GEMM_BF3B_F32)) return false;      // contig B must be plain fp32, not an image
-        if (p.a_idx || p.k_dev) return false;
-        if (p.b_idx && !((p.flags & GI_GEMM_X2) && (p.flags & GI_GEMM_SPLITK))) return false;    // gathered B: fp16x2 slabs only
-        if ((p.b_idx != nullptr) != (probs[0].b_idx != nullptr)) return false;
-    }
-    return true;
+    return gi_b3v_enable(-1) && gi_plan_routable(probs, n, GV_CAPS);
 }
 // fp16x2 weight-gradient launches go to the pipelined 128 x 256 kernel (gi_gemm_b3p.hip) unless they ask for this one
 bool gi_b3v_wants(const gi_gemm_params* probs, int n) {
@@ -437,68 +378,19 @@ bool gi_b3v_wants(const gi_gemm_params* probs, int n) {
 }
 
 int gi_b3v_launch(const gi_gemm_params* probs, int n, void* stream) {
-    GvBatch b;
-    memset(&b, 0, sizeof(b));
-    double flops = 0;
-    int total = 0, k = 0, epi = -1;
+    GiGemmBatch b;
+    double flops;
+    int epi;
+    if (int rc = gi_plan_build(probs, n, GV_CAPS, &b, &flops, &epi)) return rc;
+    if (b.n == 0) return 0;
+    const int total = b.total;
     const bool am = probs[0].a_major != 0, bmj = probs[0].b_major != 0;
-    for (int i = 0; i < n; ++i) {
-        const gi_gemm_params& p = probs[i];
-        const bool splitk = (p.flags & GI_GEMM_SPLITK) != 0;
-        if (!p.A || !p.B || p.M < 0 || p.N <= 0 || p.K < 0 || p.nsplit < 1 || p.ngroups < 0 ||
-            p.ngroups > GI_MAX_GROUPS)
-            return GI_EINVAL;
-        if (!splitk && (p.nsplit != 1 || p.ngroups)) return GI_EINVAL;
-        if (p.ngroups && !p.grp_off) return GI_EINVAL;
-        if (!p.ngroups && !p.C) return GI_EINVAL;
-        if (splitk && (!am || !bmj || p.m_dev)) return GI_EINVAL;            // slabs: weight-gradient layout only
-        if (p.ones_col >= 0 && (!bmj || p.ones_col != p.N - 1)) return GI_EINVAL;
-        const int f = p.flags & ~(GI_GEMM_BF3 | GI_GEMM_BF3B_F32 | GI_GEMM_SPLITK | GI_GEMM_X2 | GI_GEMM_T128);
-        if (f & ~(GI_EPI_BIAS | GI_EPI_SELU | GI_EPI_DSELU | GI_EPI_ACCUM | GI_EPI_MULACT)) return GI_EINVAL;
-        if ((f & GI_EPI_BIAS) && !p.bias) return GI_EINVAL;
-        if ((f & (GI_EPI_DSELU | GI_EPI_MULACT)) && !p.act) return GI_EINVAL;
-        if (((p.flags & GI_GEMM_X2) != 0) != ((probs[0].flags & GI_GEMM_X2) != 0)) return GI_EINVAL;
-        if ((p.flags & GI_GEMM_X2) && (!p.a_amax || !p.b_amax || (splitk && f != 0))) return GI_EINVAL;
-        if ((p.b_idx != nullptr) != (probs[0].b_idx != nullptr) || (p.b_idx && !(p.flags & GI_GEMM_X2))) return GI_EINVAL;
-        const long long lim = 0xffffffffLL / 4;
-        const int bcols = p.ones_col >= 0 ? p.ones_col : p.N;
-        if (!am) {
-            if (p.lda < p.K || (p.K < 4 && p.lda < 4) || (long long)p.M * p.lda > lim) return p.lda < p.K ? GI_EINVAL : GI_ELIMIT;
-        } else if (p.lda < p.M + (p.M & 1) || p.M < 1) return GI_EINVAL;
-        if (!bmj) {
-            if (p.ldb < p.K || (p.K < 4 && p.ldb < 4) || (long long)p.N * p.ldb > lim) return p.ldb < p.K ? GI_EINVAL : GI_ELIMIT;
-        } else if (p.ldb < bcols + (bcols & 1) || bcols < 1) return GI_EINVAL;
-        const int e = splitk ? (f == 0 ? 3 : 0)
-                             : (f == (GI_EPI_BIAS | GI_EPI_SELU) ? 1 : (f == GI_EPI_DSELU ? 2 : (f == 0 ? 3 : 0)));
-        epi = (epi < 0 || epi == e) ? e : 0;
-        if (p.M == 0) continue;
-        int zs = 1;
-        if (splitk) {
-            zs = p.nsplit;
-            if (p.ngroups) { zs = 0; for (int g = 0; g < p.ngroups; ++g) { if (p.gsplit[g] < 1) return GI_EINVAL; zs += p.gsplit[g]; } }
-        }
-        b.p[k] = p; b.p[k].flags = f | (splitk ? GI_GEMM_SPLITK : 0);
-        b.gx[k] = gi_cdiv(p.N, GV_BN); b.gy[k] = gi_cdiv(p.M, GV_BM);
-        b.start[k] = total;
-        if ((long long)b.gx[k] * b.gy[k] * zs + total > 0x3fffffff) return GI_ELIMIT;
-        total += b.gx[k] * b.gy[k] * zs;
-        flops += 2.0 * (double)p.M * (double)p.N * (double)p.K;
-        ++k;
-    }
-    if (k == 0) return 0;
-    b.start[k] = total; b.n = k; b.total = total;
-    bool bounded = false;
-    for (int i = 0; i < k; ++i) bounded |= b.p[i].m_dev != nullptr;
-    b.remap = (total >= 512 && !bounded && !am) ? 1 : 0;
-    hipStream_t st = (hipStream_t)stream;
     const bool x2 = (probs[0].flags & GI_GEMM_X2) != 0, bidx = probs[0].b_idx != nullptr;
+    if (x2 && epi != 3) return GI_EINVAL;                // (fp16x2: weight-gradient slabs with plain stores only)
+    hipStream_t st = (hipStream_t)stream;
     GiProfScope prof(st, GI_PROF_GEMM | (x2 ? GI_PROF_PIPE_X2 : GI_PROF_PIPE_BF3), flops);
-    gi_gemm_log_launch(x2 ? "v2" : (am ? "b2" : (bmj ? "b1" : "b0")), b.p, k, total, flops);
-    if (x2) {                                            // (weight-gradient slabs: plain stores)
-        if (!am || epi != 3) return GI_EINVAL;
-        // weight-gradient launches: consecutive tile ids = the tiles of ONE slab, which read the same rows of both
-        // operands — one XCD (one L2) per slab instead of eight (gi_gemm_b3p.hip)
-        if (total >= 16 && !bounded) b.remap = 1;
+    gi_gemm_log_launch(x2 ? "v2" : (am ? "b2" : (bmj ? "b1" : "b0")), b.p, b.n, total, flops);
+    if (x2) {
         if (bidx) hipLaunchKernelGGL((gi_b3v_kernel<true, true, 3, true, true>), dim3(total), dim3(256), 0, st, b);
         else hipLaunchKernelGGL((gi_b3v_kernel<true, true, 3, true, false>), dim3(total), dim3(256), 0, st, b);
         return gi_launch_status();

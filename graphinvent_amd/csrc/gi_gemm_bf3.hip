@@ -30,39 +30,22 @@
 #include <type_traits>
 
 #include "gi_common.h"
+#include "gi_gemm_plan.h"
 #include "gi_mfma.h"
 #include "gi_x2.h"
 
 typedef __bf16 gi_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 gi_bf16x2 __attribute__((ext_vector_type(2)));
 typedef float gi_f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned gi_u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned gi_u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-__device__ float b3_sink[256];           // where out-of-range lanes of edge tiles store
-
 constexpr int B3_BM = 128, B3_BN = 128, B3_BK = 16;
 constexpr int B3_ROWB = B3_BK * 2;                 // bytes of one row of one plane of a k tile (16 bf16)
 constexpr int B3_PLANE = 128 * B3_ROWB;            // 4 KB
 
 __host__ __device__ inline int b3_r32(int k) { return (k + 31) & ~31; }
-
-__device__ __forceinline__ unsigned b3_pk(float lo, float hi) {
-    gi_f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, gi_bf16x2));     // v_cvt_pk_bf16_f32 (RNE)
-}
-__device__ __forceinline__ float b3_lo(unsigned p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float b3_hi(unsigned p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
-// two fp32 values -> their three bf16 planes, packed pairwise (low half = x0)
-__device__ __forceinline__ void b3_split2(float x0, float x1, unsigned& p0, unsigned& p1, unsigned& p2) {
-    p0 = b3_pk(x0, x1);
-    const float r0 = x0 - b3_lo(p0), r1 = x1 - b3_hi(p0);
-    p1 = b3_pk(r0, r1);
-    const float s0 = r0 - b3_lo(p1), s1 = r1 - b3_hi(p1);
-    p2 = b3_pk(s0, s1);
-}
 
 // ---- operand image ------------------------------------------------------------------------------------
 struct B3PackArgs {
@@ -91,21 +74,13 @@ __global__ __launch_bounds__(256) void gi_bf3_pack_kernel(const B3PackArgs a) {
         return;
     }
     unsigned p0, p1, p2;
-    b3_split2(src(k), src(k + 1), p0, p1, p2);
+    gi_bf3_split2(src(k), src(k + 1), p0, p1, p2);
     unsigned* img = reinterpret_cast<unsigned*>(d.image);
     const long long plane = (long long)d.rows * half, at = (long long)n * half + (k >> 1);
     img[at] = p0; img[plane + at] = p1; img[2 * plane + at] = p2;
 }
 
 // ---- GEMM ---------------------------------------------------------------------------------------------
-struct B3Batch {
-    gi_gemm_params p[8];
-    int start[9];
-    int gx[8];
-    int n, total;
-    int remap;                                 // XCD-aware tile order (launches of many workgroups)
-};
-
 // EPI: 0 = epilogue from the run-time flags, 1 = bias + SELU (forward), 2 = * selu'(act) (dgrad).
 // APL: the A operand is a pre-split image too (GI_GEMM_BF3A: three bf16 planes [M][Kp], what an epilogue with
 // gi_gemm_params.planes wrote): its staging is then a plain copy like B's.
@@ -115,7 +90,7 @@ struct B3Batch {
 // two LDS planes per operand, three f16 MFMA products per fp32 product, scales from a_amax / b_amax, 1 / (sa sb) in
 // the epilogue.
 template <int EPI, bool APL, bool BFP, bool X2 = false>
-__global__ __launch_bounds__(256, 3) void gi_gemm_bf3_kernel(const B3Batch b) {
+__global__ __launch_bounds__(256, 3) void gi_gemm_bf3_kernel(const GiGemmBatch b) {
     constexpr int NP = X2 ? 2 : 3;
     constexpr int OPER = NP * B3_PLANE, BUF = 2 * OPER;           // one operand of a k tile (NP planes), A + B
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * BUF];
@@ -123,21 +98,9 @@ __global__ __launch_bounds__(256, 3) void gi_gemm_bf3_kernel(const B3Batch b) {
     const int wm = wid >> 1, wn = wid & 1, l31 = lane & 31, lhi = lane >> 5;
 
     // ---- tile (block-uniform) ----------------------------------------------------------------------
-    int pi = 0;
-    while (pi < b.n - 1 && (int)blockIdx.x >= b.start[pi + 1]) ++pi;
-    const gi_gemm_params& p = b.p[pi];
-    int local = blockIdx.x - b.start[pi];
-    {   // XCD-aware tile order (as in gi_gemm.hip): consecutive workgroup ids go round-robin to the 8 XCDs; the
-        // remap lets one XCD walk consecutive tiles, so the column tiles that share an A row panel hit one L2
-        const int tiles = b.start[pi + 1] - b.start[pi];
-        if (b.remap) {
-            const int q = tiles >> 3, r = tiles & 7, xcd = local & 7, j = local >> 3;
-            local = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-        }
-    }
-    const int by = local / b.gx[pi], bx = local - by * b.gx[pi];
-    const int m_end = p.m_dev ? min(p.M, *p.m_dev) : p.M;
-    const int m0 = by * B3_BM, n0 = bx * B3_BN;
+    const GiTile tile = gi_tile_decode<B3_BM, B3_BN, false>(b, blockIdx.x);
+    const gi_gemm_params& p = b.p[tile.pi];
+    const int bx = tile.bx, m_end = tile.m_end, m0 = tile.m0, n0 = tile.n0;
     if (m0 >= m_end) return;                                   // (bounded launch: beyond the rows on the device)
     const int K = p.K, Kp = b3_r32(K), nk = Kp / B3_BK;
     float sa = 1.f, ia = 1.f, sb = 1.f, ib = 1.f;               // fp16x2: per-tensor power-of-two scales
@@ -252,8 +215,8 @@ __global__ __launch_bounds__(256, 3) void gi_gemm_bf3_kernel(const B3Batch b) {
                 gx_split2(v.x, v.y, sa, x0, x1);
                 gx_split2(v.z, v.w, sa, y0, y1);
             } else {
-                b3_split2(v.x, v.y, x0, x1, x2);
-                b3_split2(v.z, v.w, y0, y1, y2);
+                gi_bf3_split2(v.x, v.y, x0, x1, x2);
+                gi_bf3_split2(v.z, v.w, y0, y1, y2);
                 w2.x = x2; w2.y = y2;
                 *reinterpret_cast<gi_u32x2*>(As + 2 * B3_PLANE + a_lds[i]) = w2;
             }
@@ -272,8 +235,8 @@ __global__ __launch_bounds__(256, 3) void gi_gemm_bf3_kernel(const B3Batch b) {
                     gx_split2(v.x, v.y, sb, x0, x1);
                     gx_split2(v.z, v.w, sb, y0, y1);
                 } else {
-                    b3_split2(v.x, v.y, x0, x1, x2);
-                    b3_split2(v.z, v.w, y0, y1, y2);
+                    gi_bf3_split2(v.x, v.y, x0, x1, x2);
+                    gi_bf3_split2(v.z, v.w, y0, y1, y2);
                     w2.x = x2; w2.y = y2;
                     *reinterpret_cast<gi_u32x2*>(Bs + 2 * B3_PLANE + bf_lds[i]) = w2;
                 }
@@ -420,7 +383,7 @@ __global__ __launch_bounds__(256, 3) void gi_gemm_bf3_kernel(const B3Batch b) {
             for (int r = 0; r < 16; ++r) {
                 const int row = row0 + 8 * (r >> 2) + (r & 3);
                 const bool ok = col_ok & (row < m_end);
-                float* dst = ok ? p.C + (long long)row * p.ldc + col : b3_sink + tid;
+                float* dst = ok ? p.C + (long long)row * p.ldc + col : gi_sink + tid;
                 *dst = v[r];
                 amax = fmaxf(amax, ok ? fabsf(v[r]) : 0.f);
             }
@@ -428,6 +391,16 @@ __global__ __launch_bounds__(256, 3) void gi_gemm_bf3_kernel(const B3Batch b) {
     }
     if (p.c_amax) gx_amax_publish(amax, p.c_amax);       // for the fp16x2 launches that read this tensor next
 }
+
+// A contig fp32 or a pre-split image, B an image or contig fp32 (every problem alike); no groups, split-K or gathers
+// (32-bit operand offsets: a gathered row index is not bounded by M, so its offset cannot be checked); fp16x2 with both
+// operands plain fp32
+constexpr GiGemmCaps B3_CAPS = {
+    /*BM, BN*/ B3_BM, B3_BN, /*layouts*/ GI_LAY_CC, /*strip*/ GI_GEMM_BF3 | GI_GEMM_BF3A | GI_GEMM_BF3B_F32 | GI_GEMM_X2,
+    /*epi_classes*/ 0x7, /*images*/ true, /*x2_layouts*/ GI_LAY_CC, /*x2_slabs_plain*/ false, /*a_idx*/ false,
+    /*b_idx*/ GI_BIDX_NONE, /*k_dev*/ false, /*m_dev*/ true, /*ones_col*/ false, /*splitk_layouts*/ 0, /*groups*/ GI_GROUPS_NONE, /*need_ptrs*/ true,
+    /*need_ld*/ true, /*even_major_ld*/ false, /*pad_major*/ false, /*limit_all*/ false, /*k_min*/ 1, /*order*/ GI_ORDER_ROWS,
+    /*limits_last*/ true, /*flags_last*/ false, /*bidx_last*/ false};
 
 }  // namespace
 
@@ -462,61 +435,14 @@ int gi_gemm_bf3_launch(const gi_gemm_params* probs, int n, void* stream) {
     if (gi_b3v_wants(probs, n)) return gi_b3v_launch(probs, n, stream);        // GI_GEMM_T128: fp16x2 weight gradients, 128 x 128 tiles
     if (gi_b3p_eligible(probs, n)) return gi_b3p_launch(probs, n, stream);     // forward / dgrad: ping-pong kernel
     if (gi_b3v_eligible(probs, n)) return gi_b3v_launch(probs, n, stream);     // 32-deep tiles, all three layouts
-    B3Batch b;
-    memset(&b, 0, sizeof(b));
-    double flops = 0;
-    int total = 0, k = 0;
-    int epi = -1, napl = 0;
-    for (int i = 0; i < n; ++i) napl += (probs[i].flags & GI_GEMM_BF3A) != 0;
-    if (napl && napl != n) return GI_EINVAL;
-    const bool apl = napl != 0;
-    int nbfp = 0;
-    for (int i = 0; i < n; ++i) nbfp += (probs[i].flags & GI_GEMM_BF3B_F32) != 0;
-    if (nbfp && nbfp != n) return GI_EINVAL;
-    const bool bfp = nbfp != 0;
-    int nx2 = 0;
-    for (int i = 0; i < n; ++i) nx2 += (probs[i].flags & GI_GEMM_X2) != 0;
-    if (nx2 && (nx2 != n || !bfp || apl)) return GI_EINVAL;       // fp16x2: every problem, both operands plain fp32
-    const bool x2 = nx2 != 0;
-    for (int i = 0; i < n; ++i) if (x2 && (!probs[i].a_amax || !probs[i].b_amax)) return GI_EINVAL;
-    for (int i = 0; i < n; ++i) {
-        const gi_gemm_params& p = probs[i];
-        if (p.a_major || p.b_major || p.ngroups || p.b_idx || p.nsplit != 1 || p.k_dev || !p.A || !p.B || !p.C)
-            return GI_EINVAL;
-        if (p.M < 0 || p.N <= 0 || p.K <= 0 || (!apl && p.lda < p.K)) return GI_EINVAL;
-        if (apl && (p.a_idx || ((uintptr_t)p.A & 15) != 0)) return GI_EINVAL;
-        // operands are addressed by 32-bit byte offsets: a gathered row index is not bounded by M, so its offset
-        // cannot be checked here (round-3 advisor finding) — the bf16x3 path takes no row gather (the model's
-        // launches have none); and the 16-byte k chunks clamp into [0, 4): rows shorter than 4 floats need padding
-        if (p.a_idx) return GI_EINVAL;
-        if (p.K < 4 && ((!apl && p.lda < 4) || (bfp && p.ldb < 4))) return GI_EINVAL;
-        if (!bfp && ((uintptr_t)p.B & 15) != 0) return GI_EINVAL;
-        if (bfp && p.ldb < p.K) return GI_EINVAL;
-        const int f = p.flags & ~(GI_GEMM_BF3 | GI_GEMM_BF3A | GI_GEMM_BF3B_F32 | GI_GEMM_X2);
-        if (f & ~(GI_EPI_BIAS | GI_EPI_SELU | GI_EPI_DSELU | GI_EPI_ACCUM | GI_EPI_MULACT)) return GI_EINVAL;
-        if ((f & GI_EPI_BIAS) && !p.bias) return GI_EINVAL;
-        if ((f & (GI_EPI_DSELU | GI_EPI_MULACT)) && !p.act) return GI_EINVAL;
-        const long long lim = 0xffffffffLL / 4;
-        if (!p.a_idx && (long long)p.M * p.lda > lim) return GI_ELIMIT;
-        if ((long long)p.N * b3_r32(p.K) * 2 > 0xffffffffLL || (bfp && (long long)p.N * p.ldb > lim)) return GI_ELIMIT;
-        const int e = f == (GI_EPI_BIAS | GI_EPI_SELU) ? 1 : (f == GI_EPI_DSELU ? 2 : 0);
-        epi = (epi < 0 || epi == e) ? e : 0;
-        if (p.M == 0) continue;
-        b.p[k] = p; b.p[k].flags = f;
-        b.gx[k] = gi_cdiv(p.N, B3_BN);
-        b.start[k] = total;
-        total += b.gx[k] * gi_cdiv(p.M, B3_BM);
-        flops += 2.0 * (double)p.M * (double)p.N * (double)p.K;
-        ++k;
-    }
-    if (k == 0) return 0;
-    b.start[k] = total; b.n = k; b.total = total;
-    {
-        bool bounded = false;
-        for (int i = 0; i < k; ++i) bounded |= b.p[i].m_dev != nullptr;
-        // measured on the node-level hidden-layer launch (684 tiles): 76.7 -> 73.0 us forward, 84.0 -> 82.1 dgrad
-        b.remap = (total >= 512 && !bounded) ? 1 : 0;       // (bounded: the order would be over the bound's tiles)
-    }
+    GiGemmBatch b;
+    double flops;
+    int epi;
+    if (int rc = gi_plan_build(probs, n, B3_CAPS, &b, &flops, &epi)) return rc;
+    if (b.n == 0) return 0;
+    const int total = b.total, k = b.n;
+    const bool apl = (probs[0].flags & GI_GEMM_BF3A) != 0, bfp = (probs[0].flags & GI_GEMM_BF3B_F32) != 0;
+    const bool x2 = (probs[0].flags & GI_GEMM_X2) != 0;
     if (x2 && (epi == 1 || epi == 2)) {
         // forward / dgrad epilogues: the column-split kernel (gi_gemm_x2n.hip), the same results bit for bit;
         // GI_X2N=0 (read per launch: a test compares both) keeps them here

@@ -22,14 +22,13 @@
 #include <type_traits>
 
 #include "gi_common.h"
+#include "gi_gemm_plan.h"
 #include "gi_mfma.h"
 #include "gi_x2.h"
 
 typedef unsigned xn_u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
-
-__device__ float xn_sink[256];           // where out-of-range lanes of edge tiles store
 
 constexpr int XN_BM = 128, XN_BN = 128, XN_BK = 32;           // block tile; k step = two 16-deep MFMA blocks
 constexpr int XN_ROWB = 32;                                   // bytes of one row of one plane of a 16-deep block
@@ -40,30 +39,12 @@ constexpr int XN_BUF = 2 * XN_SUB;                            // one 32-deep ste
 
 __host__ __device__ inline int xn_r32(int k) { return (k + 31) & ~31; }
 
-struct XnBatch {
-    gi_gemm_params p[8];
-    int gx[8];                                 // column tiles
-    int start[9];                              // first tile of each problem in gi_gemm_bf3_kernel's numbering
-    int n;
-    int old_remap;                             // gi_gemm_bf3_kernel would have walked the tiles in XCD order
-};
-
 // m_end of problem i (device)
 __device__ __forceinline__ int xn_m_end(const gi_gemm_params& p) { return p.m_dev ? max(min(p.M, *p.m_dev), 0) : p.M; }
 
-// the workgroup id gi_gemm_bf3_kernel would have run tile `local` of a problem with (the inverse of its XCD remap)
-__device__ __forceinline__ int xn_old_block(int local, int tiles, bool remap) {
-    if (!remap) return local;
-    const int q = tiles >> 3, r = tiles & 7;
-    int xcd, j;
-    if (local < r * (q + 1)) { xcd = local / (q + 1); j = local - xcd * (q + 1); }
-    else { const int l = local - r * (q + 1); xcd = r + l / q; j = l - (xcd - r) * q; }
-    return j * 8 + xcd;
-}
-
 // EPI: 1 = bias + SELU (forward), 2 = * selu'(act) (dgrad)
 template <int EPI>
-__global__ __launch_bounds__(256, 3) void gi_gemm_x2n_kernel(const XnBatch b) {
+__global__ __launch_bounds__(256, 3) void gi_gemm_x2n_kernel(const GiGemmBatch b) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * XN_BUF];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int l31 = lane & 31, lhi = lane >> 5;
@@ -262,48 +243,44 @@ __global__ __launch_bounds__(256, 3) void gi_gemm_x2n_kernel(const XnBatch b) {
         for (int r = 0; r < 16; ++r) {
             const int row = row0 + 8 * (r >> 2) + (r & 3);
             const bool ok = col_ok & (row < m_end);
-            float* dst = ok ? p.C + (long long)row * p.ldc + col : xn_sink + tid;
+            float* dst = ok ? p.C + (long long)row * p.ldc + col : gi_sink + tid;
             *dst = v[r];
             amax[t >> 1] = fmaxf(amax[t >> 1], ok ? fabsf(v[r]) : 0.f);
         }
     }
     if (p.c_amax) {                   // the slots of gi_gemm_bf3_kernel's wave (wm, wn) = (half, wid >> 1) of this tile
         const int tiles = b.start[pi + 1] - b.start[pi];
-        const int blk = b.start[pi] + xn_old_block(by * b.gx[pi] + bx, tiles, b.old_remap != 0);
+        const int local = by * b.gx[pi] + bx;       // the workgroup gi_gemm_bf3_kernel would have run this tile with
+        const int blk = b.start[pi] + (b.old_remap ? gi_xcd_remap_inv(local, tiles) : local);
 #pragma unroll
         for (int h = 0; h < 2; ++h)
             gx_amax_publish_slot(amax[h], p.c_amax, (blk * 4 + 2 * h + (wid >> 1)) & (GX_AMAX_SLOTS - 1));
     }
 }
 
+// gi_gemm_bf3_kernel's fp16x2 launches: both operands plain fp32 with k contiguous, both amax cells
+constexpr GiGemmCaps XN_CAPS = {
+    /*BM, BN*/ XN_BM, XN_BN, /*layouts*/ GI_LAY_CC, /*strip*/ GI_GEMM_BF3 | GI_GEMM_BF3A | GI_GEMM_BF3B_F32 | GI_GEMM_X2,
+    /*epi_classes*/ 0x7, /*images*/ false, /*x2_layouts*/ GI_LAY_CC, /*x2_slabs_plain*/ false, /*a_idx*/ false,
+    /*b_idx*/ GI_BIDX_NONE, /*k_dev*/ false, /*m_dev*/ true, /*ones_col*/ false, /*splitk_layouts*/ 0, /*groups*/ GI_GROUPS_NONE, /*need_ptrs*/ true,
+    /*need_ld*/ true, /*even_major_ld*/ false, /*pad_major*/ false, /*limit_all*/ false, /*k_min*/ 1, /*order*/ GI_ORDER_NONE,
+    /*limits_last*/ true, /*flags_last*/ false, /*bidx_last*/ false};
+
 }  // namespace
 
 // gi_gemm_bf3_launch hands fp16x2 launches of plain fp32 operands with the forward / dgrad epilogue here (validated
 // there: every problem GI_GEMM_X2 | GI_GEMM_BF3B_F32, no gathers, both amax cells, 32-bit offsets)
 int gi_x2n_launch(const gi_gemm_params* probs, int n, int epi, void* stream) {
-    if (n < 1 || n > 8 || (epi != 1 && epi != 2)) return GI_EINVAL;
-    XnBatch b;
-    memset(&b, 0, sizeof(b));
-    double flops = 0;
-    int k = 0, total = 0, grid = 0;
-    bool bounded = false;
-    for (int i = 0; i < n; ++i) {
-        const gi_gemm_params& p = probs[i];
-        if (p.M == 0) continue;
-        b.p[k] = p;
-        b.p[k].flags = p.flags & ~(GI_GEMM_BF3 | GI_GEMM_BF3A | GI_GEMM_BF3B_F32 | GI_GEMM_X2);
-        b.gx[k] = gi_cdiv(p.N, XN_BN);
-        b.start[k] = total;
-        const int rows = gi_cdiv(p.M, XN_BM);
-        total += b.gx[k] * rows;
-        grid += 8 * ((rows + 7) / 8) * b.gx[k];          // room for every XCD's share, whatever the real row count
-        bounded |= p.m_dev != nullptr;
-        flops += 2.0 * (double)p.M * (double)p.N * (double)p.K;
-        ++k;
-    }
-    if (k == 0) return 0;
-    b.start[k] = total; b.n = k;
-    b.old_remap = (total >= 512 && !bounded) ? 1 : 0;       // (gi_gemm_bf3_launch's rule, for the c_amax slots)
+    GiGemmBatch b;
+    double flops;
+    int e;
+    if (int rc = gi_plan_build(probs, n, XN_CAPS, &b, &flops, &e)) return rc;
+    if (e != epi || (epi != 1 && epi != 2)) return GI_EINVAL;
+    if (b.n == 0) return 0;
+    const int k = b.n, total = b.total;
+    int grid = 0;
+    for (int i = 0; i < k; ++i) grid += 8 * ((b.gy[i] + 7) / 8) * b.gx[i];   // room for every XCD's share, whatever the real row count
+    b.old_remap = gi_order_rows(total, gi_plan_bounded(b)) ? 1 : 0;          // (for the c_amax slots)
     hipStream_t st = (hipStream_t)stream;
     GiProfScope prof(st, GI_PROF_GEMM | GI_PROF_PIPE_X2, flops);
     gi_gemm_log_launch(epi == 1 ? "x0" : "x1", b.p, k, total, flops);

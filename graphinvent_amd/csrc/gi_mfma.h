@@ -33,3 +33,19 @@ __device__ __forceinline__ v4f gi_fix4(v4f w, int col, int cmax, int ncols, bool
     return r;
 }
 
+// fp32 -> bf16 planes of the bf16x3 kernels: two fp32 values -> their three bf16 parts x = p0 + p1 + p2 (round to
+// nearest even; both residuals are exact in fp32), packed pairwise (low half = x0)
+typedef __bf16 gi_bf16x2_t __attribute__((ext_vector_type(2)));
+typedef float gi_f32x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned gi_bf3_pk(float lo, float hi) {
+    gi_f32x2_t v = {lo, hi};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, gi_bf16x2_t));     // v_cvt_pk_bf16_f32 (RNE)
+}
+__device__ __forceinline__ float gi_bf3_lo(unsigned p) { return __builtin_bit_cast(float, p << 16); }
+__device__ __forceinline__ float gi_bf3_hi(unsigned p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
+__device__ __forceinline__ void gi_bf3_split2(float x0, float x1, unsigned& p0, unsigned& p1, unsigned& p2) {
+    p0 = gi_bf3_pk(x0, x1);
+    const float r0 = x0 - gi_bf3_lo(p0), r1 = x1 - gi_bf3_hi(p0);
+    p1 = gi_bf3_pk(r0, r1);
+    p2 = gi_bf3_pk(r0 - gi_bf3_lo(p1), r1 - gi_bf3_hi(p1));
+}

@@ -22,6 +22,7 @@
 #include <mutex>
 
 #include "gi_common.h"
+#include "gi_gemm_plan.h"
 
 namespace {
 
@@ -173,14 +174,8 @@ inline float* msg_cell(float* pass_base, int which, int layer) {
 constexpr int BF3_MIN_WIDTH = 192, BF3_MIN_ROWS = 2560;
 static int g_bf3 = -1;                  // -1: not read yet
 static int g_x2 = -1;                   // fp16x2 instead of bf16x3 on those launches (environment GI_X2, default 1)
-static bool x2_enabled() {
-    if (g_x2 < 0) g_x2 = getenv("GI_X2") ? (atoi(getenv("GI_X2")) != 0) : 1;
-    return g_x2 != 0;
-}
-bool bf3_enabled() {
-    if (g_bf3 < 0) g_bf3 = getenv("GI_BF3") ? (atoi(getenv("GI_BF3")) != 0) : (GI_BF3_DEFAULT != 0);
-    return g_bf3 != 0;
-}
+static bool x2_enabled() { return gi_env_switch(g_x2, "GI_X2", 1, -1) != 0; }
+bool bf3_enabled() { return gi_env_switch(g_bf3, "GI_BF3", GI_BF3_DEFAULT != 0, -1) != 0; }
 // The message / energy stacks' chain launches as fp16x2 (64-row blocks on the f16 pipe, gi_chain.hip): with the other
 // 16-bit-pipe launches (GI_BF3, GI_X2) — the dZ chains of the BACKWARD only.  The forward keeps the fp32 chain: its
 // rows are bit-independent of one another, which the pass-0 row cache, the equality of blocking and host-sync-free
@@ -2205,17 +2200,9 @@ extern "C" int gi_ggnn_forward_ex(const gi_ggnn_dims* dp, const float* const* pa
 
 // fp16x2 instead of bf16x3 on the GI_GEMM_BF3 launches of gi_ggnn_forward / backward (environment GI_X2, default 1):
 // on = 1 / 0 sets, on < 0 queries; returns the previous setting.
-extern "C" int gi_x2_enable(int on) {
-    const int prev = x2_enabled() ? 1 : 0;
-    if (on >= 0) g_x2 = on ? 1 : 0;
-    return prev;
-}
+extern "C" int gi_x2_enable(int on) { return gi_env_switch(g_x2, "GI_X2", 1, on); }
 
-extern "C" int gi_bf3_enable(int on) {
-    const int was = bf3_enabled() ? 1 : 0;
-    if (on >= 0) g_bf3 = on ? 1 : 0;
-    return was;
-}
+extern "C" int gi_bf3_enable(int on) { return gi_env_switch(g_bf3, "GI_BF3", GI_BF3_DEFAULT != 0, on); }
 
 extern "C" long long gi_p0_cache_words(const gi_ggnn_dims* d) {
     Model m;

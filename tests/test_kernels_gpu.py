@@ -1,6 +1,7 @@
 """-m gpu: every building-block kernel, called through the C ABI, against its CPU reference
 (tests/ref_dataflow.py).  Integer work is compared bit-exactly; fp32 GEMMs within 2e-5 relative of
 an fp64 CPU product (exact-fp32 MFMA = fmaf chain, so only the summation order differs)."""
+import ctypes
 import os
 
 import numpy as np
@@ -259,6 +260,58 @@ def test_gemm_bf16x3_kernels_forward_and_dgrad_layouts_vs_fp64(M, N, K, kernel, 
         ops.gemm(Xd, Wp.to(DEV), dXm, M, N, K, lda, ldw, ops.r4(N), flags=L.EPI_DSELU | L.EPI_ACCUM | L.GEMM_BF3,
                  act=act.to(DEV), ldact=ops.r4(N), b_major=True)
         assert rel(dXm[:, :N], refd) < 2e-6
+
+
+def _forward_case(M, N, K, seed):
+    g = torch.Generator().manual_seed(seed)
+    lda, ldc = ops.r4(K) + 4, ops.r4(N) + 8
+    X = torch.randn(M, lda, generator=g)
+    W = torch.randn(N, K, generator=g) / K ** 0.5
+    b = torch.randn(N, generator=g)
+    ref = D.selu(X[:, :K].double() @ W.double().t() + b.double())
+    return X, W, b, lda, ldc, ref
+
+
+@pytest.mark.parametrize("kernel,M", [("r3", 8200), ("b3v", 8200), ("b3p", 13100)])
+def test_gemm_bf16x3_forward_in_the_remapped_tile_order(kernel, M, bf3_kernel_switches):
+    """Forward launches of 512+ tiles walk them in the XCD-aware order (gi_xcd_remap): 65 x 9 = 585 tiles of 128 x 128
+    (585 mod 8 = 1) on the round-3 and b3v kernels, 103 x 5 = 515 tiles of 128 x 256 (mod 8 = 3) on b3p; partial edge
+    tiles in both directions.  Every tile must be computed exactly once: the fp64 product at the bound of the test above,
+    nothing written outside [M, N]."""
+    lib = bf3_kernel_switches
+    lib.gi_b3p_enable(1 if kernel == "b3p" else 0)
+    lib.gi_b3v_enable(1 if kernel == "b3v" else 0)
+    os.environ["GI_B3P_ALL"] = "1"
+    N, K = 1025, 36
+    X, W, b, lda, ldc, ref = _forward_case(M, N, K, M + N)
+    Y = torch.full((M, ldc), 7.0, device=DEV)
+    ops.gemm(X.to(DEV), W.to(DEV), Y, M, N, K, lda, K, ldc, flags=L.EPI_BIAS | L.EPI_SELU | L.GEMM_BF3 | L.GEMM_BF3B_F32,
+             bias=b.to(DEV))
+    assert rel(Y[:, :N], ref) < 2e-6
+    assert bool((Y[:, N:] == 7.0).all())
+
+
+@pytest.mark.parametrize("m_real", [None, 2000])
+def test_gemm_fp32_forward_in_the_remapped_tile_order(m_real):
+    """The fp32 kernel above its tile-order threshold (38 x 37 = 1406 workgroups of 64 x 64 >= 1350, mod 8 = 6), plain
+    and bounded (m_dev = 2000 of 2370 rows: the order is then taken over the tiles that have rows): the fp64 product at
+    the bound of test_gemm_forward_bias_selu; rows from m_dev on stay untouched bit for bit."""
+    M, N, K = 2370, 2305, 36
+    X, W, b, lda, ldc, ref = _forward_case(M, N, K, 5)
+    Xd, Wd, bd = X.to(DEV), W.to(DEV), b.to(DEV)
+    Y = torch.full((M, ldc), 7.0, device=DEV)
+    m_dev = torch.tensor([m_real], dtype=torch.int32, device=DEV) if m_real is not None else None
+    p = L.GemmParams()
+    p.A, p.B, p.C, p.bias = Xd.data_ptr(), Wd.data_ptr(), Y.data_ptr(), bd.data_ptr()
+    p.M, p.N, p.K, p.lda, p.ldb, p.ldc = M, N, K, lda, K, ldc
+    p.flags, p.tm, p.tn, p.nsplit, p.ones_col = L.EPI_BIAS | L.EPI_SELU, 1, 1, 1, -1
+    p.m_dev = m_dev.data_ptr() if m_dev is not None else None
+    L.check(L.load().gi_gemm(ctypes.byref(p), ops._stream()), "gi_gemm")
+    torch.cuda.synchronize()
+    rows = M if m_real is None else m_real
+    assert rel(Y[:rows, :N], ref[:rows]) < 2e-5
+    assert bool((Y[:rows, N:] == 7.0).all())
+    assert bool((Y[rows:] == 7.0).all())
 
 
 @pytest.mark.parametrize("kernel", ["b3p", "b3v"])
