@@ -34,6 +34,10 @@ out of the tensors: per atom the index inside each one-hot segment, per graph th
 of it to the host with one copy and one synchronisation; ``records`` maps the indices through the constants' tables
 into the arguments of ``Chem.Atom`` / ``AddBond``.  Building ``rdkit.Chem.RWMol`` objects stays in the caller.
 
+``smiles`` / ``write_smi`` write the molecules as SMILES strings on the device (``gi_mol_smiles``) and as a ``.smi``
+file: the product of the reference's ``util.write_graphs_to_smi``.  The string is a faithful spelling of the labelled
+graph in an OpenSMILES subset — NOT RDKit's canonical SMILES: no aromaticity, no stereo, see ``smiles``.
+
 Counts are summed as integers on the device and converted once (the exact integer as fp32, then one fp32 division):
 bit for bit the reference's values while every count is below 2**24.  Beyond that the reference's own fp32
 accumulation (``hist[i] += 1``) stops being exact, e.g. it stays at 16777216 for ever; the counts here stay exact
@@ -128,7 +132,7 @@ def _check_termination(what: str, termination, G: int, dev):
     return termination.float().contiguous(), L.DTYPE_F32
 
 
-_ITEMSIZE = {"int8": 1, "int16": 2, "int32": 4, "int64": 8, "float32": 4}
+_ITEMSIZE = {"int8": 1, "uint8": 1, "int16": 2, "int32": 4, "int64": 8, "float32": 4}
 
 
 def _pack(*arrays) -> dict:
@@ -1148,3 +1152,194 @@ def compute_score(contributions: Sequence[torch.Tensor], *, score_type: str, thr
     final = final * uniqueness
     final = final * validity
     return final * termination
+
+
+# ---- molecule strings ------------------------------------------------------------------------------------------------
+#: status bits of ``smiles`` beyond the malformed bits of ``VALIDITY_STATUS_MESSAGES``
+SMILES_STATUS_MESSAGES = {
+    **{bit: VALIDITY_STATUS_MESSAGES[bit] for bit in (L.MOL_ONEHOT, L.MOL_BOND_PAST_N, L.MOL_VALUE, L.MOL_MULTI_BOND,
+                                                      L.MOL_ASYMMETRIC, L.MOL_NODE_PAST_N)},
+    L.SMI_EMPTY: "the molecule has no atoms: no string",
+    L.SMI_SELF_LOOP: "an atom is bonded to itself: no string",
+    L.SMI_OVER: "an atom has more bonds than any allowed valence of its element and charge (informational: the string "
+                "is written)",
+    L.SMI_FRAGMENTS: "more than one connected component, joined by '.' (informational)",
+    L.SMI_AROMATIC: "a bond of order 1.5 is present: nothing is kekulised, no string (route the molecule to RDKit)",
+    L.SMI_RING_LIMIT: "more than 99 ring bonds are open at once: no string",
+    L.SMI_TRUNCATED: "the string needs more than max_len bytes: no string, length holds the need",
+}
+#: the bits that leave the text empty
+NO_STRING_BITS = MALFORMED_BITS | L.SMI_EMPTY | L.SMI_SELF_LOOP | L.SMI_AROMATIC | L.SMI_RING_LIMIT | L.SMI_TRUNCATED
+
+
+def default_smiles_len(N: int) -> int:
+    """``smiles``' default ``max_len``: 12 N + 4 rounded up to a multiple of 16 (a default, not a bound: see
+    ``gi_mol_smiles`` in include/graphinvent_amd.h)."""
+    return (12 * int(N) + 4 + 15) // 16 * 16
+
+
+class MoleculeStrings(_ResultBuffer):
+    """What ``smiles`` wrote, on the device: ``text`` [G, max_len] uint8 (zero padded), ``length`` / ``status`` [G]
+    int32, ``atom_pos`` [G, N] int32 (the byte offset of every atom's token; -1 past n and throughout a molecule whose
+    text is empty); ``host()`` -> ``(list of str, length, status, atom_pos)`` with one copy and one synchronisation."""
+
+    def __init__(self, buf: torch.Tensor, G: int, N: int, max_len: int):
+        super().__init__(buf, G, N, max_len)
+        self.N, self.max_len = N, max_len
+
+    @staticmethod
+    @functools.lru_cache(maxsize=64)
+    def layout(G: int, N: int, max_len: int) -> dict:
+        return _pack(("text", "uint8", (G, max_len)), ("length", "int32", (G,)), ("status", "int32", (G,)),
+                     ("atom_pos", "int32", (G, N)))
+
+    @staticmethod
+    def _host_result(a):
+        text, length, status = a["text"], a["length"], a["status"]
+        rows = text.tobytes()
+        width = text.shape[1]
+        strings = ["" if int(status[g]) & NO_STRING_BITS else rows[g * width:g * width + int(length[g])].decode("ascii")
+                   for g in range(text.shape[0])]
+        return strings, length, status, a["atom_pos"]
+
+
+def symbol_table(atom_types: Sequence[str]) -> np.ndarray:
+    """The element symbols as the [A, 2] byte table ``gi_mol_smiles`` reads (the second byte 0 for a one-letter
+    symbol); ``ValueError`` for a symbol that is not one or two ASCII letters."""
+    sym = np.zeros((len(atom_types), 2), np.uint8)
+    for a, s in enumerate(atom_types):
+        if not (isinstance(s, str) and 1 <= len(s) <= 2 and s.isascii() and s.isalpha()):
+            raise ValueError(f"smiles: the element symbol {s!r} is not one or two ASCII letters")
+        sym[a, :len(s)] = np.frombuffer(s.encode("ascii"), np.uint8)
+    return sym
+
+
+def _smiles_tables(what: str, rules: ValenceRules):
+    """-> (symbols [A, 2] uint8, charges [C] int8) on the rules' device, uploaded once per rules."""
+    tables = rules.__dict__.get("_smiles")
+    if tables is None:
+        if rules.device is None:
+            raise RuntimeError(f"{what}: the rules were built with device=None and hold no device tables (no CPU "
+                               "fallback)")
+        tables = rules.__dict__["_smiles"] = (torch.from_numpy(symbol_table(rules.atom_types)).to(rules.device),
+                                              torch.tensor(rules.formal_charge, dtype=torch.int8, device=rules.device))
+    return tables
+
+
+_canonical = canonical                                      # ``smiles`` has a keyword of that name
+
+
+def smiles(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Optional[torch.Tensor], rules: ValenceRules, *,
+           rank: Optional[torch.Tensor] = None, canonical: bool = False, hydrogens: Optional[str] = None,
+           max_len: Optional[int] = None) -> MoleculeStrings:
+    """Every molecule as a SMILES string — what the reference's ``util.write_graphs_to_smi`` (util.py:520-585) gets from
+    one ``RWMol``, one ``SanitizeMol`` and one ``MolToSmiles`` per molecule on the host — for all G molecules in one
+    launch (``gi_mol_smiles``), with no RDKit and no read-back; inputs as ``validity``.
+
+    **THE STRING IS A FAITHFUL SPELLING OF THE LABELLED GRAPH, NOT RDKit's CANONICAL SMILES**: an OpenSMILES subset with
+    no aromaticity (nothing is perceived, nothing is kekulised: a bond of order 1.5 gives ``SMI_AROMATIC`` and no
+    string, so that the caller can route such molecules to RDKit), no stereo marks (the reference's ``graph_to_mol``
+    sets no chiral tag either, only the ``_CIPCode`` property, so its strings carry none), and hydrogen counts that are
+    ``rules``' fill or the stored ones.  Any OpenSMILES reader gets the labelled graph back (tests/smiles_model.py
+    holds one, and the Python specification of the writer; include/graphinvent_amd.h has the grammar).
+
+    ``rank`` [G, N] int32 on the device: the traversal key of every atom (ties go to the lower index; without it the key
+    is the input index).  Components come in ascending order of their lowest-key atom, each walked depth-first from it
+    with the neighbours in ascending key.  ``canonical=True`` calls ``canonical`` and passes its ``rank`` (one launch
+    more, no read-back; giving both is a ``ValueError``): then two molecules get the same string exactly when
+    ``canonical`` gives them the same form — that includes its documented incompleteness on graphs whose refinement
+    cells are not orbits — whereas the reference compares RDKit's canonical SMILES.
+
+    ``hydrogens``: ``"fill"`` — ``validity``'s ``h = v* - x``, 0 for an atom over its valence — or ``"stored"`` — the
+    count in the implicit-H segment, the reference's ``_TotalNumHs`` (needs ``rules.imp_H``); default ``"stored"`` when
+    the rules have such a segment.  An atom is written bare (``C``) when its symbol is in the organic subset, it has
+    no charge and its count equals the OpenSMILES implicit count, else in brackets (``[NH4+]``).  The symbols are
+    ``rules.atom_types``: one or two ASCII letters each, else ``ValueError``.
+
+    ``max_len`` (a multiple of 16, at most ``lib.SMI_MAX_LEN``) defaults to ``default_smiles_len(N)``: enough for
+    molecules but not a bound, a dense graph needs more and gets ``SMI_TRUNCATED`` with the need in ``length``.
+
+    Result (``MoleculeStrings``, views of one device buffer): ``text`` [G, max_len] uint8, ``length``, ``status`` [G]
+    int32 (``SMILES_STATUS_MESSAGES``: the malformed bits of ``validity``, ``SMI_EMPTY``, ``SMI_SELF_LOOP``,
+    ``SMI_AROMATIC``, ``SMI_RING_LIMIT`` — empty text, length 0 — ``SMI_TRUNCATED`` — empty text, length = the need —
+    and the informational ``SMI_OVER`` and ``SMI_FRAGMENTS``), ``atom_pos`` [G, N] int32.  ``.host()`` is one copy and
+    one synchronisation.  G = 0 is answered without a launch."""
+    what = "smiles"
+    if not isinstance(rules, ValenceRules):
+        raise TypeError(f"{what}: rules must be a ValenceRules, got {type(rules).__name__}")
+    if canonical and rank is not None:
+        raise ValueError(f"{what}: give rank or canonical=True, not both")
+    A, Cn, H = rules.groups
+    if hydrogens is None:
+        hydrogens = "stored" if H else "fill"
+    if hydrogens not in ("fill", "stored"):
+        raise ValueError(f"{what}: hydrogens must be 'fill' or 'stored', got {hydrogens!r}")
+    if hydrogens == "stored" and not H:
+        raise ValueError(f"{what}: hydrogens='stored' needs rules with an implicit-H segment (imp_H)")
+    symbol_table(rules.atom_types)                           # raises for a symbol that cannot be written
+    if not all(-127 <= c <= 127 for c in rules.formal_charge):
+        raise ValueError(f"{what}: formal charges {rules.formal_charge} must lie in [-127, 127]")
+    G, N, Fn, Fe, dtype, n_nodes, nn_bytes, _ = _check_inputs(what, nodes, edges, n_nodes, None, False)
+    max_len = default_smiles_len(N) if max_len is None else max_len
+    if (not isinstance(max_len, (int, np.integer)) or isinstance(max_len, bool) or max_len % 16
+            or not 16 <= max_len <= L.SMI_MAX_LEN):
+        raise ValueError(f"{what}: max_len must be a multiple of 16 in [16, {L.SMI_MAX_LEN}], got {max_len!r}")
+    max_len = int(max_len)
+    dev = nodes.device
+    if A + Cn + H > Fn:
+        raise ValueError(f"{what}: the rules' segments {rules.groups} do not fit node rows of Fn = {Fn}")
+    symbols, charges = _smiles_tables(what, rules)
+    order2 = rules.order2(Fe)
+    if order2.device != dev:
+        raise ValueError(f"{what}: the molecules are on {dev}, the rules' tables on {order2.device}")
+    if rank is not None:
+        if not isinstance(rank, torch.Tensor) or not rank.is_cuda or rank.device != dev:
+            raise RuntimeError(f"{what}: rank must be a CUDA tensor on {dev} (no CPU fallback)")
+        if tuple(rank.shape) != (G, N) or rank.dtype != torch.int32 or not rank.is_contiguous():
+            raise ValueError(f"{what}: rank must be a contiguous int32 tensor of shape ({G}, {N}), got {rank.dtype} "
+                             f"{tuple(rank.shape)}")
+    elif canonical:
+        rank = _canonical(nodes, edges, n_nodes).rank
+    res = MoleculeStrings.empty(dev, G, N, max_len)
+    if G > 0:
+        out = res._ptrs()
+        with torch.cuda.device(dev):
+            L.check(L.load().gi_mol_smiles(
+                G, N, Fn, Fe, nodes.data_ptr(), edges.data_ptr(), dtype,
+                None if n_nodes is None else n_nodes.data_ptr(), nn_bytes, A, Cn, H, rules.allowed_mask.data_ptr(),
+                order2.data_ptr(), None if rules.h_values is None else rules.h_values.data_ptr(), charges.data_ptr(),
+                symbols.data_ptr(), int(hydrogens == "stored"), None if rank is None else rank.data_ptr(), max_len,
+                out["text"], out["length"], out["status"], out["atom_pos"],
+                torch.cuda.current_stream(dev).cuda_stream), "gi_mol_smiles")
+    return res
+
+
+def write_smi(path, strings, *, valid=None, placeholder: str = "[Xe]") -> int:
+    """Write a ``.smi`` file in the layout of the reference's shipped ones (``SmilesWriter``'s): the header row
+    ``SMILES Name``, then one ``<string> <row index>`` row per molecule.  ``strings``: ``smiles``' result (read back
+    here, with its one copy) or a sequence of str.  ``valid`` [G] (a tensor, e.g. ``validity(...).valid``, or a
+    sequence; non-zero = valid; default all): a molecule whose entry is 0, and one whose string is empty, is written as
+    ``placeholder`` — the reference's ``[Xe]`` line for a molecule that fails sanitisation (util.py:573-578).  Returns
+    the number of placeholder rows."""
+    rows = strings.host()[0] if isinstance(strings, MoleculeStrings) else list(strings)
+    if valid is None:
+        ok = [True] * len(rows)
+    else:
+        if isinstance(valid, torch.Tensor) and valid.is_cuda:
+            with _host_sync_allowed():                       # the file needs the values: one read-back
+                valid = valid.detach().cpu()
+        if isinstance(valid, torch.Tensor):
+            valid = valid.detach().numpy()
+        ok = [bool(v) for v in np.asarray(valid).reshape(-1)]
+        if len(ok) != len(rows):
+            raise ValueError(f"write_smi: {len(rows)} strings but {len(ok)} validity entries")
+    if not placeholder or any(ch.isspace() for ch in placeholder):
+        raise ValueError(f"write_smi: placeholder {placeholder!r} must be a non-empty string without blanks")
+    replaced = 0
+    with open(path, "w") as f:
+        f.write("SMILES Name\n")
+        for k, s in enumerate(rows):
+            if not s or not ok[k]:
+                s, replaced = placeholder, replaced + 1
+            f.write(f"{s} {k}\n")
+    return replaced

@@ -160,6 +160,9 @@ MOL_COUNTS, SEEN_FULL = 3, 1                            # GI_MOL_COUNTS, GI_SEEN
 VAL_DESC, VAL_COUNTS, VAL_SCRATCH = 6, 4, 4             # GI_VAL_DESC, GI_VAL_COUNTS, GI_VAL_SCRATCH
 FP_MIN_BITS, FP_MAX_BITS, FP_MAX_RADIUS = 64, 4096, 4   # GI_FP_* of gi_mol_fingerprint
 FP_TANIMOTO, FP_RBF, FP_LINEAR = 0, 1, 2                # GI_FP_* kinds of gi_fp_compare
+(SMI_EMPTY, SMI_SELF_LOOP, SMI_OVER, SMI_FRAGMENTS, SMI_AROMATIC, SMI_RING_LIMIT,
+ SMI_TRUNCATED) = 128, 256, 512, 1024, 2048, 8192, 16384  # GI_SMI_* of gi_mol_smiles
+SMI_MAX_LEN = 8192                                      # GI_SMI_MAX_LEN
 
 
 class RouteDims(C.Structure):
@@ -302,6 +305,8 @@ SIGNATURES = {
     "gi_mol_fingerprint": (ci, [ci, ci, ci, ci, vp, vp, ci, vp, ci, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp]),
     "gi_fp_compare": (ci, [ci, ci, ci, ci, vp, vp, vp, ci, C.c_double, C.c_double, C.c_double, C.c_double,
                            vp, vp, vp, vp, vp, vp, vp]),
+    "gi_mol_smiles": (ci, [ci, ci, ci, ci, vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, ci,
+                           vp, vp, vp, vp, vp]),
 }
 FUSE_GATES_V4, FUSE_DH_SCATTER, FUSE_TIER2_DSELU, FUSE_SLOTS = 1, 2, 4, 8  # GI_FUSE_*
 GLUE_READOUT_FWD, GLUE_READOUT_BWD, GLUE_LOSS_MEAN, GLUE_GRU_AGG = 1, 2, 4, 8  # GI_GLUE_*

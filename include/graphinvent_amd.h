@@ -1305,6 +1305,64 @@ int gi_fp_compare(int G, int S, int W_query, int W_set, const int* query, const 
                   int kind, double gamma, double intercept, double prob_a, double prob_b, int* nearest, int* common,
                   int* uni, float* max_sim, float* decision, float* proba, void* stream);
 
+/* Molecule strings (gi_smiles.hip): every molecule as a SMILES string, the product of the reference's
+ * write_graphs_to_smi (util.py:520-585; one RWMol, one SanitizeMol and one MolToSmiles per molecule on the host).  THE
+ * STRING IS A FAITHFUL SPELLING OF THE LABELLED GRAPH in an OpenSMILES subset, NOT RDKit's CANONICAL SMILES: no
+ * aromaticity perception or kekulisation, no stereo marks (the reference sets no chiral tag either: graph_to_mol keeps
+ * chirality only as the _CIPCode property), hydrogen counts from the caller's table or from the stored segment.
+ * tests/smiles_model.py is the Python specification, with an independent reader.
+ *
+ * gi_mol_smiles, one launch, one workgroup per molecule, no global atomics, nothing to clear before it.  nodes / edges
+ * / n_nodes / dtype, the node row's segments n_types | n_charges | n_imp_h, allowed and order2 as for gi_mol_valence.
+ * charges [n_charges] (int8, device): the formal charge of every entry; symbols [n_types, 2] (bytes, device): the
+ * element symbol, the second byte 0 for a one-letter symbol; h_values [n_imp_h] as for gi_mol_valence.  stored_h = 0:
+ * an atom's hydrogen count h is the fill of gi_mol_valence (v* - x, 0 for an atom over its valence); stored_h = 1
+ * (needs n_imp_h > 0): the count its implicit-H entry stands for.  rank [G, N] (int32, device; NULL: the input index):
+ * the traversal key of atom i is its place in the order by (rank[i], i), so any values are accepted; gi_mol_canon's
+ * rank makes the string canonical in gi_mol_canon's sense (its documented incompleteness included).
+ *
+ * The string.
+ *   atom token   bare symbol when the symbol is one of B C N O P S F Cl Br I, the charge is 0 and h equals the OpenSMILES
+ *                implicit count for the bond-order sum x = ceil(o2 / 2): v - x with v the smallest of the element's
+ *                normal valences >= x (B 3, C 4, N 3 5, O 2, P 3 5, S 2 4 6, halogens 1), 0 without one.  Otherwise
+ *                '[' symbol, 'H' if h >= 1, h if h >= 2, '+' or '-' and the magnitude if >= 2, ']'.  An atom of type
+ *                "H" is always "[H]" with its charge, never a count.  A token has at most 12 bytes.
+ *   bonds        a single bond is elided, a double bond is '=', a triple bond '#'.
+ *   order        components in ascending order of their lowest-key atom, joined by '.'; each is walked depth-first from
+ *                that atom, neighbours in ascending key: one that is unvisited when it is reached becomes a tree child,
+ *                one that is visited and is not the tree parent is a ring bond.  Atoms appear in pre-order.
+ *   at an atom   1 the token; 2 its ring closings in ascending pre-order index of the partner, each the bond symbol and
+ *                the number, which is free again at once; 3 its ring openings in the same order, each the smallest free
+ *                number >= 1 without a bond symbol; 4 its children in visiting order, every one but the last in
+ *                parentheses, the bond symbol directly in front of the child's token, inside the parenthesis.
+ *   numbers      1-9 one digit, 10-99 "%nn".  Kekule benzene in ring order is "C1=CC=CC=C1".
+ *
+ * text [G, max_len] bytes (16-byte aligned), zero padded; max_len a multiple of 16 in [16, GI_SMI_MAX_LEN] (beyond:
+ * GI_ELIMIT; the limit keeps the string, the ring tokens and the adjacency rows of N = 128, Fe = 8 inside 64 KB of
+ * LDS).  No bound short of N^2 bytes holds for every legal input — a clique of n atoms carries (n - 1)(n - 2) / 2 ring
+ * bonds — so 12 N + 4 is a default, not a bound: it holds a molecule whose every atom has an 8-byte bracket token, a bond
+ * symbol, a branch of its own and a ring digit.  length [G]: the bytes of the string.  atom_pos [G, N] int32: the byte offset of every
+ * atom's token, -1 for i >= n and throughout a molecule with an empty text.  status [G]: the GI_MOL_* bits of a
+ * malformed molecule exactly as gi_mol_valence sets them (GI_MOL_MULTI_BOND included) and the bits below, the first
+ * five with the values and meanings of GI_VAL_EMPTY .. GI_VAL_AROMATIC.  A malformed molecule, GI_SMI_EMPTY,
+ * _SELF_LOOP, _AROMATIC and _RING_LIMIT give an empty text, length 0 and atom_pos -1; GI_SMI_TRUNCATED gives an empty
+ * text and atom_pos -1 with length = the bytes needed, so that the caller can ask again; GI_SMI_OVER and
+ * GI_SMI_FRAGMENTS are informational, the string is written.  G = 0 returns 0 and touches nothing.  Every loop is
+ * bounded by N, Fe, the 32 bits of a word or 2 N + 1 (the walk) whatever the data holds. */
+#define GI_SMI_EMPTY 128            /* n == 0 */
+#define GI_SMI_SELF_LOOP 256        /* edges[i, i, t] is set */
+#define GI_SMI_OVER 512             /* some atom exceeds every allowed valence of its type and charge (informational) */
+#define GI_SMI_FRAGMENTS 1024       /* more than one component: the string has a '.' (informational) */
+#define GI_SMI_AROMATIC 2048        /* a bond of order 1.5 is present: nothing is kekulised, no string */
+#define GI_SMI_RING_LIMIT 8192      /* more than 99 ring bonds are open at once */
+#define GI_SMI_TRUNCATED 16384      /* the string needs more than max_len bytes; length holds the need */
+#define GI_SMI_MAX_LEN 8192
+int gi_mol_smiles(int G, int N, int Fn, int Fe, const void* nodes, const void* edges, int dtype,
+                  const void* n_nodes, int n_nodes_bytes, int n_types, int n_charges, int n_imp_h,
+                  const unsigned short* allowed, const signed char* order2, const signed char* h_values,
+                  const signed char* charges, const unsigned char* symbols, int stored_h, const int* rank,
+                  int max_len, unsigned char* text, int* length, int* status, int* atom_pos, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
