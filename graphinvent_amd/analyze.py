@@ -38,6 +38,11 @@ into the arguments of ``Chem.Atom`` / ``AddBond``.  Building ``rdkit.Chem.RWMol`
 file: the product of the reference's ``util.write_graphs_to_smi``.  The string is a faithful spelling of the labelled
 graph in an OpenSMILES subset — NOT RDKit's canonical SMILES: no aromaticity, no stereo, see ``smiles``.
 
+``pack_strings`` / ``read_smiles`` / ``read_smi`` go the other way (``gi_smiles_read``): SMILES strings and ``.smi``
+files into the int8 molecules that ``routes.RouteLoader``, ``SeedBank``, ``SeenSet`` and ``FingerprintSet`` take — the
+reference's RDKit preprocessing on the writer's subset: no aromatic input, no stereo, atoms in string order, see
+``read_smiles``.
+
 Counts are summed as integers on the device and converted once (the exact integer as fp32, then one fp32 division):
 bit for bit the reference's values while every count is below 2**24.  Beyond that the reference's own fp32
 accumulation (``hist[i] += 1``) stops being exact, e.g. it stays at 16777216 for ever; the counts here stay exact
@@ -1343,3 +1348,225 @@ def write_smi(path, strings, *, valid=None, placeholder: str = "[Xe]") -> int:
                 s, replaced = placeholder, replaced + 1
             f.write(f"{s} {k}\n")
     return replaced
+
+
+# ---- molecule reading ------------------------------------------------------------------------------------------------
+#: status bits of ``read_smiles`` (``lib.SMR_*``); every bit of ``lib.SMR_ERROR`` leaves the all-zero molecule
+READ_STATUS_MESSAGES = {
+    L.SMR_MULTI_BOND: "the same pair of atoms is bonded twice",
+    L.SMR_EMPTY: "the string is empty",
+    L.SMR_SELF_LOOP: "a ring closes on the atom that opened it",
+    L.SMR_OVER: "an atom has more bonds than any allowed valence of its element and charge (informational: the "
+                "molecule is written)",
+    L.SMR_FRAGMENTS: "more than one connected component (informational)",
+    L.SMR_AROMATIC: "a lowercase (aromatic) atom or ':': nothing is kekulised, no molecule (route the string to RDKit)",
+    L.SMR_TOO_MANY: "more atoms than max_n_nodes: no molecule, n_nodes holds the need",
+    L.SMR_SYNTAX: "not a string of the grammar (an unclosed bracket or branch, a dangling bond, a bond or ring digit "
+                  "without an atom, '..', an unknown byte, '%' without two digits, bare H, a length outside the row)",
+    L.SMR_RING_OPEN: "a ring number is left open",
+    L.SMR_RING_ORDER: "the two ends of a ring bond state different bond orders",
+    L.SMR_ELEMENT: "an element that is not in the rules' atom types",
+    L.SMR_CHARGE: "a formal charge that is not in the rules' charges",
+    L.SMR_HCOUNT: "a hydrogen count that is not in the rules' implicit-H values",
+    L.SMR_BOND_ORDER: "a bond order that the rules' bond types do not hold",
+    L.SMR_STEREO: "a stereo mark ('@', '/', '\\'): no molecule (stereo='drop' skips the marks; or route the string to "
+                  "RDKit)",
+    L.SMR_STEREO_DROPPED: "stereo marks were skipped (informational)",
+    L.SMR_UNSUPPORTED: "an isotope, an atom class, '++' / '--', '$' or the wildcard",
+}
+
+
+def describe_read_status(bits: int) -> str:
+    return "; ".join(msg for bit, msg in READ_STATUS_MESSAGES.items() if bits & bit) or "read"
+
+
+def pack_strings(strings, max_len: Optional[int] = None, device="cuda"):
+    """Python strings (or ``bytes``) as the byte rows ``read_smiles`` takes — ``smiles``' own layout — built in ONE host
+    buffer and uploaded with ONE copy: ``(text [G, max_len] uint8 zero padded, length [G] int32)``, views of one device
+    buffer.  ``max_len`` (a multiple of 16, at most ``lib.SMI_MAX_LEN``) defaults to the longest string rounded up; a
+    string that is longer, or not ASCII, is a ``ValueError`` that names its row."""
+    raw = []
+    for g, s in enumerate(strings):
+        if isinstance(s, str):
+            try:
+                s = s.encode("ascii")
+            except UnicodeEncodeError:
+                raise ValueError(f"pack_strings: string {g} ({s!r}) is not ASCII") from None
+        elif not isinstance(s, (bytes, bytearray)):
+            raise TypeError(f"pack_strings: string {g} is a {type(s).__name__}, expected str or bytes")
+        raw.append(bytes(s))
+    need = max([len(r) for r in raw] + [1])
+    if max_len is None:
+        max_len = (need + 15) // 16 * 16
+    if (not isinstance(max_len, (int, np.integer)) or isinstance(max_len, bool) or max_len % 16
+            or not 16 <= max_len <= L.SMI_MAX_LEN):
+        raise ValueError(f"pack_strings: max_len must be a multiple of 16 in [16, {L.SMI_MAX_LEN}], got {max_len!r} "
+                         f"(the longest string has {need} bytes)")
+    max_len, G = int(max_len), len(raw)
+    if need > max_len:
+        g = next(g for g, r in enumerate(raw) if len(r) > max_len)
+        raise ValueError(f"pack_strings: string {g} has {len(raw[g])} bytes, max_len is {max_len}")
+    host = np.zeros(G * max_len + 4 * G, np.uint8)
+    host[:G * max_len] = np.frombuffer(b"".join([r.ljust(max_len, b"\0") for r in raw]), np.uint8)
+    host[G * max_len:].view(np.int32)[:] = np.fromiter(map(len, raw), np.int32, count=G)
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"pack_strings needs a CUDA (ROCm) device, got {dev}: the MI355X HIP path has no CPU fallback")
+    with _host_sync_allowed():                               # (set-up: a host buffer's upload may synchronise)
+        buf = torch.from_numpy(host).to(dev)
+    if G == 0:                                               # (an empty slice has no stride to view as int32)
+        return buf.view(0, max_len), torch.empty(0, dtype=torch.int32, device=dev)
+    return buf[:G * max_len].view(G, max_len), buf[G * max_len:].view(torch.int32)
+
+
+class ReadMolecules(_ResultBuffer):
+    """What ``read_smiles`` read, on the device: ``nodes`` [G, N, Fn] / ``edges`` [G, N, N, Fe] int8 (what
+    ``routes.RouteLoader``, ``SeedBank``, ``SeenSet.add``, ``FingerprintSet.from_molecules`` and
+    ``likelihood.molecule_log_likelihood`` take), ``n_nodes`` / ``status`` [G] int32, ``atom_pos`` [G, N] int32 (the byte
+    offset of every atom's token, -1 past n); ``host()`` -> ``(nodes, edges, n_nodes, status, atom_pos)`` with one copy
+    and one synchronisation."""
+
+    def __init__(self, buf: torch.Tensor, G: int, N: int, Fn: int, Fe: int):
+        super().__init__(buf, G, N, Fn, Fe)
+        self.N, self.Fn, self.Fe = N, Fn, Fe
+
+    @staticmethod
+    @functools.lru_cache(maxsize=64)
+    def layout(G: int, N: int, Fn: int, Fe: int) -> dict:
+        return _pack(("atom_pos", "int32", (G, N)), ("n_nodes", "int32", (G,)), ("status", "int32", (G,)),
+                     ("_pad", "uint8", (-4 * G * (N + 2) % 16,)),                # the molecule rows start a 16-byte piece
+                     ("nodes", "int8", (G, N, Fn)), ("edges", "int8", (G, N, N, Fe)))
+
+    @staticmethod
+    def _host_result(a):
+        return a["nodes"], a["edges"], a["n_nodes"], a["status"], a["atom_pos"]
+
+
+def read_smiles(strings, rules: ValenceRules, max_n_nodes: int, *, length: Optional[torch.Tensor] = None,
+                n_chirality: int = 0, none_chirality: int = 0, stereo: str = "error",
+                n_bond_types: Optional[int] = None) -> ReadMolecules:
+    """SMILES strings into int8 molecules — what the reference's preprocessing gets from one ``MolFromSmiles`` and one
+    graph construction per molecule on the host — for all G strings in one launch (``gi_smiles_read``), with no RDKit
+    and no read-back.  The exact inverse of ``smiles`` on what ``smiles`` writes: ``read_smiles(smiles(m))`` is ``m``
+    with its atoms in the order of the string (``argsort(atom_pos)``), byte for byte.
+
+    **WHAT IT IS NOT**: no aromatic input (``c1ccccc1``: nothing is kekulised) and no stereo (``@``, ``/``, ``\\``).
+    Such a string gets ``SMR_AROMATIC`` / ``SMR_STEREO`` and no molecule, so that the caller can route it to RDKit;
+    ``stereo="drop"`` skips the marks instead (``SMR_STEREO_DROPPED``).  Atoms are numbered IN STRING ORDER, which is
+    not the order of the reference's preprocessing: train with ``routes.RouteLoader(reorder=...)``.  The grammar is in
+    include/graphinvent_amd.h at ``gi_smiles_read``; tests/smiles_read_model.py is the Python specification.
+
+    ``strings``: a sequence of ``str`` (packed by ``pack_strings``: one host buffer, one copy), ``smiles``' result, or a
+    [G, max_len] uint8 tensor on the device (16-byte aligned, max_len a multiple of 16) with ``length`` [G] int32 or
+    without (a string then ends at its first zero byte).  A node row is ``rules``' segments type | charge | implicit H,
+    then ``n_chirality`` entries of which ``none_chirality`` is set; a bare atom's hydrogens are the OpenSMILES implicit
+    count, a bracket atom's the stated ones, stored only when the rules have an implicit-H segment.  ``n_bond_types``:
+    Fe, default the rules' bond orders or 3.
+
+    Result (``ReadMolecules``, views of one device buffer): ``nodes``, ``edges``, ``n_nodes``, ``status``
+    (``READ_STATUS_MESSAGES``; any bit of ``lib.SMR_ERROR`` leaves the all-zero molecule, which the rest of the library
+    treats as empty, and ``SMR_TOO_MANY`` leaves the atoms needed in ``n_nodes``), ``atom_pos``.  G = 0 is answered
+    without a launch."""
+    what = "read_smiles"
+    if not isinstance(rules, ValenceRules):
+        raise TypeError(f"{what}: rules must be a ValenceRules, got {type(rules).__name__}")
+    if stereo not in ("error", "drop"):
+        raise ValueError(f"{what}: stereo must be 'error' or 'drop', got {stereo!r}")
+    A, Cn, H = rules.groups
+    for name, v, lo in (("max_n_nodes", max_n_nodes, 1), ("n_chirality", n_chirality, 0),
+                        ("none_chirality", none_chirality, 0)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < lo:
+            raise ValueError(f"{what}: {name} must be an integer >= {lo}, got {v!r}")
+    N, Fn = int(max_n_nodes), A + Cn + H + int(n_chirality)
+    if n_chirality and none_chirality >= n_chirality:
+        raise ValueError(f"{what}: none_chirality {none_chirality} is outside the {n_chirality} chirality entries")
+    Fe = (len(rules.bond_orders) if rules.bond_orders is not None else 3) if n_bond_types is None else int(n_bond_types)
+    if N > L.GI_MAX_NODES or not 1 <= Fe <= L.GI_MAX_GROUPS or Fn > L.ANALYZE_MAX_FN:
+        raise ValueError(f"{what}: needs max_n_nodes <= {L.GI_MAX_NODES}, 1 <= Fe <= {L.GI_MAX_GROUPS}, Fn <= "
+                         f"{L.ANALYZE_MAX_FN}; got N {N}, Fn {Fn}, Fe {Fe}")
+    symbol_table(rules.atom_types)                           # raises for a symbol that cannot be spelt
+    if not all(-127 <= c <= 127 for c in rules.formal_charge):
+        raise ValueError(f"{what}: formal charges {rules.formal_charge} must lie in [-127, 127]")
+    if rules.device is None:
+        raise RuntimeError(f"{what}: the rules were built with device=None and hold no device tables (no CPU fallback)")
+    if isinstance(strings, MoleculeStrings):
+        if length is not None:
+            raise ValueError(f"{what}: smiles' result brings its own length")
+        text, length = strings.text, strings.length
+    elif isinstance(strings, torch.Tensor):
+        text = strings
+    else:
+        if length is not None:
+            raise ValueError(f"{what}: length goes with a byte tensor, a list of strings brings its own")
+        text, length = pack_strings(strings, device=rules.device)
+    if not text.is_cuda:
+        raise RuntimeError(f"{what} needs CUDA (ROCm) tensors (the text is on {text.device}): the MI355X HIP path has no "
+                           "CPU fallback")
+    if text.dim() != 2 or text.dtype != torch.uint8 or not text.is_contiguous():
+        raise ValueError(f"{what}: the text must be a contiguous [G, max_len] uint8 tensor, got {text.dtype} "
+                         f"{tuple(text.shape)}")
+    G, max_len = text.shape
+    if max_len % 16 or not 16 <= max_len <= L.SMI_MAX_LEN or text.data_ptr() % 16:
+        raise ValueError(f"{what}: max_len must be a multiple of 16 in [16, {L.SMI_MAX_LEN}] and the text 16-byte "
+                         f"aligned, got max_len {max_len}")
+    dev = text.device
+    if length is not None:
+        if not isinstance(length, torch.Tensor) or not length.is_cuda or length.device != dev:
+            raise RuntimeError(f"{what}: length must be a CUDA tensor on {dev} (no CPU fallback)")
+        if tuple(length.shape) != (G,) or length.dtype != torch.int32 or not length.is_contiguous():
+            raise ValueError(f"{what}: length must be a contiguous int32 tensor of shape ({G},), got {length.dtype} "
+                             f"{tuple(length.shape)}")
+    symbols, charges = _smiles_tables(what, rules)
+    order2 = rules.order2(Fe)
+    if order2.device != dev:
+        raise ValueError(f"{what}: the text is on {dev}, the rules' tables on {order2.device}")
+    res = ReadMolecules.empty(dev, G, N, Fn, Fe)
+    if G > 0:
+        out = res._ptrs()
+        with torch.cuda.device(dev):
+            L.check(L.load().gi_smiles_read(
+                G, N, Fn, Fe, text.data_ptr(), None if length is None else length.data_ptr(), max_len, A, Cn, H,
+                rules.allowed_mask.data_ptr(), order2.data_ptr(),
+                None if rules.h_values is None else rules.h_values.data_ptr(), charges.data_ptr(), symbols.data_ptr(),
+                int(none_chirality), int(stereo == "drop"), out["nodes"], out["edges"], out["n_nodes"], out["status"],
+                out["atom_pos"], torch.cuda.current_stream(dev).cuda_stream), "gi_smiles_read")
+    return res
+
+
+class SmiMolecules:
+    """What ``read_smi`` read: ``nodes`` [G, N, Fn] / ``edges`` [G, N, N, Fe] int8, ``n_nodes`` / ``status`` [G] int32
+    on the device, row for row the file's lines, and ``names`` (the second column, ``""`` without one) on the host."""
+
+    def __init__(self, nodes, edges, n_nodes, status, names):
+        self.nodes, self.edges, self.n_nodes, self.status, self.names = nodes, edges, n_nodes, status, names
+
+    def __len__(self):
+        return len(self.names)
+
+
+def read_smi(path, rules: ValenceRules, max_n_nodes: int, *, batch: int = 8192, **kw) -> SmiMolecules:
+    """The inverse of ``write_smi``: a ``.smi`` file into int8 molecules on the device, ``batch`` lines per
+    ``read_smiles`` launch (``**kw`` goes to it), nothing read back.  A first line whose first column is ``SMILES`` is
+    the header and is skipped; of every other line the first blank-separated column is the string and the second the
+    name.  NO LINE IS LEFT OUT: a string with an error bit — ``write_smi``'s ``[Xe]`` placeholder under rules without
+    Xe, an aromatic string, an empty line — stays in its row as the all-zero molecule with its ``status``; it is the
+    caller who masks (``status & lib.SMR_ERROR``) or routes such rows to RDKit."""
+    if not isinstance(batch, (int, np.integer)) or isinstance(batch, bool) or batch < 1:
+        raise ValueError(f"read_smi: batch must be a positive integer, got {batch!r}")
+    with open(path, "rb") as f:
+        lines = f.read().split(b"\n")
+    if lines and lines[-1] == b"":
+        lines.pop()                                          # the file ends with a newline, not with an empty line
+    cols = [line.split() for line in lines]
+    if cols and cols[0] and cols[0][0] == b"SMILES":
+        cols = cols[1:]
+    strings = [c[0] if c else b"" for c in cols]
+    names = [c[1].decode("utf-8", "replace") if len(c) > 1 else "" for c in cols]
+    parts = [read_smiles(strings[k:k + batch], rules, max_n_nodes, **kw) for k in range(0, len(strings), batch)]
+    if not parts:
+        parts = [read_smiles([], rules, max_n_nodes, **kw)]
+    if len(parts) == 1:
+        one = parts[0]
+        return SmiMolecules(one.nodes, one.edges, one.n_nodes, one.status, names)
+    return SmiMolecules(*(torch.cat([getattr(p, name) for p in parts]) for name in ("nodes", "edges", "n_nodes", "status")),
+                        names)

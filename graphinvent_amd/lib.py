@@ -163,6 +163,13 @@ FP_TANIMOTO, FP_RBF, FP_LINEAR = 0, 1, 2                # GI_FP_* kinds of gi_fp
 (SMI_EMPTY, SMI_SELF_LOOP, SMI_OVER, SMI_FRAGMENTS, SMI_AROMATIC, SMI_RING_LIMIT,
  SMI_TRUNCATED) = 128, 256, 512, 1024, 2048, 8192, 16384  # GI_SMI_* of gi_mol_smiles
 SMI_MAX_LEN = 8192                                      # GI_SMI_MAX_LEN
+(SMR_MULTI_BOND, SMR_EMPTY, SMR_SELF_LOOP, SMR_OVER, SMR_FRAGMENTS, SMR_AROMATIC,
+ SMR_TOO_MANY) = 16, 128, 256, 512, 1024, 2048, 16384   # GI_SMR_* of gi_smiles_read: the values of their GI_SMI_* namesakes
+(SMR_SYNTAX, SMR_RING_OPEN, SMR_RING_ORDER, SMR_ELEMENT, SMR_CHARGE, SMR_HCOUNT, SMR_BOND_ORDER, SMR_STEREO,
+ SMR_STEREO_DROPPED, SMR_UNSUPPORTED) = (1 << k for k in range(16, 26))
+SMR_ERROR = (SMR_MULTI_BOND | SMR_EMPTY | SMR_SELF_LOOP | SMR_AROMATIC | SMR_TOO_MANY | SMR_SYNTAX | SMR_RING_OPEN |
+             SMR_RING_ORDER | SMR_ELEMENT | SMR_CHARGE | SMR_HCOUNT | SMR_BOND_ORDER | SMR_STEREO |
+             SMR_UNSUPPORTED)                           # GI_SMR_ERROR: the bits that leave no molecule
 
 
 class RouteDims(C.Structure):
@@ -307,6 +314,8 @@ SIGNATURES = {
                            vp, vp, vp, vp, vp, vp, vp]),
     "gi_mol_smiles": (ci, [ci, ci, ci, ci, vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, ci,
                            vp, vp, vp, vp, vp]),
+    "gi_smiles_read": (ci, [ci, ci, ci, ci, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp,
+                            vp]),
 }
 FUSE_GATES_V4, FUSE_DH_SCATTER, FUSE_TIER2_DSELU, FUSE_SLOTS = 1, 2, 4, 8  # GI_FUSE_*
 GLUE_READOUT_FWD, GLUE_READOUT_BWD, GLUE_LOSS_MEAN, GLUE_GRU_AGG = 1, 2, 4, 8  # GI_GLUE_*

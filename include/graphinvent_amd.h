@@ -1363,6 +1363,72 @@ int gi_mol_smiles(int G, int N, int Fn, int Fe, const void* nodes, const void* e
                   const signed char* charges, const unsigned char* symbols, int stored_h, const int* rank,
                   int max_len, unsigned char* text, int* length, int* status, int* atom_pos, void* stream);
 
+/* Molecule reading (gi_smiles_read.hip): SMILES strings into molecules, the inverse of gi_mol_smiles ON THE WRITER'S
+ * SUBSET of OpenSMILES — what the reference's preprocessing gets from one MolFromSmiles and one graph construction per
+ * molecule on the host.  NOT RDKit: NO AROMATIC INPUT (nothing is kekulised) AND NO STEREO; such a string gets a status
+ * bit and no molecule, so that the caller can route it to RDKit.  Atoms are numbered IN STRING ORDER, which is not the
+ * order of the reference's preprocessing.  tests/smiles_read_model.py is the Python specification, stage by stage.
+ *
+ * gi_smiles_read, one launch, one workgroup per string, integers only, no global atomics, no scratch, nothing to clear
+ * before it.  text [G, max_len] bytes (16-byte aligned; gi_mol_smiles' own layout), max_len a multiple of 16 in
+ * [16, GI_SMI_MAX_LEN] (beyond: GI_ELIMIT); length [G] int32, or NULL: the string ends at its first zero byte (at max_len
+ * without one).  A length outside [0, max_len] is GI_SMR_SYNTAX.  The node row's segments n_types | n_charges | n_imp_h
+ * and the device tables symbols [n_types, 2], charges [n_charges], h_values [n_imp_h], order2 [Fe] and allowed as for
+ * gi_mol_smiles.  none_chirality: where n_types + n_charges + n_imp_h < Fn, the entry set inside the rest of every
+ * atom's row (0 <= none_chirality < the rest, GI_EINVAL otherwise; the reference's chirality list puts 'None' first).
+ * drop_stereo 0 or 1.
+ *
+ * The grammar: what gi_mol_smiles writes, plus what OpenSMILES lets other writers say about the same graphs.
+ *   bracket atom '[' symbol, 'H' and a count, '+' or '-' and a magnitude ']': the symbol a capital and at most one small
+ *                letter; 'H' alone counts 1, a sign alone 1; counts saturate at 1000.  "[H]" is an atom of type "H".
+ *   bare atom    B C N O P S F Cl Br I (bare H is GI_SMR_SYNTAX).
+ *   bonds        '-' '=' '#' in front of an atom or a ring number; none: a single bond.
+ *   branches     '(' behind an atom, nested up to 128 deep; "((" and "()" are GI_SMR_SYNTAX.
+ *   rings        a digit or "%nn" behind an atom opens a ring number or closes the open one; a bond symbol may stand on
+ *                either end and must agree if it stands on both; a closed number may be used again.
+ *   '.'          between components.
+ * Hydrogens: a bare atom has the OpenSMILES implicit count for its bond-order sum x (v - x with v the smallest normal
+ * valence >= x of B 3, C 4, N 3 5, O 2, P 3 5, S 2 4 6, halogens 1; 0 without one: the table gi_mol_smiles calls an atom
+ * bare by), a bracket atom the count it states.  With n_imp_h > 0 the count is stored as its entry of the implicit-H
+ * segment; with n_imp_h = 0 nothing is stored.
+ *
+ * nodes [G, N, Fn] / edges [G, N, N, Fe] int8 (any alignment; edges symmetric, one-hot per bonded pair), n_nodes [G],
+ * status [G], atom_pos [G, N] int32 (the byte offset of every atom's token, -1 for i >= n: gi_mol_smiles' output).
+ * Every byte of every output is written, the node and edge rows in 16-byte stores between the ragged ends of their
+ * address range.  A string with any bit of GI_SMR_ERROR gives the all-zero molecule — what the rest of the library
+ * treats as empty — with n_nodes 0 and atom_pos -1; GI_SMR_TOO_MANY alone keeps n_nodes = the atoms the string needs,
+ * so that the caller can ask again.  The bits are set in stages (bytes; atom tokens; the walk over the other tokens,
+ * which ends at its first error; hydrogens) and a stage runs only while no error bit is set, GI_SMR_TOO_MANY skipping
+ * all but the first: tests/smiles_read_model.py has the order.  Limits N <= GI_MAX_NODES, Fe <= GI_MAX_GROUPS (GI_EINVAL),
+ * Fn <= GI_ANALYZE_MAX_FN (GI_ELIMIT).  G = 0 returns 0 and touches nothing.  Every loop is bounded by max_len, N, Fe,
+ * the table widths or the 64 bits of a word whatever the bytes hold. */
+#define GI_SMR_MULTI_BOND 16        /* the same pair bonded twice ("C12CC12"): GI_MOL_MULTI_BOND */
+#define GI_SMR_EMPTY 128            /* the string is empty: GI_SMI_EMPTY */
+#define GI_SMR_SELF_LOOP 256        /* a ring closes on the atom that opened it ("C11"): GI_SMI_SELF_LOOP */
+#define GI_SMR_OVER 512             /* some atom exceeds every allowed valence of its type and charge (informational) */
+#define GI_SMR_FRAGMENTS 1024       /* more than one component (informational) */
+#define GI_SMR_AROMATIC 2048        /* a lowercase atom or ':': nothing is kekulised, no molecule */
+#define GI_SMR_TOO_MANY 16384       /* more than N atoms; n_nodes holds the need (as GI_SMI_TRUNCATED's length does) */
+#define GI_SMR_SYNTAX 65536         /* an unclosed bracket or branch, a dangling bond, a bond or ring digit without an atom
+                                       to its left, "..", an unknown byte, '%' without two digits, bare H, a bad length */
+#define GI_SMR_RING_OPEN 131072     /* a ring number is still open at the end */
+#define GI_SMR_RING_ORDER 262144    /* the two ends of a ring bond state different orders */
+#define GI_SMR_ELEMENT 524288       /* a symbol that is not in symbols */
+#define GI_SMR_CHARGE 1048576       /* a charge that is not in charges */
+#define GI_SMR_HCOUNT 2097152       /* a hydrogen count that is not in h_values (n_imp_h > 0 only) */
+#define GI_SMR_BOND_ORDER 4194304   /* a bond order that is not in order2 */
+#define GI_SMR_STEREO 8388608       /* '@' '/' '\' with drop_stereo = 0 */
+#define GI_SMR_STEREO_DROPPED 16777216 /* the same with drop_stereo = 1: skipped, '/' '\' are single bonds (informational) */
+#define GI_SMR_UNSUPPORTED 33554432 /* an isotope, an atom class, "++" / "--", '$', the wildcard */
+#define GI_SMR_ERROR (GI_SMR_MULTI_BOND | GI_SMR_EMPTY | GI_SMR_SELF_LOOP | GI_SMR_AROMATIC | GI_SMR_TOO_MANY | \
+                      GI_SMR_SYNTAX | GI_SMR_RING_OPEN | GI_SMR_RING_ORDER | GI_SMR_ELEMENT | GI_SMR_CHARGE | \
+                      GI_SMR_HCOUNT | GI_SMR_BOND_ORDER | GI_SMR_STEREO | GI_SMR_UNSUPPORTED)
+int gi_smiles_read(int G, int N, int Fn, int Fe, const unsigned char* text, const int* length, int max_len,
+                   int n_types, int n_charges, int n_imp_h, const unsigned short* allowed, const signed char* order2,
+                   const signed char* h_values, const signed char* charges, const unsigned char* symbols,
+                   int none_chirality, int drop_stereo, signed char* nodes, signed char* edges, int* n_nodes,
+                   int* status, int* atom_pos, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
