@@ -40,7 +40,8 @@ graph in an OpenSMILES subset — NOT RDKit's canonical SMILES: no aromaticity, 
 
 ``pack_strings`` / ``read_smiles`` / ``read_smi`` go the other way (``gi_smiles_read``): SMILES strings and ``.smi``
 files into the int8 molecules that ``routes.RouteLoader``, ``SeedBank``, ``SeenSet`` and ``FingerprintSet`` take — the
-reference's RDKit preprocessing on the writer's subset: no aromatic input, no stereo, atoms in string order, see
+reference's RDKit preprocessing on the writer's subset: no stereo, atoms in string order, aromatic input only with
+``aromatic="kekulize"`` (``gi_smiles_read_arom``) and then kekulised by the library's own rule, not RDKit's, see
 ``read_smiles``.
 
 Counts are summed as integers on the device and converted once (the exact integer as fp32, then one fp32 division):
@@ -1376,8 +1377,17 @@ READ_STATUS_MESSAGES = {
 }
 
 
+#: the two bits ``read_smiles(..., aromatic="kekulize")`` adds (``lib.SMR_KEKULE`` is an error bit: ``lib.SMR_READ_ERROR``)
+KEKULE_STATUS_MESSAGES = {
+    L.SMR_KEKULE: "the aromatic atoms have no Kekule structure (no perfect matching of the atoms that need a double "
+                  "bond): no molecule",
+    L.SMR_KEKULIZED: "aromatic atoms were read and kekulised by the library's own rule (informational)",
+}
+
+
 def describe_read_status(bits: int) -> str:
-    return "; ".join(msg for bit, msg in READ_STATUS_MESSAGES.items() if bits & bit) or "read"
+    return "; ".join(msg for table in (READ_STATUS_MESSAGES, KEKULE_STATUS_MESSAGES) for bit, msg in table.items()
+                     if bits & bit) or "read"
 
 
 def pack_strings(strings, max_len: Optional[int] = None, device="cuda"):
@@ -1444,17 +1454,26 @@ class ReadMolecules(_ResultBuffer):
 
 def read_smiles(strings, rules: ValenceRules, max_n_nodes: int, *, length: Optional[torch.Tensor] = None,
                 n_chirality: int = 0, none_chirality: int = 0, stereo: str = "error",
-                n_bond_types: Optional[int] = None) -> ReadMolecules:
+                n_bond_types: Optional[int] = None, aromatic: str = "error") -> ReadMolecules:
     """SMILES strings into int8 molecules — what the reference's preprocessing gets from one ``MolFromSmiles`` and one
     graph construction per molecule on the host — for all G strings in one launch (``gi_smiles_read``), with no RDKit
     and no read-back.  The exact inverse of ``smiles`` on what ``smiles`` writes: ``read_smiles(smiles(m))`` is ``m``
     with its atoms in the order of the string (``argsort(atom_pos)``), byte for byte.
 
-    **WHAT IT IS NOT**: no aromatic input (``c1ccccc1``: nothing is kekulised) and no stereo (``@``, ``/``, ``\\``).
+    **WHAT IT IS NOT**: by default no aromatic input (``c1ccccc1``) and no stereo (``@``, ``/``, ``\\``).
     Such a string gets ``SMR_AROMATIC`` / ``SMR_STEREO`` and no molecule, so that the caller can route it to RDKit;
     ``stereo="drop"`` skips the marks instead (``SMR_STEREO_DROPPED``).  Atoms are numbered IN STRING ORDER, which is
     not the order of the reference's preprocessing: train with ``routes.RouteLoader(reorder=...)``.  The grammar is in
     include/graphinvent_amd.h at ``gi_smiles_read``; tests/smiles_read_model.py is the Python specification.
+
+    ``aromatic="kekulize"`` (``gi_smiles_read_arom``) reads aromatic atoms (``b c n o p s``, ``[nH]``, ``[se]`` ...) and
+    ``:`` and assigns single and double bonds to the aromatic-marked bonds inside the same launch: a perfect matching
+    of the atoms that need a double bond, chosen deterministically.  **IT IS NOT RDKit'S KEKULISATION**: no ring or
+    aromaticity perception and no canonical choice, so two strings of one compound can come out as two different Kekule
+    structures, which ``unique`` counts as two molecules.  A string without a Kekule structure gets ``SMR_KEKULE`` (in
+    ``lib.SMR_READ_ERROR``) and no molecule; one that had aromatic atoms and was read gets ``SMR_KEKULIZED``.  The rule
+    is written out at ``gi_smiles_read_arom`` in the header; tests/kekule_read_model.py is its specification.  Writing
+    aromatic SMILES, stereo and order-1.5 bonds (``use_aromatic_bonds``) stay out of scope.
 
     ``strings``: a sequence of ``str`` (packed by ``pack_strings``: one host buffer, one copy), ``smiles``' result, or a
     [G, max_len] uint8 tensor on the device (16-byte aligned, max_len a multiple of 16) with ``length`` [G] int32 or
@@ -1464,14 +1483,16 @@ def read_smiles(strings, rules: ValenceRules, max_n_nodes: int, *, length: Optio
     Fe, default the rules' bond orders or 3.
 
     Result (``ReadMolecules``, views of one device buffer): ``nodes``, ``edges``, ``n_nodes``, ``status``
-    (``READ_STATUS_MESSAGES``; any bit of ``lib.SMR_ERROR`` leaves the all-zero molecule, which the rest of the library
-    treats as empty, and ``SMR_TOO_MANY`` leaves the atoms needed in ``n_nodes``), ``atom_pos``.  G = 0 is answered
-    without a launch."""
+    (``READ_STATUS_MESSAGES``, ``KEKULE_STATUS_MESSAGES``; any bit of ``lib.SMR_ERROR``, or of ``lib.SMR_READ_ERROR``
+    with ``aromatic="kekulize"``, leaves the all-zero molecule, which the rest of the library treats as empty, and
+    ``SMR_TOO_MANY`` leaves the atoms needed in ``n_nodes``), ``atom_pos``.  G = 0 is answered without a launch."""
     what = "read_smiles"
     if not isinstance(rules, ValenceRules):
         raise TypeError(f"{what}: rules must be a ValenceRules, got {type(rules).__name__}")
     if stereo not in ("error", "drop"):
         raise ValueError(f"{what}: stereo must be 'error' or 'drop', got {stereo!r}")
+    if aromatic not in ("error", "kekulize"):
+        raise ValueError(f"{what}: aromatic must be 'error' or 'kekulize', got {aromatic!r}")
     A, Cn, H = rules.groups
     for name, v, lo in (("max_n_nodes", max_n_nodes, 1), ("n_chirality", n_chirality, 0),
                         ("none_chirality", none_chirality, 0)):
@@ -1523,13 +1544,17 @@ def read_smiles(strings, rules: ValenceRules, max_n_nodes: int, *, length: Optio
     res = ReadMolecules.empty(dev, G, N, Fn, Fe)
     if G > 0:
         out = res._ptrs()
-        with torch.cuda.device(dev):
-            L.check(L.load().gi_smiles_read(
-                G, N, Fn, Fe, text.data_ptr(), None if length is None else length.data_ptr(), max_len, A, Cn, H,
+        head = (G, N, Fn, Fe, text.data_ptr(), None if length is None else length.data_ptr(), max_len, A, Cn, H,
                 rules.allowed_mask.data_ptr(), order2.data_ptr(),
                 None if rules.h_values is None else rules.h_values.data_ptr(), charges.data_ptr(), symbols.data_ptr(),
-                int(none_chirality), int(stereo == "drop"), out["nodes"], out["edges"], out["n_nodes"], out["status"],
-                out["atom_pos"], torch.cuda.current_stream(dev).cuda_stream), "gi_smiles_read")
+                int(none_chirality), int(stereo == "drop"))
+        with torch.cuda.device(dev):
+            tail = (out["nodes"], out["edges"], out["n_nodes"], out["status"], out["atom_pos"],
+                    torch.cuda.current_stream(dev).cuda_stream)
+            if aromatic == "kekulize":
+                L.check(L.load().gi_smiles_read_arom(*head, 1, *tail), "gi_smiles_read_arom")
+            else:
+                L.check(L.load().gi_smiles_read(*head, *tail), "gi_smiles_read")
     return res
 
 
@@ -1550,7 +1575,8 @@ def read_smi(path, rules: ValenceRules, max_n_nodes: int, *, batch: int = 8192, 
     the header and is skipped; of every other line the first blank-separated column is the string and the second the
     name.  NO LINE IS LEFT OUT: a string with an error bit — ``write_smi``'s ``[Xe]`` placeholder under rules without
     Xe, an aromatic string, an empty line — stays in its row as the all-zero molecule with its ``status``; it is the
-    caller who masks (``status & lib.SMR_ERROR``) or routes such rows to RDKit."""
+    caller who masks (``status & lib.SMR_ERROR``; ``lib.SMR_READ_ERROR`` with ``aromatic="kekulize"``, which goes
+    through ``**kw`` like every other option) or routes such rows to RDKit."""
     if not isinstance(batch, (int, np.integer)) or isinstance(batch, bool) or batch < 1:
         raise ValueError(f"read_smi: batch must be a positive integer, got {batch!r}")
     with open(path, "rb") as f:

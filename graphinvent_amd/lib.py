@@ -169,7 +169,9 @@ SMI_MAX_LEN = 8192                                      # GI_SMI_MAX_LEN
  SMR_STEREO_DROPPED, SMR_UNSUPPORTED) = (1 << k for k in range(16, 26))
 SMR_ERROR = (SMR_MULTI_BOND | SMR_EMPTY | SMR_SELF_LOOP | SMR_AROMATIC | SMR_TOO_MANY | SMR_SYNTAX | SMR_RING_OPEN |
              SMR_RING_ORDER | SMR_ELEMENT | SMR_CHARGE | SMR_HCOUNT | SMR_BOND_ORDER | SMR_STEREO |
-             SMR_UNSUPPORTED)                           # GI_SMR_ERROR: the bits that leave no molecule
+             SMR_UNSUPPORTED)                           # the bits of gi_smiles_read that leave no molecule
+SMR_KEKULE, SMR_KEKULIZED = 1 << 26, 1 << 27            # GI_SMR_* of gi_smiles_read_arom with aromatic = 1 only
+SMR_READ_ERROR = SMR_ERROR | SMR_KEKULE                 # GI_SMR_ERROR: SMR_ERROR and the one error bit kekulising adds
 
 
 class RouteDims(C.Structure):
@@ -316,6 +318,8 @@ SIGNATURES = {
                            vp, vp, vp, vp, vp]),
     "gi_smiles_read": (ci, [ci, ci, ci, ci, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp,
                             vp]),
+    "gi_smiles_read_arom": (ci, [ci, ci, ci, ci, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp,
+                                 vp, vp]),
 }
 FUSE_GATES_V4, FUSE_DH_SCATTER, FUSE_TIER2_DSELU, FUSE_SLOTS = 1, 2, 4, 8  # GI_FUSE_*
 GLUE_READOUT_FWD, GLUE_READOUT_BWD, GLUE_LOSS_MEAN, GLUE_GRU_AGG = 1, 2, 4, 8  # GI_GLUE_*

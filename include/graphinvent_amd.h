@@ -1366,7 +1366,8 @@ int gi_mol_smiles(int G, int N, int Fn, int Fe, const void* nodes, const void* e
 /* Molecule reading (gi_smiles_read.hip): SMILES strings into molecules, the inverse of gi_mol_smiles ON THE WRITER'S
  * SUBSET of OpenSMILES — what the reference's preprocessing gets from one MolFromSmiles and one graph construction per
  * molecule on the host.  NOT RDKit: NO AROMATIC INPUT (nothing is kekulised) AND NO STEREO; such a string gets a status
- * bit and no molecule, so that the caller can route it to RDKit.  Atoms are numbered IN STRING ORDER, which is not the
+ * bit and no molecule, so that the caller can route it to RDKit (gi_smiles_read_arom below reads aromatic input, and
+ * kekulises it by a rule of its own).  Atoms are numbered IN STRING ORDER, which is not the
  * order of the reference's preprocessing.  tests/smiles_read_model.py is the Python specification, stage by stage.
  *
  * gi_smiles_read, one launch, one workgroup per string, integers only, no global atomics, no scratch, nothing to clear
@@ -1420,14 +1421,53 @@ int gi_mol_smiles(int G, int N, int Fn, int Fe, const void* nodes, const void* e
 #define GI_SMR_STEREO 8388608       /* '@' '/' '\' with drop_stereo = 0 */
 #define GI_SMR_STEREO_DROPPED 16777216 /* the same with drop_stereo = 1: skipped, '/' '\' are single bonds (informational) */
 #define GI_SMR_UNSUPPORTED 33554432 /* an isotope, an atom class, "++" / "--", '$', the wildcard */
+#define GI_SMR_KEKULE 67108864      /* gi_smiles_read_arom, aromatic = 1: no Kekule structure (no perfect matching) */
+#define GI_SMR_KEKULIZED 134217728  /* the same: the string had an aromatic atom and was read (informational) */
 #define GI_SMR_ERROR (GI_SMR_MULTI_BOND | GI_SMR_EMPTY | GI_SMR_SELF_LOOP | GI_SMR_AROMATIC | GI_SMR_TOO_MANY | \
                       GI_SMR_SYNTAX | GI_SMR_RING_OPEN | GI_SMR_RING_ORDER | GI_SMR_ELEMENT | GI_SMR_CHARGE | \
-                      GI_SMR_HCOUNT | GI_SMR_BOND_ORDER | GI_SMR_STEREO | GI_SMR_UNSUPPORTED)
+                      GI_SMR_HCOUNT | GI_SMR_BOND_ORDER | GI_SMR_STEREO | GI_SMR_UNSUPPORTED | GI_SMR_KEKULE)
 int gi_smiles_read(int G, int N, int Fn, int Fe, const unsigned char* text, const int* length, int max_len,
                    int n_types, int n_charges, int n_imp_h, const unsigned short* allowed, const signed char* order2,
                    const signed char* h_values, const signed char* charges, const unsigned char* symbols,
                    int none_chirality, int drop_stereo, signed char* nodes, signed char* edges, int* n_nodes,
                    int* status, int* atom_pos, void* stream);
+
+/* gi_smiles_read with AROMATIC INPUT: the same arguments and `aromatic`, 0 or 1 (anything else: GI_EINVAL).  0 is
+ * gi_smiles_read, the same kernel instantiation, byte for byte.  1 reads aromatic atoms and ':' and KEKULISES inside the
+ * same launch: single and double bonds are assigned to the aromatic-marked bonds, since the library stores Kekule graphs
+ * (the reference's use_aromatic_bonds False).  THE RULE IS OURS, NOT RDKit'S KEKULISATION: no ring or aromaticity
+ * perception, no canonical choice among several Kekule structures; two strings of one compound can come out as two
+ * different Kekule structures.  tests/kekule_read_model.py is the Python specification, in every output byte.
+ *
+ * Grammar added with aromatic = 1 (everything else as above; GI_SMR_AROMATIC is never set):
+ *   bare atom    b c n o p s are aromatic atoms.  Any other small letter where a symbol is expected is GI_SMR_SYNTAX.
+ *   bracket atom the symbol may be b c n o p s se as (OpenSMILES' list; another small symbol is GI_SMR_SYNTAX); it is
+ *                looked up in symbols CAPITALISED; H count and charge as above ("[nH]", "[n+]", "[cH-]", "[se]").
+ *   bonds        ':' is a bond symbol.  A bond with no symbol (a chain bond, or a ring bond with no symbol on either
+ *                end) between two aromatic atoms is AROMATIC-MARKED, and so is ':'; ':' next to an atom that is not
+ *                aromatic is GI_SMR_UNSUPPORTED; ':' on one end of a ring bond and another symbol on the other is
+ *                GI_SMR_RING_ORDER.  '-' '=' '#' between aromatic atoms mean what they say.
+ * Which atoms need a double bond: with sigma the atom's bond-order sum, every aromatic-marked bond counted 1, a bare
+ * aromatic atom needs one when sigma is not a normal valence of its element (the table above) and a larger one exists;
+ * a bracket aromatic atom when sigma + its stated H is not in allowed[type, charge] and a larger allowed valence exists.
+ * So c needs one unless it has an exocyclic "=O", pyridine n needs one; three-coordinate n, [nH], o, s, [se], [n-] do
+ * not; [n+], [o+], [s+] with two ring bonds and n(=O) do.  No other atom needs one.
+ * The assignment: a perfect matching of the needing atoms over the aromatic-marked bonds between two needing atoms.
+ * Matched bonds become the double type (order2 == 4), every other aromatic-marked bond the single type (order2 == 2); a
+ * type that is needed and missing is GI_SMR_BOND_ORDER.  No perfect matching: GI_SMR_KEKULE and the all-zero molecule.
+ * Which matching: a greedy pass over the atoms in ascending index, each matched to its lowest-index free candidate
+ * neighbour, then one breadth-first augmenting-path search with blossom contraction (base / parent / queue) per needing
+ * atom still free, in ascending index, neighbours scanned in ascending index.  An aromatic-marked bond between two
+ * rings ("c1ccccc1c1ccccc1") is in every perfect matching or in none, by the parity of the needing atoms on its two
+ * sides: biphenyl gets a single linker, "c1cccc1c1cccc1" is read as fulvalene.
+ * Hydrogens are counted after the assignment, on the Kekule bonds, a bare aromatic symbol capitalised first.  The stage
+ * runs after the walk and before the hydrogens, only while no error bit is set.  GI_SMR_KEKULIZED: the string had an
+ * aromatic atom and no error bit. */
+int gi_smiles_read_arom(int G, int N, int Fn, int Fe, const unsigned char* text, const int* length, int max_len,
+                        int n_types, int n_charges, int n_imp_h, const unsigned short* allowed,
+                        const signed char* order2, const signed char* h_values, const signed char* charges,
+                        const unsigned char* symbols, int none_chirality, int drop_stereo, int aromatic,
+                        signed char* nodes, signed char* edges, int* n_nodes, int* status, int* atom_pos, void* stream);
 
 #ifdef __cplusplus
 }
