@@ -727,6 +727,28 @@ class ValenceRules:
         return self._order2[Fe]
 
 
+def _rules_groups(what: str, rules) -> tuple:
+    """-> ``rules.groups``.  Every entry point asks this first, before it looks at a tensor: the ``TypeError`` wins."""
+    if not isinstance(rules, ValenceRules):
+        raise TypeError(f"{what}: rules must be a ValenceRules, got {type(rules).__name__}")
+    return rules.groups
+
+
+def _check_rules(what: str, rules, Fn: int, Fe: int, dev):
+    """``rules`` (which ``_rules_groups`` has seen) against inputs of ``Fn`` node entries and ``Fe`` bond types on
+    ``dev`` -> (A, C, H, order2 on the device).  ``dev = None``: the caller does not know the inputs' device yet and
+    compares it itself."""
+    A, Cn, H = rules.groups
+    if A + Cn + H > Fn:
+        raise ValueError(f"{what}: the rules' segments {rules.groups} do not fit node rows of Fn = {Fn}")
+    if rules.device is None:
+        raise RuntimeError(f"{what}: the rules were built with device=None and hold no device tables (no CPU fallback)")
+    order2 = rules.order2(Fe)
+    if dev is not None and order2.device != dev:
+        raise ValueError(f"{what}: the molecules are on {dev}, the rules' tables on {order2.device}")
+    return A, Cn, H, order2
+
+
 class MoleculeValidity(_ResultBuffer):
     """What ``validity`` wrote, on the device: ``valid`` [G] fp32, ``status`` / ``first_bad`` [G] int32,
     ``atom_valence`` / ``atom_h`` [G, N] int8, ``desc`` [G, 6] int32 (``DESC_NAMES``) and ``counts`` [4] int32 (valid,
@@ -780,18 +802,10 @@ def validity(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Optional[torch.T
     i < j with a bond), n_components, n_rings (= n_bonds - n_atoms + n_components); ``counts`` [4] int32 = valid,
     terminated (``termination`` [G] non-zero; none given: 0), valid and terminated, G."""
     what = "validity"
-    if not isinstance(rules, ValenceRules):
-        raise TypeError(f"{what}: rules must be a ValenceRules, got {type(rules).__name__}")
+    _rules_groups(what, rules)
     G, N, Fn, Fe, dtype, n_nodes, nn_bytes, _ = _check_inputs(what, nodes, edges, n_nodes, None, False)
     dev = nodes.device
-    A, Cn, H = rules.groups
-    if A + Cn + H > Fn:
-        raise ValueError(f"{what}: the rules' segments {rules.groups} do not fit node rows of Fn = {Fn}")
-    order2 = rules.order2(Fe)
-    if rules.device is None:
-        raise RuntimeError(f"{what}: the rules were built with device=None and hold no device tables (no CPU fallback)")
-    if rules.allowed_mask.device != dev:
-        raise ValueError(f"{what}: the molecules are on {dev}, the rules' tables on {rules.allowed_mask.device}")
+    A, Cn, H, order2 = _check_rules(what, rules, Fn, Fe, dev)
     termination, term_dtype = _check_termination(what, termination, G, dev)
     if G == 0:                                               # no launch: the counts are zero
         return MoleculeValidity(torch.zeros(MoleculeValidity.nbytes(0, N), dtype=torch.uint8, device=dev), 0, N)
@@ -879,21 +893,13 @@ def fingerprint(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Optional[torc
     a molecule gets an ALL-ZERO row (and scores 0 in ``activity``: the reference's ``except: pass``).  ``.host()`` is one
     copy and one synchronisation.  G = 0 is answered without a launch."""
     what = "fingerprint"
-    if not isinstance(rules, ValenceRules):
-        raise TypeError(f"{what}: rules must be a ValenceRules, got {type(rules).__name__}")
+    _rules_groups(what, rules)
     n_bits = _check_n_bits(what, n_bits)
     if not isinstance(radius, (int, np.integer)) or isinstance(radius, bool) or not 0 <= radius <= L.FP_MAX_RADIUS:
         raise ValueError(f"{what}: radius must be an integer in [0, {L.FP_MAX_RADIUS}], got {radius!r}")
     G, N, Fn, Fe, dtype, n_nodes, nn_bytes, _ = _check_inputs(what, nodes, edges, n_nodes, None, False)
     dev = nodes.device
-    A, Cn, H = rules.groups
-    if A + Cn + H > Fn:
-        raise ValueError(f"{what}: the rules' segments {rules.groups} do not fit node rows of Fn = {Fn}")
-    if rules.device is None:
-        raise RuntimeError(f"{what}: the rules were built with device=None and hold no device tables (no CPU fallback)")
-    order2 = rules.order2(Fe)
-    if order2.device != dev:
-        raise ValueError(f"{what}: the molecules are on {dev}, the rules' tables on {order2.device}")
+    A, Cn, H, order2 = _check_rules(what, rules, Fn, Fe, dev)
     W = n_bits // 32
     res = Fingerprints.empty(dev, G, N, W, bool(atom_ids))
     if G > 0:
@@ -1271,11 +1277,9 @@ def smiles(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Optional[torch.Ten
     and the informational ``SMI_OVER`` and ``SMI_FRAGMENTS``), ``atom_pos`` [G, N] int32.  ``.host()`` is one copy and
     one synchronisation.  G = 0 is answered without a launch."""
     what = "smiles"
-    if not isinstance(rules, ValenceRules):
-        raise TypeError(f"{what}: rules must be a ValenceRules, got {type(rules).__name__}")
+    A, Cn, H = _rules_groups(what, rules)
     if canonical and rank is not None:
         raise ValueError(f"{what}: give rank or canonical=True, not both")
-    A, Cn, H = rules.groups
     if hydrogens is None:
         hydrogens = "stored" if H else "fill"
     if hydrogens not in ("fill", "stored"):
@@ -1292,12 +1296,8 @@ def smiles(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Optional[torch.Ten
         raise ValueError(f"{what}: max_len must be a multiple of 16 in [16, {L.SMI_MAX_LEN}], got {max_len!r}")
     max_len = int(max_len)
     dev = nodes.device
-    if A + Cn + H > Fn:
-        raise ValueError(f"{what}: the rules' segments {rules.groups} do not fit node rows of Fn = {Fn}")
+    A, Cn, H, order2 = _check_rules(what, rules, Fn, Fe, dev)
     symbols, charges = _smiles_tables(what, rules)
-    order2 = rules.order2(Fe)
-    if order2.device != dev:
-        raise ValueError(f"{what}: the molecules are on {dev}, the rules' tables on {order2.device}")
     if rank is not None:
         if not isinstance(rank, torch.Tensor) or not rank.is_cuda or rank.device != dev:
             raise RuntimeError(f"{what}: rank must be a CUDA tensor on {dev} (no CPU fallback)")
@@ -1487,13 +1487,11 @@ def read_smiles(strings, rules: ValenceRules, max_n_nodes: int, *, length: Optio
     with ``aromatic="kekulize"``, leaves the all-zero molecule, which the rest of the library treats as empty, and
     ``SMR_TOO_MANY`` leaves the atoms needed in ``n_nodes``), ``atom_pos``.  G = 0 is answered without a launch."""
     what = "read_smiles"
-    if not isinstance(rules, ValenceRules):
-        raise TypeError(f"{what}: rules must be a ValenceRules, got {type(rules).__name__}")
+    A, Cn, H = _rules_groups(what, rules)
     if stereo not in ("error", "drop"):
         raise ValueError(f"{what}: stereo must be 'error' or 'drop', got {stereo!r}")
     if aromatic not in ("error", "kekulize"):
         raise ValueError(f"{what}: aromatic must be 'error' or 'kekulize', got {aromatic!r}")
-    A, Cn, H = rules.groups
     for name, v, lo in (("max_n_nodes", max_n_nodes, 1), ("n_chirality", n_chirality, 0),
                         ("none_chirality", none_chirality, 0)):
         if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < lo:
@@ -1508,8 +1506,7 @@ def read_smiles(strings, rules: ValenceRules, max_n_nodes: int, *, length: Optio
     symbol_table(rules.atom_types)                           # raises for a symbol that cannot be spelt
     if not all(-127 <= c <= 127 for c in rules.formal_charge):
         raise ValueError(f"{what}: formal charges {rules.formal_charge} must lie in [-127, 127]")
-    if rules.device is None:
-        raise RuntimeError(f"{what}: the rules were built with device=None and hold no device tables (no CPU fallback)")
+    A, Cn, H, order2 = _check_rules(what, rules, Fn, Fe, None)    # the text's device is known only below
     if isinstance(strings, MoleculeStrings):
         if length is not None:
             raise ValueError(f"{what}: smiles' result brings its own length")
@@ -1538,7 +1535,6 @@ def read_smiles(strings, rules: ValenceRules, max_n_nodes: int, *, length: Optio
             raise ValueError(f"{what}: length must be a contiguous int32 tensor of shape ({G},), got {length.dtype} "
                              f"{tuple(length.shape)}")
     symbols, charges = _smiles_tables(what, rules)
-    order2 = rules.order2(Fe)
     if order2.device != dev:
         raise ValueError(f"{what}: the text is on {dev}, the rules' tables on {order2.device}")
     res = ReadMolecules.empty(dev, G, N, Fn, Fe)

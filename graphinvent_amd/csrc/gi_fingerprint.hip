@@ -7,10 +7,11 @@
 // specification; K0 / K1 are copied from it.
 //
 // mol_fingerprint_kernel  one 256-lane WORKGROUP per molecule:
-//   1  read and check exactly as mol_valence_kernel stages 1-2 (gi_for_each_nonzero, one 128-bit adjacency row per
-//      (bond type, node) in LDS, gi_mol_structure, GI_MOL_ONEHOT / _MULTI_BOND, GI_VAL_SELF_LOOP, GI_VAL_EMPTY).  A
-//      molecule with any of these bits gets an all-zero row, popcount 0, atom_id -1 and its status word; nothing below
-//      is evaluated for it (so no diagonal bit is ever seen below);
+//   1  read and check: gi_read_labelled of gi_molread.h, the front end shared with gi_valence.hip and gi_smiles.hip
+//      (one 128-bit adjacency row per (bond type, node) in LDS, the bits of GI_MOL_MALFORMED, GI_VAL_SELF_LOOP,
+//      GI_VAL_EMPTY).  A molecule with any of these bits gets an all-zero row, popcount 0, atom_id -1 and its status
+//      word; nothing below is evaluated for it (so no diagonal bit is ever seen below).  deg_i and o2_i are taken from
+//      that function's one pass over the rows (GiLabelledNode), not from a second walk with gi_atom_order2;
 //   2  one thread per atom i < n: id_0[i] = mix64(K0 + a_i + 256 c_i + 2^16 deg_i + 2^24 o2_i);
 //   3  rounds r = 1 .. R: id_r[i] = mix64(mix64(id_{r-1}[i] + r) + sum over bonds (t, j) of i of
 //      mix64(id_{r-1}[j] ^ (K1 order2[t]))), 64-bit wrap-around (a commutative sum: no order to depend on), two [128]
@@ -48,8 +49,7 @@ constexpr int NT = GI_MOL_NT;
 constexpr int MAXN = GI_MAX_NODES;
 constexpr int MAXW = GI_FP_MAX_BITS / 32;
 constexpr int TILE = 16;                                     // query rows of a workgroup of fp_compare_kernel
-constexpr int ZERO_ROW = GI_MOL_ONEHOT | GI_MOL_BOND_PAST_N | GI_MOL_VALUE | GI_MOL_MULTI_BOND | GI_MOL_ASYMMETRIC |
-                         GI_MOL_NODE_PAST_N | GI_VAL_EMPTY | GI_VAL_SELF_LOOP;
+constexpr int ZERO_ROW = GI_MOL_MALFORMED | GI_VAL_EMPTY | GI_VAL_SELF_LOOP;
 constexpr u64 K0 = 0xD1B54A32D192ED03ull, K1 = 0x8CB92BA72F3D8DD7ull;
 
 template <typename T>
@@ -60,74 +60,28 @@ __global__ __launch_bounds__(NT) void mol_fingerprint_kernel(const T* __restrict
                                                              int* __restrict__ bits, int* __restrict__ popcount,
                                                              int* __restrict__ status, int* __restrict__ atom_id) {
     extern __shared__ unsigned adj[];                        // [Fe][N][4]: bit j of row (t, i): bond t between i and j
-    __shared__ int seg_cnt[3][MAXN], seg_first[2][MAXN];     // set entries per segment; the lowest of type and charge
+    __shared__ GiLabelled st;
     __shared__ u64 ids[2][MAXN];
     __shared__ __attribute__((aligned(16))) unsigned row[MAXW];
-    __shared__ unsigned present[4];
-    __shared__ int flags_sh, pop_sh;
+    __shared__ int pop_sh;
     const int g = blockIdx.x, tid = threadIdx.x;
-    const int len_n = N * Fn, len_e = N * N * Fe;
-    const T* nd = nodes + (size_t)g * len_n;
-    const T* ed = edges + (size_t)g * len_e;
-    const int o_c = A, o_h = A + C, o_x = A + C + H;         // segment ends; o_x <= Fn (checked on the host)
     for (int i = tid; i < Fe * N * 4; i += NT) adj[i] = 0u;
-    for (int i = tid; i < 3 * MAXN; i += NT) (&seg_cnt[0][0])[i] = 0;
-    for (int i = tid; i < 2 * MAXN; i += NT) (&seg_first[0][0])[i] = 0x7fffffff;
     for (int i = tid; i < MAXW; i += NT) row[i] = 0u;
-    if (tid < 4) present[tid] = 0u;
-    if (tid == 0) { flags_sh = 0; pop_sh = 0; }
-    __syncthreads();
+    if (tid == 0) pop_sh = 0;
 
     // ---- 1: read and check -------------------------------------------------------------------------------
-    int flags = 0;
-    gi_for_each_nonzero(nd, len_n, tid, [&](int o, T v) {
-        if (!gi_is01(v)) flags |= GI_MOL_VALUE;
-        const int i = o / Fn, f = o - i * Fn;                // i < N
-        atomicOr(&present[i >> 5], 1u << (i & 31));
-        if (f < o_x) {                                       // a chirality segment (f >= o_x) is not looked at
-            const int s = f < o_c ? 0 : f < o_h ? 1 : 2;
-            atomicAdd(&seg_cnt[s][i], 1);
-            if (s < 2) atomicMin(&seg_first[s][i], f - (s == 0 ? 0 : o_c));
-        }
-    });
-    gi_for_each_nonzero(ed, len_e, tid, [&](int o, T v) {
-        if (!gi_is01(v)) flags |= GI_MOL_VALUE;
-        const int e = o / Fe, t = o - e * Fe, i = e / N, j = e - i * N;
-        if (i == j) flags |= GI_VAL_SELF_LOOP;
-        atomicOr(&adj[(t * N + i) * 4 + (j >> 5)], 1u << (j & 31));
-    });
-    __syncthreads();
-    const int n = gi_mol_structure(adj, present, n_nodes, nn_bytes, g, N, Fe, tid, flags);
-    int deg = 0, o2 = 0;
-    if (tid < N) {                                           // this thread's node: several types on a pair, deg, o2
-        unsigned seen[4] = {0u, 0u, 0u, 0u};
-        for (int t = 0; t < Fe; ++t) {
-            int cnt = 0;
-            for (int w = 0; w < 4; ++w) {
-                const unsigned r = adj[(t * N + tid) * 4 + w];
-                const unsigned diag = (tid >> 5) == w ? 1u << (tid & 31) : 0u;
-                if (r & seen[w] & ~diag) flags |= GI_MOL_MULTI_BOND;
-                seen[w] |= r;
-                cnt += __popc(r);
-            }
-            o2 += (int)order2[t] * cnt;                      // <= 6 * 8 * 128
-        }
-        for (int w = 0; w < 4; ++w) deg += __popc(seen[w]);
-        if (tid < n && (seg_cnt[0][tid] != 1 || seg_cnt[1][tid] != 1 || (H > 0 && seg_cnt[2][tid] != 1)))
-            flags |= GI_MOL_ONEHOT;
-    }
-    if (n == 0) flags |= GI_VAL_EMPTY;
-    if (flags) atomicOr(&flags_sh, flags);
-    __syncthreads();
-    const bool sound = (flags_sh & ZERO_ROW) == 0;           // uniform
+    GiLabelledNode me;                                       // deg and o2 come from the pass that checks the rows
+    const int n = gi_read_labelled<true>(nodes + (size_t)g * (N * Fn), edges + (size_t)g * (N * N * Fe), n_nodes,
+                                         nn_bytes, g, N, Fn, Fe, A, C, H, order2, tid, adj, st, nullptr, me);
+    const bool sound = (st.flags & ZERO_ROW) == 0;           // uniform
     const bool mine = sound && tid < n;                      // this thread owns atom `tid`
     const unsigned fold_mask = (unsigned)(W * 32 - 1);
 
     // ---- 2-4: identifiers, rounds, folding (uniform control flow: every thread meets every barrier) ---------
     u64 id = 0;
     if (mine) {
-        const int a = seg_first[0][tid], c = seg_first[1][tid];           // a < A, c < C: the row is one-hot
-        id = mix64(K0 + (u64)a + 256ull * (u64)c + ((u64)deg << 16) + ((u64)o2 << 24));
+        const int a = st.seg_first[0][tid], c = st.seg_first[1][tid];     // a < A, c < C: the row is one-hot
+        id = mix64(K0 + (u64)a + 256ull * (u64)c + ((u64)me.deg << 16) + ((u64)me.o2 << 24));
         ids[0][tid] = id;
         const unsigned b = (unsigned)id & fold_mask;
         atomicOr(&row[b >> 5], 1u << (b & 31));
@@ -172,7 +126,7 @@ __global__ __launch_bounds__(NT) void mol_fingerprint_kernel(const T* __restrict
     __syncthreads();
     if (tid == 0) {
         popcount[g] = pop_sh;
-        status[g] = flags_sh;
+        status[g] = st.flags;
     }
 }
 
@@ -303,7 +257,7 @@ extern "C" int gi_mol_fingerprint(int G, int N, int Fn, int Fe, const void* node
     (void)hipGetLastError();
     if (const int rc = gi_mol_check_dims(G, N, Fn, Fe)) return rc;
     if (const int rc = gi_mol_check_types(dtype, n_nodes_bytes)) return rc;
-    if (n_types < 1 || n_charges < 1 || n_imp_h < 0 || (long long)n_types + n_charges + n_imp_h > Fn) return GI_EINVAL;
+    if (const int rc = gi_mol_check_segments(n_types, n_charges, n_imp_h, Fn)) return rc;
     if (radius < 0 || radius > GI_FP_MAX_RADIUS || n_bits % 32 != 0 || !fp_width_ok(n_bits / 32)) return GI_EINVAL;
     if (G == 0) return 0;
     if (!nodes || !edges || !order2 || !bits || !popcount || !status || ((uintptr_t)bits & 15)) return GI_EINVAL;

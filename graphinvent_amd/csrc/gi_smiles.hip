@@ -5,13 +5,13 @@
 // segment.  The grammar is written out at gi_mol_smiles in include/graphinvent_amd.h; tests/smiles_model.py is the
 // Python specification the bytes are held to.
 //
-// mol_smiles_kernel  one 256-lane WORKGROUP per molecule, the reading and checking of mol_valence_kernel:
-//   1  all waves read the molecule once (gi_for_each_nonzero of gi_molread.h; fp32 or int8) and check it while they
-//      read; in LDS one 128-bit adjacency row per (bond type, node) and the segment entries of every node;
-//   2  n and the well-formedness bits (gi_mol_structure, _ONEHOT, _MULTI_BOND), GI_SMI_SELF_LOOP, _EMPTY, _AROMATIC;
-//   3  one lane per atom: x, the hydrogen count (the fill of gi_mol_valence, or the stored one), GI_SMI_OVER and the atom
-//      token (at most TOK bytes); the traversal key of an atom = its place in the order by (rank, index); the OR of its
-//      rows with the bits moved to key space;
+// mol_smiles_kernel  one 256-lane WORKGROUP per molecule:
+//   1, 2  gi_read_labelled of gi_molread.h, the front end shared with gi_valence.hip and gi_fingerprint.hip: all waves
+//      read the molecule once (fp32 or int8) and check it while they read; in LDS one 128-bit adjacency row per (bond
+//      type, node) and the segment entries of every node; n and the bits of GI_MOL_MALFORMED, GI_SMI_SELF_LOOP, _EMPTY;
+//   3  one lane per atom: x, the hydrogen count (gi_hydrogen_fill, as gi_mol_valence, or the stored one), GI_SMI_OVER,
+//      _AROMATIC and the atom token (at most TOK bytes); the traversal key of an atom = its place in the order by
+//      (rank, index); the OR of its rows with the bits moved to key space;
 //   4  ONE LANE walks depth-first over the key-space rows, its stack in LDS, the visited set in registers: 2 n + 1 steps
 //      at most (every step pushes an atom, pops one, or ends the walk).  It leaves the pre-order, the tree parent, the
 //      last child and the end of the subtree of every atom, and the number of components;
@@ -40,9 +40,7 @@ typedef unsigned char u8;
 constexpr int NT = GI_MOL_NT;
 constexpr int MAXN = GI_MAX_NODES;
 constexpr int TOK = 12;                                      // '[' 2 letters 'H' 3 digits sign 3 digits ']'
-constexpr int MOL_BITS = GI_MOL_ONEHOT | GI_MOL_BOND_PAST_N | GI_MOL_VALUE | GI_MOL_MULTI_BOND | GI_MOL_ASYMMETRIC |
-                         GI_MOL_NODE_PAST_N;
-constexpr int NO_STRING = MOL_BITS | GI_SMI_EMPTY | GI_SMI_SELF_LOOP | GI_SMI_AROMATIC | GI_SMI_RING_LIMIT;
+constexpr int NO_STRING = GI_MOL_MALFORMED | GI_SMI_EMPTY | GI_SMI_SELF_LOOP | GI_SMI_AROMATIC | GI_SMI_RING_LIMIT;
 
 struct SmiTables {
     const unsigned short* allowed;                           // [A * C]: bit v = total valence v is allowed
@@ -61,22 +59,6 @@ struct SmiOut {
     int max_len;
 };
 
-// the normal valences of the OpenSMILES organic subset as a bit mask (bit v), 0 for any other symbol
-__device__ __forceinline__ unsigned organic_valences(u8 s0, u8 s1) {
-    if (s1 == 0) {
-        switch (s0) {
-            case 'B': return 1u << 3;
-            case 'C': return 1u << 4;
-            case 'N': case 'P': return (1u << 3) | (1u << 5);
-            case 'O': return 1u << 2;
-            case 'S': return (1u << 2) | (1u << 4) | (1u << 6);
-            case 'F': case 'I': return 1u << 1;
-            default: return 0u;
-        }
-    }
-    return ((s0 == 'C' && s1 == 'l') || (s0 == 'B' && s1 == 'r')) ? 1u << 1 : 0u;
-}
-
 // v in [0, 999] as decimal digits at p -> the digits written (1 to 3)
 __device__ __forceinline__ int put_number(u8* p, int v) {
     int k = 0;
@@ -86,8 +68,6 @@ __device__ __forceinline__ int put_number(u8* p, int v) {
     return k;
 }
 
-__device__ __forceinline__ bool row_bit(const unsigned* row, int j) { return (row[j >> 5] >> (j & 31)) & 1u; }
-
 template <typename T>
 __global__ __launch_bounds__(NT) void mol_smiles_kernel(const T* __restrict__ nodes, const T* __restrict__ edges,
                                                         const void* __restrict__ n_nodes, int nn_bytes, int N, int Fn,
@@ -95,95 +75,42 @@ __global__ __launch_bounds__(NT) void mol_smiles_kernel(const T* __restrict__ no
     extern __shared__ __align__(16) unsigned dyn[];          // adj [Fe][N][4] | the string [max_len] | ring text [max_len]
     __shared__ __align__(16) unsigned krow[MAXN][4];         // key space: bit of every bonded partner
     __shared__ __align__(16) unsigned rrow[MAXN][4], dbl[MAXN][4], tpl[MAXN][4];   // pre-order space: ring / double / triple
-    __shared__ int seg_cnt[3][MAXN], seg_first[3][MAXN];
+    __shared__ GiLabelled st;
     __shared__ u8 tok[MAXN][TOK];
     __shared__ int toklen[MAXN], rk[MAXN], kpos[MAXN], kinv[MAXN];     // by input index; kinv by key
     __shared__ int pre[MAXN], park[MAXN], lastc[MAXN], subk[MAXN], stack[MAXN];   // by key
     __shared__ int ord[MAXN], para[MAXN], closers[MAXN], rstart[MAXN], rlen[MAXN], lens[MAXN];   // by pre-order index
     __shared__ int apos[MAXN];                               // by input index
-    __shared__ unsigned present[4], ringat[4];                  // ringat: the pre-order indices that have a ring bond
-    __shared__ int flags_sh;
+    __shared__ unsigned ringat[4];                           // the pre-order indices that have a ring bond
     unsigned* adj = dyn;
     u8* str = reinterpret_cast<u8*>(dyn + Fe * N * 4);
     u8* rtx = str + out.max_len;
-    const int g = blockIdx.x, tid = threadIdx.x;
-    const int len_n = N * Fn, len_e = N * N * Fe, max_len = out.max_len;
-    const T* nd = nodes + (size_t)g * len_n;
-    const T* ed = edges + (size_t)g * len_e;
-    const int o_c = tb.A, o_h = tb.A + tb.C, o_x = tb.A + tb.C + tb.H;    // segment ends; o_x <= Fn (checked on the host)
+    const int g = blockIdx.x, tid = threadIdx.x, max_len = out.max_len;
     for (int i = tid; i < Fe * N * 4; i += NT) adj[i] = 0u;
     for (int i = tid; i < max_len / 16; i += NT) reinterpret_cast<uint4*>(str)[i] = make_uint4(0u, 0u, 0u, 0u);
-    for (int i = tid; i < 3 * MAXN; i += NT) { (&seg_cnt[0][0])[i] = 0; (&seg_first[0][0])[i] = 0x7fffffff; }
     if (tid < MAXN) { closers[tid] = 0; apos[tid] = -1; }
-    if (tid < 4) { present[tid] = 0u; ringat[tid] = 0u; }
-    if (tid == 0) flags_sh = 0;
-    __syncthreads();
+    if (tid < 4) ringat[tid] = 0u;
 
-    // ---- 1: read and check -------------------------------------------------------------------------------
-    int flags = 0;
-    gi_for_each_nonzero(nd, len_n, tid, [&](int o, T v) {
-        if (!gi_is01(v)) flags |= GI_MOL_VALUE;
-        const int i = o / Fn, f = o - i * Fn;                // i < N
-        atomicOr(&present[i >> 5], 1u << (i & 31));
-        if (f < o_x) {                                       // a chirality segment (f >= o_x) is not looked at
-            const int s = f < o_c ? 0 : f < o_h ? 1 : 2;
-            atomicAdd(&seg_cnt[s][i], 1);
-            atomicMin(&seg_first[s][i], f - (s == 0 ? 0 : s == 1 ? o_c : o_h));
-        }
-    });
-    gi_for_each_nonzero(ed, len_e, tid, [&](int o, T v) {
-        if (!gi_is01(v)) flags |= GI_MOL_VALUE;
-        const int e = o / Fe, t = o - e * Fe, i = e / N, j = e - i * N;
-        if (i == j) flags |= GI_SMI_SELF_LOOP;
-        atomicOr(&adj[(t * N + i) * 4 + (j >> 5)], 1u << (j & 31));
-    });
-    __syncthreads();
-
-    // ---- 2: n and the well-formedness bits ---------------------------------------------------------------
-    const int n = gi_mol_structure(adj, present, n_nodes, nn_bytes, g, N, Fe, tid, flags);
-    bool arom = false;
-    unsigned seen[4] = {0u, 0u, 0u, 0u};                     // this lane's node: the OR of its rows
-    if (tid < N) {
-        for (int t = 0; t < Fe; ++t)
-            for (int w = 0; w < 4; ++w) {
-                const unsigned row = adj[(t * N + tid) * 4 + w];
-                const unsigned diag = (tid >> 5) == w ? 1u << (tid & 31) : 0u;
-                if (row & seen[w] & ~diag) flags |= GI_MOL_MULTI_BOND;
-                if (row && tb.order2[t] == 3) arom = true;
-                seen[w] |= row;
-            }
-        if (tid < n && (seg_cnt[0][tid] != 1 || seg_cnt[1][tid] != 1 || (tb.H > 0 && seg_cnt[2][tid] != 1)))
-            flags |= GI_MOL_ONEHOT;
-    }
-    if (n == 0) flags |= GI_SMI_EMPTY;
-    if (flags) atomicOr(&flags_sh, flags);
-    __syncthreads();
-    const bool sound = (flags_sh & MOL_BITS) == 0;           // uniform
+    // ---- 1, 2: read and check; n and the well-formedness bits ---------------------------------------------
+    GiLabelledNode me;                                       // me.seen: this lane's node, the OR of its rows
+    const int n = gi_read_labelled<false>(nodes + (size_t)g * (N * Fn), edges + (size_t)g * (N * N * Fe), n_nodes,
+                                          nn_bytes, g, N, Fn, Fe, tb.A, tb.C, tb.H, tb.order2, tid, adj, st, nullptr, me);
+    const bool sound = (st.flags & GI_MOL_MALFORMED) == 0;   // uniform
     const bool mine = sound && tid < n;                      // this lane owns input atom `tid`
 
     // ---- 3: valence, hydrogens, the atom token; the keys ----------------------------------------------------
-    flags = 0;
+    int flags = 0;
     if (mine) {
-        int o2 = 0;
-        for (int t = 0; t < Fe; ++t) {
-            int deg = 0;
-            for (int w = 0; w < 4; ++w) deg += __popc(adj[(t * N + tid) * 4 + w]);
-            o2 += (int)tb.order2[t] * deg;                   // <= 6 * 8 * 128
-        }
-        const int x = (o2 + 1) >> 1;
-        const int a = seg_first[0][tid], c = seg_first[1][tid];           // a < A, c < C: the row is one-hot
-        const unsigned ok = (unsigned)tb.allowed[a * tb.C + c];
-        const unsigned at_least = x > 15 ? 0u : (ok >> x) << x;
-        int h = 0;
-        if (at_least == 0u) flags |= GI_SMI_OVER;
-        else h = __builtin_ctz(at_least) - x;
-        if (tb.stored) h = (int)tb.h_values[seg_first[2][tid]];           // < H: the row is one-hot
-        if (arom) flags |= GI_SMI_AROMATIC;
+        const int x = (gi_atom_order2(adj, tb.order2, N, Fe, tid) + 1) >> 1;
+        const int a = st.seg_first[0][tid], c = st.seg_first[1][tid];     // a < A, c < C: the row is one-hot
+        int h = gi_hydrogen_fill((unsigned)tb.allowed[a * tb.C + c], x);
+        if (h < 0) { flags |= GI_SMI_OVER; h = 0; }
+        if (tb.stored) h = (int)tb.h_values[st.seg_first[2][tid]];        // < H: the row is one-hot
+        if (me.arom) flags |= GI_SMI_AROMATIC;
         const u8 s0 = tb.symbols[2 * a], s1 = tb.symbols[2 * a + 1];
         const int q = (int)tb.charges[c];
         const unsigned org = organic_valences(s0, s1);
-        const unsigned room = x > 15 ? 0u : (org >> x) << x;
-        const int implicit = room ? __builtin_ctz(room) - x : 0;
+        const int implicit = max(gi_hydrogen_fill(org, x), 0);
         u8* p = tok[tid];
         int k = 0;
         if (s0 == 'H' && s1 == 0) h = 0;                     // "[H]" never carries a count
@@ -222,7 +149,7 @@ __global__ __launch_bounds__(NT) void mol_smiles_kernel(const T* __restrict__ no
     if (mine) {
         unsigned moved[4] = {0u, 0u, 0u, 0u};
         for (int w = 0; w < 4; ++w) {
-            unsigned bits = seen[w] & gi_below_word(n, w);
+            unsigned bits = me.seen[w] & gi_below_word(n, w);
             while (bits) {                                   // at most 32 bits
                 const int j = 32 * w + __builtin_ctz(bits);
                 bits &= bits - 1;
@@ -272,11 +199,11 @@ __global__ __launch_bounds__(NT) void mol_smiles_kernel(const T* __restrict__ no
             stack[sp++] = c;                                 // sp <= n: every atom is pushed once
             p = c;
         }
-        if (comps > 1) atomicOr(&flags_sh, GI_SMI_FRAGMENTS);
+        if (comps > 1) atomicOr(&st.flags, GI_SMI_FRAGMENTS);
     }
-    if (flags) atomicOr(&flags_sh, flags);
+    if (flags) atomicOr(&st.flags, flags);
     __syncthreads();
-    const bool walk = (flags_sh & NO_STRING) == 0;           // uniform; the ring limit is not known yet
+    const bool walk = (st.flags & NO_STRING) == 0;           // uniform; the ring limit is not known yet
     const bool atom = walk && tid < n;                       // this lane owns the atom of pre-order index `tid`
 
     // ---- 5: pre-order space ----------------------------------------------------------------------------------
@@ -379,10 +306,10 @@ __global__ __launch_bounds__(NT) void mol_smiles_kernel(const T* __restrict__ no
                 if (tid == 0) { rstart[a] = start; rlen[a] = roff - start; }
             }
         }
-        if (limit && tid == 0) atomicOr(&flags_sh, GI_SMI_RING_LIMIT);
+        if (limit && tid == 0) atomicOr(&st.flags, GI_SMI_RING_LIMIT);
     }
     __syncthreads();
-    const bool written = walk && (flags_sh & GI_SMI_RING_LIMIT) == 0;    // uniform
+    const bool written = walk && (st.flags & GI_SMI_RING_LIMIT) == 0;    // uniform
 
     // ---- 7: byte counts, offsets, the string -------------------------------------------------------------------
     const int dot = atom && tid > 0 && para[tid] < 0;
@@ -414,7 +341,7 @@ __global__ __launch_bounds__(NT) void mol_smiles_kernel(const T* __restrict__ no
     if (tid < N) out.atom_pos[(size_t)g * N + tid] = apos[tid];
     if (tid == 0) {
         out.length[g] = written ? total : 0;
-        out.status[g] = flags_sh | (written && !fits ? GI_SMI_TRUNCATED : 0);
+        out.status[g] = st.flags | (written && !fits ? GI_SMI_TRUNCATED : 0);
     }
 }
 
@@ -428,10 +355,9 @@ extern "C" int gi_mol_smiles(int G, int N, int Fn, int Fe, const void* nodes, co
     (void)hipGetLastError();
     if (const int rc = gi_mol_check_dims(G, N, Fn, Fe)) return rc;
     if (const int rc = gi_mol_check_types(dtype, n_nodes_bytes)) return rc;
-    if (n_types < 1 || n_charges < 1 || n_imp_h < 0 || (long long)n_types + n_charges + n_imp_h > Fn) return GI_EINVAL;
+    if (const int rc = gi_mol_check_segments(n_types, n_charges, n_imp_h, Fn)) return rc;
     if ((stored_h != 0 && stored_h != 1) || (stored_h && n_imp_h == 0)) return GI_EINVAL;
-    if (max_len < 16 || (max_len & 15)) return GI_EINVAL;
-    if (max_len > GI_SMI_MAX_LEN) return GI_ELIMIT;
+    if (const int rc = gi_smi_check_max_len(max_len)) return rc;
     if (G == 0) return 0;
     if (!nodes || !edges || !allowed || !order2 || (n_imp_h > 0 && !h_values) || !charges || !symbols || !text ||
         !length || !status || !atom_pos || ((uintptr_t)text & 15))

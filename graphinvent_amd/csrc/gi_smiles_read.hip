@@ -72,24 +72,6 @@ __device__ __forceinline__ bool is_digit(u8 b) { return b >= '0' && b <= '9'; }
 __device__ __forceinline__ bool is_upper(u8 b) { return b >= 'A' && b <= 'Z'; }
 __device__ __forceinline__ bool is_lower(u8 b) { return b >= 'a' && b <= 'z'; }
 
-// the normal valences of the OpenSMILES organic subset as a bit mask (bit v); the writer's table
-__device__ __forceinline__ unsigned organic_valences(u8 s0, u8 s1) {
-    if (s1 == 0) {
-        switch (s0) {
-            case 'B': return 1u << 3;
-            case 'C': return 1u << 4;
-            case 'N': case 'P': return (1u << 3) | (1u << 5);
-            case 'O': return 1u << 2;
-            case 'S': return (1u << 2) | (1u << 4) | (1u << 6);
-            case 'F': case 'I': return 1u << 1;
-            default: return 0u;
-        }
-    }
-    return ((s0 == 'C' && s1 == 'l') || (s0 == 'B' && s1 == 'r')) ? 1u << 1 : 0u;
-}
-
-__device__ __forceinline__ bool row_bit(const unsigned* row, int j) { return (row[j >> 5] >> (j & 31)) & 1u; }
-
 template <bool AROM>
 __global__ __launch_bounds__(NT) void smiles_read_kernel(const u8* __restrict__ text, const int* __restrict__ length,
                                                          int max_len, int N, int Fn, int Fe, ReadTables tb,
@@ -436,12 +418,7 @@ __global__ __launch_bounds__(NT) void smiles_read_kernel(const u8* __restrict__ 
             t2 = o2 == 4 ? t : t2;
         }
         if (walked && tid < n && is_arom[tid]) {             // who needs a double bond
-            int o2 = 0;
-            for (int t = 0; t < Fe; ++t) {
-                int deg = 0;
-                for (int w = 0; w < 4; ++w) deg += __popc(adj[(t * N + tid) * 4 + w]);
-                o2 += (int)tb.order2[t] * deg;
-            }
+            int o2 = gi_atom_order2(adj, tb.order2, N, Fe, tid);
             for (int w = 0; w < 4; ++w) o2 += 2 * __popc(arom[tid][w]);
             const int h = h_stated[tid];
             const int x = ((o2 + 1) >> 1) + (h < 0 ? 0 : h);             // sigma, with the stated hydrogens of a bracket atom
@@ -587,21 +564,13 @@ __global__ __launch_bounds__(NT) void smiles_read_kernel(const u8* __restrict__ 
 
     // ---- D: one lane per atom: hydrogens, their entry, the valence -----------------------------------------------
     if (walked && tid < n) {
-        int o2 = 0;
-        for (int t = 0; t < Fe; ++t) {
-            int deg = 0;
-            for (int w = 0; w < 4; ++w) deg += __popc(adj[(t * N + tid) * 4 + w]);
-            o2 += (int)tb.order2[t] * deg;                   // <= 6 * 127
-        }
-        const int x = (o2 + 1) >> 1;
+        const int x = (gi_atom_order2(adj, tb.order2, N, Fe, tid) + 1) >> 1;
         int h = h_stated[tid], f = 0;
         if (h < 0) {                                         // bare: the OpenSMILES implicit count
             const int k = start[tid];
             const u8 s0 = AROM && is_lower(str[k]) ? (u8)(str[k] - 32) : str[k];           // a bare aromatic symbol, capitalised
             const u8 s1 = (k + 1 < len && ((s0 == 'C' && str[k + 1] == 'l') || (s0 == 'B' && str[k + 1] == 'r'))) ? str[k + 1] : 0;
-            const unsigned org = organic_valences(s0, s1);
-            const unsigned room = x > 15 ? 0u : (org >> x) << x;
-            h = room ? __builtin_ctz(room) - x : 0;
+            h = max(gi_hydrogen_fill(organic_valences(s0, s1), x), 0);    // the writer's `implicit`
         }
         if (H > 0) {
             int e = -1;
@@ -610,8 +579,7 @@ __global__ __launch_bounds__(NT) void smiles_read_kernel(const u8* __restrict__ 
             if (e < 0) f |= GI_SMR_HCOUNT;
             h_idx[tid] = max(e, 0);
         }
-        const unsigned ok = (unsigned)tb.allowed[a_idx[tid] * C + c_idx[tid]];
-        if ((x > 15 ? 0u : (ok >> x) << x) == 0u) f |= GI_SMR_OVER;
+        if (gi_hydrogen_fill((unsigned)tb.allowed[a_idx[tid] * C + c_idx[tid]], x) < 0) f |= GI_SMR_OVER;
         if (f) atomicOr(&flags_sh, f);
     }
     __syncthreads();
@@ -654,12 +622,11 @@ static int smiles_read_launch(int G, int N, int Fn, int Fe, const unsigned char*
     (void)hipGetLastError();
     if (aromatic != 0 && aromatic != 1) return GI_EINVAL;
     if (const int rc = gi_mol_check_dims(G, N, Fn, Fe)) return rc;
-    if (n_types < 1 || n_charges < 1 || n_imp_h < 0 || (long long)n_types + n_charges + n_imp_h > Fn) return GI_EINVAL;
+    if (const int rc = gi_mol_check_segments(n_types, n_charges, n_imp_h, Fn)) return rc;
     const int rest = Fn - (n_types + n_charges + n_imp_h);
     if (none_chirality < 0 || (rest > 0 && none_chirality >= rest)) return GI_EINVAL;
     if (drop_stereo != 0 && drop_stereo != 1) return GI_EINVAL;
-    if (max_len < 16 || (max_len & 15)) return GI_EINVAL;
-    if (max_len > GI_SMI_MAX_LEN) return GI_ELIMIT;
+    if (const int rc = gi_smi_check_max_len(max_len)) return rc;
     if (G == 0) return 0;
     if (!text || !allowed || !order2 || (n_imp_h > 0 && !h_values) || !charges || !symbols || !nodes || !edges ||
         !n_nodes || !status || !atom_pos || ((uintptr_t)text & 15))

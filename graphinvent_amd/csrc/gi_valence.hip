@@ -5,12 +5,11 @@
 // caller's (analyze.ValenceRules), not RDKit's.
 //
 // mol_valence_kernel  one 256-lane WORKGROUP per molecule:
-//   1  all waves read the molecule once (gi_for_each_nonzero of gi_molread.h; fp32 or int8) and check it while they
-//      read; in LDS one 128-bit adjacency row per (bond type, node), and per node and segment (atom type, formal
-//      charge, implicit H) the number of set entries and the lowest of them;
-//   2  n (given, or the leading rows with a set entry) and the well-formedness bits: GI_MOL_VALUE, _NODE_PAST_N,
-//      _BOND_PAST_N, _ASYMMETRIC (gi_mol_structure, shared with gi_canon.hip), _ONEHOT, _MULTI_BOND (any of them:
-//      the molecule is malformed and nothing below is evaluated), GI_VAL_SELF_LOOP, GI_VAL_EMPTY;
+//   1, 2  gi_read_labelled of gi_molread.h, the front end it shares with gi_fingerprint.hip and gi_smiles.hip: all
+//      waves read the molecule once (fp32 or int8) and check it while they read; in LDS one 128-bit adjacency row per
+//      (bond type, node), and per node and segment (atom type, formal charge, implicit H) the number of set entries and
+//      the lowest of them; n (given, or the leading rows with a set entry) and the bits of GI_MOL_MALFORMED (any of
+//      them: nothing below is evaluated), GI_VAL_SELF_LOOP, GI_VAL_EMPTY;
 //   3  one thread per atom: o2 = sum over bond types of order2[t] * popcount(row (t, i)), x = ceil(o2 / 2), v* = the lowest
 //      allowed valence >= x of (atom type, charge), fill = v* - x; no v*: the atom is over its valence;
 //   4  components by frontier expansion over the OR of the rows; at most N rounds whatever the data holds;
@@ -30,8 +29,6 @@ typedef signed char i8;
 
 constexpr int NT = GI_MOL_NT;
 constexpr int MAXN = GI_MAX_NODES;
-constexpr int MOL_BITS = GI_MOL_ONEHOT | GI_MOL_BOND_PAST_N | GI_MOL_VALUE | GI_MOL_MULTI_BOND | GI_MOL_ASYMMETRIC |
-                         GI_MOL_NODE_PAST_N;
 
 struct ValTables {
     const unsigned short* allowed;                           // [A * C]: bit v = total valence v is allowed
@@ -59,87 +56,35 @@ __global__ __launch_bounds__(NT) void mol_valence_kernel(const T* __restrict__ n
                                                          int term_dtype, int require_connected, ValOut out) {
     extern __shared__ unsigned adj[];                        // [Fe][N][4]: bit j of row (t, i): bond t between i and j
     __shared__ unsigned orr[MAXN][4];                        // the OR of a node's rows over the bond types
-    __shared__ int seg_cnt[3][MAXN], seg_first[3][MAXN];
-    __shared__ unsigned present[4], vis[4], front[2][4];
-    __shared__ int flags_sh, first_sh, sums[4];              // sums: fills, atoms of type H, mass, bonds
+    __shared__ GiLabelled st;
+    __shared__ unsigned vis[4], front[2][4];
+    __shared__ int first_sh, sums[4];                        // sums: fills, atoms of type H, mass, bonds
     const int g = blockIdx.x, tid = threadIdx.x;
-    const int len_n = N * Fn, len_e = N * N * Fe;
-    const T* nd = nodes + (size_t)g * len_n;
-    const T* ed = edges + (size_t)g * len_e;
-    const int o_c = tb.A, o_h = tb.A + tb.C, o_x = tb.A + tb.C + tb.H;    // segment ends; o_x <= Fn (checked on the host)
     for (int i = tid; i < Fe * N * 4; i += NT) adj[i] = 0u;
-    for (int i = tid; i < 3 * MAXN; i += NT) { (&seg_cnt[0][0])[i] = 0; (&seg_first[0][0])[i] = 0x7fffffff; }
-    if (tid < 4) { present[tid] = 0u; vis[tid] = 0u; front[0][tid] = 0u; front[1][tid] = 0u; }
-    if (tid < 4) sums[tid] = 0;
-    if (tid == 0) { flags_sh = 0; first_sh = 0x7fffffff; }
-    __syncthreads();
+    if (tid < 4) { vis[tid] = 0u; front[0][tid] = 0u; front[1][tid] = 0u; sums[tid] = 0; }
+    if (tid == 0) first_sh = 0x7fffffff;
 
-    // ---- 1: read and check -------------------------------------------------------------------------------
-    int flags = 0;
-    gi_for_each_nonzero(nd, len_n, tid, [&](int o, T v) {
-        if (!gi_is01(v)) flags |= GI_MOL_VALUE;
-        const int i = o / Fn, f = o - i * Fn;                // i < N
-        atomicOr(&present[i >> 5], 1u << (i & 31));
-        if (f < o_x) {                                       // a chirality segment (f >= o_x) is not looked at
-            const int s = f < o_c ? 0 : f < o_h ? 1 : 2;
-            atomicAdd(&seg_cnt[s][i], 1);
-            atomicMin(&seg_first[s][i], f - (s == 0 ? 0 : s == 1 ? o_c : o_h));
-        }
-    });
-    gi_for_each_nonzero(ed, len_e, tid, [&](int o, T v) {
-        if (!gi_is01(v)) flags |= GI_MOL_VALUE;
-        const int e = o / Fe, t = o - e * Fe, i = e / N, j = e - i * N;
-        if (i == j) flags |= GI_VAL_SELF_LOOP;
-        atomicOr(&adj[(t * N + i) * 4 + (j >> 5)], 1u << (j & 31));
-    });
-    __syncthreads();
-
-    // ---- 2: n and the well-formedness bits ---------------------------------------------------------------
-    const int n = gi_mol_structure(adj, present, n_nodes, nn_bytes, g, N, Fe, tid, flags);
-    bool arom = false;
-    if (tid < N) {                                           // this thread's node: OR of its rows, several types on a pair
-        unsigned seen[4] = {0u, 0u, 0u, 0u};
-        for (int t = 0; t < Fe; ++t)
-            for (int w = 0; w < 4; ++w) {
-                const unsigned row = adj[(t * N + tid) * 4 + w];
-                const unsigned diag = (tid >> 5) == w ? 1u << (tid & 31) : 0u;
-                if (row & seen[w] & ~diag) flags |= GI_MOL_MULTI_BOND;
-                if (row && tb.order2[t] == 3) arom = true;
-                seen[w] |= row;
-            }
-        for (int w = 0; w < 4; ++w) orr[tid][w] = seen[w];
-        if (tid < n && (seg_cnt[0][tid] != 1 || seg_cnt[1][tid] != 1 || (tb.H > 0 && seg_cnt[2][tid] != 1)))
-            flags |= GI_MOL_ONEHOT;
-    }
-    if (n == 0) flags |= GI_VAL_EMPTY;
-    if (flags) atomicOr(&flags_sh, flags);
-    __syncthreads();
-    const bool sound = (flags_sh & MOL_BITS) == 0;           // uniform
+    // ---- 1, 2: read and check; n and the well-formedness bits ---------------------------------------------
+    GiLabelledNode me;
+    const int n = gi_read_labelled<false>(nodes + (size_t)g * (N * Fn), edges + (size_t)g * (N * N * Fe), n_nodes,
+                                          nn_bytes, g, N, Fn, Fe, tb.A, tb.C, tb.H, tb.order2, tid, adj, st, orr, me);
+    const bool sound = (st.flags & GI_MOL_MALFORMED) == 0;   // uniform
     const bool mine = sound && tid < n;                      // this thread owns atom `tid`
 
     // ---- 3: valences and the hydrogen fill -----------------------------------------------------------------
-    int x = -1, h = -1;
-    flags = 0;
+    int x = -1, h = -1, flags = 0;
     if (mine) {
-        int o2 = 0;
-        for (int t = 0; t < Fe; ++t) {
-            int deg = 0;
-            for (int w = 0; w < 4; ++w) deg += __popc(adj[(t * N + tid) * 4 + w]);
-            o2 += (int)tb.order2[t] * deg;                   // <= 6 * 8 * 128
-        }
-        x = (o2 + 1) >> 1;
-        const int a = seg_first[0][tid], c = seg_first[1][tid];           // a < A, c < C: the row is one-hot
-        const unsigned ok = (unsigned)tb.allowed[a * tb.C + c];
-        const unsigned at_least = x > 15 ? 0u : (ok >> x) << x;
-        if (at_least == 0u) {
+        x = (gi_atom_order2(adj, tb.order2, N, Fe, tid) + 1) >> 1;
+        const int a = st.seg_first[0][tid], c = st.seg_first[1][tid];     // a < A, c < C: the row is one-hot
+        h = gi_hydrogen_fill((unsigned)tb.allowed[a * tb.C + c], x);
+        if (h < 0) {
             flags |= GI_VAL_OVER;
             atomicMin(&first_sh, tid);
             h = 0;
-        } else {
-            h = __builtin_ctz(at_least) - x;
-            if (tb.H > 0 && (int)tb.h_values[seg_first[2][tid]] != h) flags |= GI_VAL_H_MISMATCH;
+        } else if (tb.H > 0 && (int)tb.h_values[st.seg_first[2][tid]] != h) {
+            flags |= GI_VAL_H_MISMATCH;
         }
-        if (arom) flags |= GI_VAL_AROMATIC;
+        if (me.arom) flags |= GI_VAL_AROMATIC;
         int above = 0;                                       // bonded partners of higher index
         for (int w = 0; w < 4; ++w) above += __popc(orr[tid][w] & ~gi_below_word(tid + 1, w));
         if (h) atomicAdd(&sums[0], h);
@@ -180,7 +125,7 @@ __global__ __launch_bounds__(NT) void mol_valence_kernel(const T* __restrict__ n
         }
         if (comps > 1) flags |= GI_VAL_FRAGMENTS;
     }
-    if (flags) atomicOr(&flags_sh, flags);
+    if (flags) atomicOr(&st.flags, flags);
     __syncthreads();
 
     // ---- 5: outputs ------------------------------------------------------------------------------------------
@@ -189,8 +134,8 @@ __global__ __launch_bounds__(NT) void mol_valence_kernel(const T* __restrict__ n
         out.atom_h[(size_t)g * N + a] = (i8)h;
     }
     if (tid == 0) {
-        const int status = flags_sh;
-        int invalid = MOL_BITS | GI_VAL_EMPTY | GI_VAL_SELF_LOOP | GI_VAL_OVER;
+        const int status = st.flags;
+        int invalid = GI_MOL_MALFORMED | GI_VAL_EMPTY | GI_VAL_SELF_LOOP | GI_VAL_OVER;
         if (require_connected) invalid |= GI_VAL_FRAGMENTS;
         const int valid = (status & invalid) == 0;
         out.status[g] = status;
@@ -233,9 +178,8 @@ extern "C" int gi_mol_valence(int G, int N, int Fn, int Fe, const void* nodes, c
     if (const int rc = gi_mol_check_dims(G, N, Fn, Fe)) return rc;
     if (const int rc = gi_mol_check_types(dtype, n_nodes_bytes)) return rc;
     if (term_dtype != GI_DTYPE_F32 && term_dtype != GI_DTYPE_I8) return GI_EINVAL;
-    if (n_types < 1 || n_charges < 1 || n_imp_h < 0 || (long long)n_types + n_charges + n_imp_h > Fn ||
-        h_type < -1 || h_type >= n_types)
-        return GI_EINVAL;
+    if (const int rc = gi_mol_check_segments(n_types, n_charges, n_imp_h, Fn)) return rc;
+    if (h_type < -1 || h_type >= n_types) return GI_EINVAL;
     if (G == 0) return 0;
     if (!nodes || !edges || !allowed || !mass || !order2 || (n_imp_h > 0 && !h_values) || !valid || !status ||
         !first_bad || !atom_valence || !atom_h || !desc || !counts || !scratch)

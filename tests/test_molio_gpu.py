@@ -1,10 +1,12 @@
 """-m gpu: the one molecule reader of csrc/gi_molread.h at every alignment, through every entry point that uses it —
-``analyze.molecular_properties``, ``decode``, ``canonical(want_molecules=True)``, ``validity`` and ``routes.reorder``.
+``analyze.molecular_properties``, ``decode``, ``canonical(want_molecules=True)``, ``routes.reorder`` and the three that
+share the labelled read (``gi_read_labelled``): ``validity``, ``fingerprint`` and ``smiles``.
 
 An alignment sweep at the smallest shapes where the ragged-granule arithmetic can go wrong: int8 molecules at all 16
 byte offsets of a 16-byte granule, fp32 molecules at element offsets 0 to 3 (``routes.reorder`` takes int8 only).  Every
-comparison is exact, against the numpy models tests/analyze_model.py, canon_model.py, valence_model.py and
-reorder_model.py; a shape's models are computed once and shared by all alignments.
+comparison is exact, against the numpy models tests/analyze_model.py, canon_model.py, valence_model.py,
+fingerprint_model.py (radius 2, 64 bits: the smallest row), smiles_model.py (``max_len`` 64) and reorder_model.py; a
+shape's models are computed once and shared by all alignments.
 
 Each case runs G = 3 molecules, so that the middle one has a neighbour on both sides, inside an allocation that holds
 1 everywhere else (tests/molio.py), in two batches:
@@ -12,7 +14,8 @@ Each case runs G = 3 molecules, so that the middle one has a neighbour on both s
             last begins with one.  A read outside a molecule's range finds a set entry that no model has.
     edged   the middle one between two molecules whose FIRST and LAST node and edge entries are set (which makes them
             self-bonded: ``routes.reorder`` copies them through with ROUTE_ERR_PADDING, ``validity`` flags
-            VAL_SELF_LOOP), so that the middle one's neighbours are non-zero right up to its range.
+            VAL_SELF_LOOP, ``fingerprint`` leaves a zero row and ``smiles`` an empty string with the same bit), so that
+            the middle one's neighbours are non-zero right up to its range.
 
 Shapes (N, Fn, Fe), by the bytes of an int8 molecule's nodes and edges:
     (1, 1, 1)    one element: first and last granule are the same ragged granule
@@ -22,7 +25,7 @@ Shapes (N, Fn, Fe), by the bytes of an int8 molecule's nodes and edges:
     (5, 3, 3)    15 and 75
     (13, 8, 3)   104 and 507: the fixtures' pitches
 Left out: (1, 1, 1) for ``molecular_properties`` and ``decode`` (``groups`` needs at least two segments, so Fn >= 2)
-and for ``validity`` (its rules need an atom-type and a formal-charge segment)."""
+and for ``validity``, ``fingerprint`` and ``smiles`` (their rules need an atom-type and a formal-charge segment)."""
 import numpy as np
 import pytest
 import torch
@@ -32,8 +35,10 @@ from graphinvent_amd import lib as L
 from graphinvent_amd import routes
 from tests import analyze_model as AM
 from tests import canon_model as CM
+from tests import fingerprint_model as FM
 from tests import molio
 from tests import reorder_model as OM
+from tests import smiles_model as SM
 from tests import valence_model as VM
 
 pytestmark = pytest.mark.gpu
@@ -175,6 +180,49 @@ def test_validity_at_every_alignment(shape):
     whole, edged = (shared(("valid", shape, k, "given"), None)["status"] for k in ("whole", "edged"))
     assert not (whole & analyze.MALFORMED_BITS).any()
     assert (edged & L.VAL_SELF_LOOP != 0).tolist() == [True, False, True]
+
+
+def labelled_rules(shape):
+    """(the library's rules, the models' rules) for the two segments of `shape`, as in the validity sweep."""
+    A, C = GROUPS[shape[1]]
+    args = dict(atom_types=list("CNOFS")[:A], formal_charge=[0, 1, -1][:C], bond_orders=BOND_ORDERS[shape[2]])
+    return analyze.ValenceRules(**args), VM.Rules(**args)
+
+
+@pytest.mark.parametrize("shape", SHAPES[1:], ids=str)
+def test_fingerprint_at_every_alignment(shape):
+    rules, model_rules = labelled_rules(shape)
+    for kind, (nodes, edges, n), at, dn, de in sweep(shape):
+        for mode, nn in n_given(n).items():
+            want = shared(("fp", shape, kind, mode), lambda: FM.fingerprint(
+                nodes, edges, n if mode == "given" else None, model_rules, radius=2, n_bits=64))
+            got = analyze.fingerprint(dn, de, nn, rules, radius=2, n_bits=64).host()
+            for name in ("bits", "popcount", "status"):
+                assert_equal(got[name], want[name], (kind, at, mode, name))
+    whole, edged = (shared(("fp", shape, k, "given"), None) for k in ("whole", "edged"))
+    assert not whole["status"].any() and whole["popcount"].all()
+    assert (edged["status"] & L.VAL_SELF_LOOP != 0).tolist() == [True, False, True]
+    assert edged["popcount"].tolist()[::2] == [0, 0] and not edged["bits"][::2].any()       # the zero rows ...
+    assert edged["status"][1] == 0 and edged["popcount"][1] > 0                           # ... and the one between them
+
+
+@pytest.mark.parametrize("shape", SHAPES[1:], ids=str)
+def test_smiles_at_every_alignment(shape):
+    rules, model_rules = labelled_rules(shape)
+    for kind, (nodes, edges, n), at, dn, de in sweep(shape):
+        for mode, nn in n_given(n).items():
+            want = shared(("smiles", shape, kind, mode), lambda: SM.write_batch(
+                nodes, edges, n if mode == "given" else None, model_rules, max_len=64))
+            res = analyze.smiles(dn, de, nn, rules, max_len=64)
+            _, length, status, atom_pos = res.host()
+            for name, g in (("status", status), ("length", length), ("atom_pos", atom_pos),
+                            ("text", res.text.cpu().numpy())):
+                assert_equal(g, want[name], (kind, at, mode, name))
+    whole, edged = (shared(("smiles", shape, k, "given"), None) for k in ("whole", "edged"))
+    assert not (whole["status"] & analyze.NO_STRING_BITS).any() and all(whole["strings"])
+    assert (edged["status"] & L.SMI_SELF_LOOP != 0).tolist() == [True, False, True]
+    assert edged["strings"][0] == edged["strings"][2] == "" and edged["length"].tolist()[::2] == [0, 0]
+    assert not edged["status"][1] & analyze.NO_STRING_BITS and edged["strings"][1]
 
 
 @pytest.mark.parametrize("route", ["bfs", "dfs"])
