@@ -1,5 +1,26 @@
-// Host-side orchestration of the whole GGNN / AttentionGGNN forward and backward (gfx950): the
+// Host-side orchestration of the whole GGNN / AttentionGGNN / MNN forward and backward (gfx950): the
 // forward on one HIP stream, the backward on two (dZ chain; weight gradients + their reductions).
+//
+// ONE driver per direction for every model kind.  gi_ggnn_forward_ex / gi_ggnn_backward_phase decode their flags, open
+// the call context (struct Call, open_call: every argument check, the workspace plan, the Run, for a backward the slab
+// plan and the queue of deferred weight-gradient GEMMs, the views of the compact graph) and run the stages, each
+// written once on that context:
+//   forward   weights_prologue_fwd; per pass: pass_cells_fwd, the message step, gru_update_fwd; node_stacks_fwd,
+//             gather_fwd, graph_stacks_fwd, epilogue_fwd
+//   backward  await_prepack; bf3_prepare, tier2_selu_bwd, graph_stacks_bwd, gather_bwd, zero_row_colsums,
+//             node_stacks_bwd, graph_sum_bwd; pack_chains_bwd; per pass: pass_cells_bwd, gru_update_bwd, the message
+//             step; finish
+// A model kind plugs in at three places (and with its own argument checks in open_call):
+//   1. node_stacks: the per-kind list of node-level readout stacks (MNN: fAddNet1, fConnNet1; GGNN / AttentionGGNN also
+//      the gather's att / emb stacks);
+//   2. gather versus graph sum: gather_fwd / gather_bwd / graph_sum_bwd;
+//   3. the message step of a pass, one body per kind and direction: msg_fwd_ggnn / msg_bwd_ggnn (chain MLP + segmented
+//      sum, pass 0 on the class rows), msg_fwd_attggnn / msg_bwd_attggnn (edge chains + softmax), msg_fwd_mnn /
+//      msg_bwd_mnn (typed sum + one GEMM; msg_wgrad_mnn = the all-pass dW GEMM behind the passes).
+// Nothing else in the drivers and stages consults the kind (build_model, make_ws, plan_slabs and wcache_layout describe
+// it; open_call derives Call::nfam, the number of bond-type-grouped stack families, from it).  The order of HIP
+// runtime calls per stream is this file's contract: a stage may be rewritten, moved to the side stream or fused for
+// every kind at once, in one place.
 //
 // One call from Python enqueues every kernel of `SummationMPNN.forward`'s message passes and
 // `GGNN.readout` (gnn/summation_mpnn.py:128-149, gnn/mpnn.py:284-303) — no Python between
@@ -154,8 +175,40 @@ struct Ws {
     long long total;
 };
 
-bool chain_fits(const Mlp& q, int dx_cols);
-long long chain_image_floats(const Mlp& q, int groups, bool backward, long long* stride);
+// ---- resident-activation chains (gi_chain.hip) ---------------------------------------------------
+// The per-bond-type message / energy stacks run as ONE launch per direction when every layer fits
+// the chain kernel (<= GI_CHAIN_MAXL layers, widths 4..GI_CHAIN_MAXW); wider stacks take the
+// layer-by-layer GEMM path (same arithmetic, more launches).
+bool chain_fits(const Mlp& q, int dx_cols) {
+    if (q.layers() > GI_CHAIN_MAXL) return false;
+    for (int l = 0; l < q.layers(); ++l)
+        if (q.fan_in(l) < 4 || q.fan_in(l) > GI_CHAIN_MAXW || q.fan_out(l) < 4 ||
+            q.fan_out(l) > GI_CHAIN_MAXW)
+            return false;
+    return dx_cols >= 4 && dx_cols <= GI_CHAIN_MAXW;
+}
+
+// skeleton (dims only) of a stack's chain, forward or backward order (backward: every layer, the
+// first Linear's input gradient last)
+void chain_dims(gi_chain_params& c, const Mlp& q, int groups, bool backward) {
+    memset(&c, 0, sizeof(c));
+    const int L = q.layers();
+    c.nlayers = L; c.ngroups = groups; c.backward = backward ? 1 : 0;
+    for (int i = 0; i < L; ++i) {
+        const int l = backward ? L - 1 - i : i;
+        c.layer[i].K = backward ? q.fan_out(l) : q.fan_in(l);
+        c.layer[i].N = backward ? q.fan_in(l) : q.fan_out(l);
+    }
+}
+
+long long chain_image_floats(const Mlp& q, int groups, bool backward, long long* stride) {
+    gi_chain_params c;
+    chain_dims(c, q, groups, backward);
+    const long long n = gi_mlp_chain_image_floats(&c);
+    if (stride) *stride = n > 0 ? n / groups : 0;
+    return n > 0 ? n : 0;
+}
+
 // Round 6: EVERY weight-gradient problem of a backward can run as an fp16x2 launch.  Operands whose largest magnitude
 // no kernel publishes (GRU gate gradients, aggregated messages, h, the stacks' first / last layers, the graph-level
 // stacks at small batches) get it from one gi_absmax launch per hand-over, on the stream of the weight-gradient launches
@@ -467,13 +520,38 @@ void plan_slabs(const Model& m, int S, int E, const int* Et, SlabPlan& sp) {   /
 // ---- launch helpers -----------------------------------------------------------------------------
 struct Grp { int n; const int* off; int max_rows; const int* host_rows = nullptr; int dim_slot = 1; };   // dim_slot: which device dim holds the row-block height of a bounded chain launch (1: message rows, 2: pass-0 rows)   // n == 0: ungrouped; host_rows: per-group upper bounds (null: max_rows)
 
-struct SideStream;
+// ---- weight gradients on a second stream --------------------------------------------------------
+// The dZ chain is a sequence of short dependent launches that leave MFMA slots idle (few blocks per
+// CU, all in prologue / epilogue at the same time); the weight-gradient GEMMs only feed the final
+// slab reduction.  With a caller-provided side stream they are launched there, 8 problems at a
+// time, as soon as their operands exist (event from the main stream), and run in the gaps of the
+// chain; the main stream joins before gi_reduce_slabs.
+struct SideStream {
+    hipStream_t st;
+    int used;
+    static constexpr int NEV = 48;
+    // one pool per device (events belong to the device that is current when they are created);
+    // callers hold the GIL / call from one thread per process, like every entry point of this ABI
+    static hipEvent_t* pool() {
+        constexpr int MAXDEV = 16;
+        static hipEvent_t ev[MAXDEV][NEV];
+        static bool made[MAXDEV] = {};
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        dev = (dev >= 0 && dev < MAXDEV) ? dev : 0;
+        if (!made[dev]) {
+            for (hipEvent_t& e : ev[dev]) (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
+            made[dev] = true;
+        }
+        return ev[dev];
+    }
+    hipEvent_t next() { return pool()[used++ % NEV]; }
+};
 
 struct Run {
     hipStream_t st;
     const float* const* P;
     int rc;
-    SideStream* side = nullptr;    // optional second stream for the weight-gradient GEMMs
     float* img_f[2] = {nullptr, nullptr};   // packed chain weight images [msg, energy stack]; null: the
     float* img_b[2] = {nullptr, nullptr};   // stack runs layer by layer
     float* chain_amax[2] = {nullptr, nullptr};   // != null: the stack's chains run as fp16x2 (gi_chain.hip), images packed that way
@@ -532,9 +610,6 @@ struct Run {
     bool x2 = true;                         // fp16x2 on this call's 16-bit-pipe launches (GI_X2 and not GI_RUN_NO_X2 / GI_BWD_NO_X2)
     int* guard = nullptr;                   // gi_graph.x2_guard / x2_guard_host: the fp16x2 dynamic-range guard
     int* guard_host = nullptr;
-    struct SlabPlan* sp = nullptr; // backward only: where the wgrad slabs go and what they reduce to
-    float* slabs = nullptr;
-    float* const* grads = nullptr;
     bool ok() const { return rc == 0; }
     void chk(int r) { if (rc == 0 && r != 0) rc = r; }
 };
@@ -617,29 +692,6 @@ void linear_dgrad(Run& r, const int* widx, const Grp& g, int n_out,
     r.chk(gi_gemm(&p, r.st));
 }
 
-bool chain_fits(const Mlp& q, int dx_cols);
-void chain_fwd_params(gi_chain_params& c, const Run& r, float* ws, const Mlp* mlps, const Grp& g,
-                      const float* X, int ldx, const int* idx, int rows, const long long* acts,
-                      int ldh, float* final_dst, int ld_final);
-void mlp_forward(Run& r, float* ws, const Mlp* mlps, const Grp& g, const float* X, int ldx,
-                 const int* a_idx, int rows, const long long* acts, int ldh, float* final_dst,
-                 int ld_final) {
-    const int L = mlps[0].layers();
-    if (g.n && r.ok() && rows > 0 && r.img_f[mlps == r.eatt0 ? 1 : 0] && ldx >= gi_r4(mlps[0].in)) {
-        gi_chain_params c;                      // the whole stack in one resident-activation launch
-        chain_fwd_params(c, r, ws, mlps, g, X, ldx, a_idx, rows, acts, ldh, final_dst, ld_final);
-        r.chk(gi_mlp_chain(&c, 1, r.st));
-        return;
-    }
-    for (int l = 0; l < L; ++l) {
-        const float* src = (l == 0) ? X : ws + acts[l - 1];
-        float* dst = (l == L - 1) ? final_dst : ws + acts[l];
-        linear_fwd(r, mlps, l, g, src, l == 0 ? ldx : ldh, l == 0 ? a_idx : nullptr, rows, dst,
-                   l == L - 1 ? ld_final : ldh);
-        drop_site(r, mlps[0], l, r.pass, dst, l == L - 1 ? ld_final : ldh, rows, r.fshift);
-    }
-}
-
 // ---- batched ("horizontally fused") execution of sibling MLPs -----------------------------------
 // The readout's four node-level stacks (att, emb, fAddNet1, fConnNet1), its three graph-level
 // stacks (fAddNet2, fConnNet2, fTermNet2) and the two GRU projections are mutually independent;
@@ -696,6 +748,49 @@ struct Deferred {
     unsigned char want_amax[96];     // fp16x2 problem whose a_amax (bit 0) / b_amax (bit 1) cell comes from the pool at launch time
     int n = 0;
     gi_gemm_params& next() { gemm_defaults(p[n]); nw[n] = 0; want_amax[n] = 0; return p[n++]; }
+};
+
+// ---- the call context ---------------------------------------------------------------------------
+// Everything one forward or backward call of any model kind works on.  open_call fills it (and makes every argument
+// check); the helpers and the stage functions below take it instead of threading its members through their
+// parameter lists.
+struct Call {
+    Model m;
+    const gi_graph* g = nullptr;
+    gi_compact_layout_t L;
+    Ws w;
+    float* ws = nullptr;
+    Run r;
+    // the caller's logits [B (2 B in dropout mode: rows [B, 2 B) take the logits' factors), ldout]: the forward's
+    // `out`, the backward's y_out, and the backward's d_out [B, lddout]
+    float* out = nullptr;
+    const float* y_out = nullptr;
+    const float* d_out = nullptr;
+    int ldout = 0, lddout = 0;
+    // backward: where the weight-gradient slabs go and what they reduce to, the queued weight-gradient GEMMs
+    SlabPlan sp;
+    Deferred dq;
+    float* slabs = nullptr;
+    float* const* grads = nullptr;
+    float *dh = nullptr, *dh2 = nullptr;      // d h of the pass being differentiated / of the pass below (swapped per pass)
+    float* dh_sib[3] = {nullptr, nullptr, nullptr};   // the readout's other contributions to the last pass's d h (open_call)
+    const float *scat0 = nullptr, *scat1 = nullptr;   // a pass's d h scatter that rides in the next gate backward launch
+    // optional second stream (st == null: none): the backward's weight-gradient GEMMs, the forward's weights-only work
+    SideStream side{nullptr, 0};
+    bool has_side() const { return side.st != nullptr; }
+    // views of the compact graph and of the model that every stage reads
+    const int *seg_off = nullptr, *src_off = nullptr, *cidx = nullptr, *mask = nullptr, *type_off = nullptr;
+    int R = 0, NA = 0, NC = 0;
+    int nfam = 0;                             // bond-type-grouped stack families: 0 (MNN), 1 (msg), 2 (msg, energy)
+    bool attn = false;
+    Grp bytype{}, bytype0{};                  // message rows / pass-0 class rows by bond type
+    long long out_fshift = 0;                 // dropout mode: logits -> their factors
+    // forward: gi_graph.wcache, the events of the weights-only prologue, the message stacks' amax cells, the row cache
+    Wc wc;
+    float* wcache = nullptr;
+    hipEvent_t cells_ready = nullptr, packed = nullptr, msg_cells_ready = nullptr;
+    float* msg_cells_base[2] = {nullptr, nullptr};
+    int* p0c = nullptr;                       // != null: the pass-0 row cache is in use
 };
 
 void flush_batch(Run& r, Batch& b, bool wgrad) {
@@ -775,8 +870,6 @@ void add_dgrad(Batch& b, Run& r, int widx, int n_out, int n_in, int ncols, const
     maybe_split_k(b, r, p);
 }
 
-void flush_deferred(Run& r, Deferred& q);
-void kick_deferred(Run& r, Deferred& q, SideStream* side, bool all);
 // queued weight-gradient problems that make up one hand-over to the side stream (one launch)
 constexpr int WGRAD_KICK_N = 8;
 // node rows up to which no weight-gradient launch goes to the side stream beside the node-level dgrad launches
@@ -791,10 +884,148 @@ gi_reduce_desc reduce_desc(const SlabEntry& e, float* slabs, float* const* grads
     return q;
 }
 
-void defer_wgrad(Run& r, Deferred& q, SlabPlan& sp, float* slabs, const int* widx, const Grp& g,
-                 const float* dZ, int lddz, const float* X, int ldx, const int* b_idx, int rows,
-                 const float* dz_amax = nullptr, const float* x_amax = nullptr) {
-    if (q.n == 96) flush_deferred(r, q);          // list full (very deep configurations only)
+// The amax cells the queued fp16x2 problems still lack (Deferred::want_amax): one cell of the pool per distinct operand
+// tensor of this backward call, filled by gi_absmax launches on `st` in front of the GEMMs that read them.  A problem
+// the pool has no cell left for goes back to the fp32 MFMA (its slab count stays the plan's).
+void resolve_pool_amax(Run& r, gi_gemm_params* p, const unsigned char* want, int n, hipStream_t st) {
+    Run::AmaxPool& pool = r.pool;
+    gi_absmax_desc ad[GI_ABSMAX_MAX];
+    int na = 0;
+    auto flush = [&]() { if (na && r.ok()) r.chk(gi_absmax(ad, na, st)); na = 0; };
+    auto cell_of = [&](const float* x, int rows, int cols, int ld) -> float* {
+        for (int i = 0; i < pool.used; ++i) {
+            const Run::AmaxPool::Key& k = pool.have[i];
+            if (k.x == x && k.rows == rows && k.cols == cols && k.ld == ld) return k.cell;
+        }
+        if (!pool.base || pool.used >= AMAX_POOL_CELLS) return nullptr;
+        if (!pool.zeroed) {
+            r.chk((int)hipMemsetAsync(pool.base, 0, sizeof(float) * AMAX_POOL_CELLS * GI_AMAX_WORDS, st));
+            pool.zeroed = true; pool.st = st;
+        }
+        float* cell = pool.base + (long long)pool.used * GI_AMAX_WORDS;
+        pool.have[pool.used++] = Run::AmaxPool::Key{x, rows, cols, ld, cell};
+        if (na == GI_ABSMAX_MAX) flush();
+        ad[na].x = x; ad[na].rows = rows; ad[na].cols = cols; ad[na].ld = ld; ad[na].out = cell;
+        ++na;
+        return cell;
+    };
+    bool any = false;
+    for (int i = 0; i < n; ++i) any |= want && want[i];
+    if (!any) return;
+    if (pool.zeroed && pool.st != st) {            // (a second stream joins: order it behind the pool's kernels so far)
+        hipEvent_t e = nullptr;
+        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess) {
+            r.chk((int)hipEventRecord(e, pool.st));
+            r.chk((int)hipStreamWaitEvent(st, e, 0));
+            (void)hipEventDestroy(e);              // (destruction is deferred until the event has completed)
+        }
+        pool.st = st;
+    }
+    for (int i = 0; i < n; ++i) {
+        if (!want[i]) continue;
+        gi_gemm_params& q = p[i];
+        const int bcols = q.ones_col >= 0 ? q.ones_col : q.N;
+        if ((want[i] & 1) && !q.a_amax) q.a_amax = cell_of(q.A, q.K, q.M, q.lda);       // dZ [rows, n_out]
+        if ((want[i] & 2) && !q.b_amax) q.b_amax = cell_of(q.B, q.K, bcols, q.ldb);     // X  [rows, n_in]
+        if (!q.a_amax || !q.b_amax) {              // pool exhausted
+            q.flags &= ~(GI_GEMM_BF3 | GI_GEMM_X2); q.a_amax = q.b_amax = nullptr;
+        }
+    }
+    flush();
+}
+
+// consecutive queued problems, up to 8 per launch; the bf16x3 ones (one workgroup per CU, equal tiles) are packed
+// separately, biggest first, into launches of about one round of the device
+void launch_wgrad_batches(Call& c, int n, hipStream_t st) {
+    Run& r = c.r; const Deferred& dq = c.dq;
+    gi_gemm_params p[96];
+    for (int i = 0; i < n; ++i) p[i] = dq.p[i];
+    resolve_pool_amax(r, p, dq.want_amax, n, st);
+    // b3[0]: bf16x3; fp16x2: b3[1 + 1 (gathered B)] (a launch is ONE kernel instantiation)
+    gi_gemm_params rest[96], b3[3][96];
+    int nr = 0, n3[3] = {0, 0, 0};
+    for (int i = 0; i < n; ++i) {
+        if (p[i].flags & GI_GEMM_BF3) {
+            const int x = (p[i].flags & GI_GEMM_X2) ? 1 + (p[i].b_idx ? 1 : 0) : 0;
+            b3[x][n3[x]++] = p[i];
+        }
+        else rest[nr++] = p[i];
+    }
+    auto tiles = [](const gi_gemm_params& q) {
+        int zs = q.nsplit;
+        if (q.ngroups) { zs = 0; for (int g = 0; g < q.ngroups; ++g) zs += q.gsplit[g]; }
+        return gi_cdiv(q.M, 128) * gi_cdiv(q.N, 256) * zs;
+    };
+    static const int cus = [] {
+        int dev = 0, c = 0;
+        (void)hipGetDevice(&dev);
+        if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c <= 0) c = 256;
+        return c;
+    }();
+    for (int x = 2; x >= 0; --x) {
+        gi_gemm_params* q = b3[x];
+        for (int i = 1; i < n3[x]; ++i)                           // stable insertion sort, most tiles first
+            for (int j = i; j > 0 && tiles(q[j]) > tiles(q[j - 1]); --j) std::swap(q[j], q[j - 1]);
+        for (int base = 0; base < n3[x] && r.ok();) {
+            int k = 0, t = 0;
+            while (base + k < n3[x] && k < 8 && (k == 0 || t + tiles(q[base + k]) <= cus)) { t += tiles(q[base + k]); ++k; }
+            r.chk(gi_gemm_batch(q + base, k, st));
+            base += k;
+        }
+    }
+    for (int base = 0; base < nr && r.ok(); base += 8) r.chk(gi_gemm_batch(rest + base, std::min(8, nr - base), st));   // (64x64 tiles)
+}
+
+void flush_deferred(Call& c) {
+    launch_wgrad_batches(c, c.dq.n, c.r.st);
+    c.dq.n = 0;
+}
+
+// launch every complete batch of 8 queued problems (all of them when `all`) on the side stream
+void kick_deferred(Call& c, bool all) {
+    Run& r = c.r; Deferred& q = c.dq;
+    SideStream* const side = &c.side;
+    if (!c.has_side() || !r.ok()) return;
+    const int n = all ? q.n : (q.n / WGRAD_KICK_N) * WGRAD_KICK_N;
+    if (n == 0) return;
+    hipEvent_t ready = side->next();
+    r.chk((int)hipEventRecord(ready, r.st));
+    r.chk((int)hipStreamWaitEvent(side->st, ready, 0));
+    launch_wgrad_batches(c, n, side->st);
+    // parameters whose last slab has just been queued: reduce them right behind, on the side stream
+    // too, so that only the final pass's gradients are left for the end of the backward
+    gi_reduce_desc descs[96 * GI_MAX_GROUPS > MAXPARAMS ? MAXPARAMS : 96 * GI_MAX_GROUPS];
+    int nd = 0;
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < q.nw[i]; ++k) {
+            SlabEntry& e = c.sp.e[q.widx[i][k]];
+            if (++e.launched == e.calls && !e.reduced && nd < (int)(sizeof(descs) / sizeof(descs[0]))) {
+                e.reduced = 1;
+                descs[nd++] = reduce_desc(e, c.slabs, c.grads, q.widx[i][k]);
+            }
+        }
+    if (nd && r.ok()) r.chk(gi_reduce_slabs(descs, nd, side->st));
+    for (int i = n; i < q.n; ++i) {
+        q.p[i - n] = q.p[i];
+        q.nw[i - n] = q.nw[i];
+        q.want_amax[i - n] = q.want_amax[i];
+        for (int k = 0; k < q.nw[i]; ++k) q.widx[i - n][k] = q.widx[i][k];
+    }
+    q.n -= n;
+}
+
+void join_side(Call& c) {
+    Run& r = c.r;
+    if (!c.has_side() || !r.ok()) return;
+    hipEvent_t done = c.side.next();
+    r.chk((int)hipEventRecord(done, c.side.st));
+    r.chk((int)hipStreamWaitEvent(r.st, done, 0));
+}
+
+void defer_wgrad(Call& c, const int* widx, const Grp& g, const float* dZ, int lddz, const float* X, int ldx,
+                 const int* b_idx, int rows, const float* dz_amax = nullptr, const float* x_amax = nullptr) {
+    Run& r = c.r; Deferred& q = c.dq; SlabPlan& sp = c.sp; float* const slabs = c.slabs;
+    if (q.n == 96) flush_deferred(c);             // list full (very deep configurations only)
     gi_gemm_params& p = q.next();
     SlabEntry& e0 = sp.e[widx[0]];
     p.A = dZ; p.lda = lddz; p.a_major = 1;
@@ -851,172 +1082,11 @@ void defer_wgrad(Run& r, Deferred& q, SlabPlan& sp, float* slabs, const int* wid
         q.widx[slot][0] = widx[0];
         q.nw[slot] = 1;
     }
-    if (r.side && q.n >= WGRAD_KICK_N && !r.hold_kicks) kick_deferred(r, q, r.side, false);
+    if (c.has_side() && q.n >= WGRAD_KICK_N && !r.hold_kicks) kick_deferred(c, false);
 }
 
-// The amax cells the queued fp16x2 problems still lack (Deferred::want_amax): one cell of the pool per distinct operand
-// tensor of this backward call, filled by gi_absmax launches on `st` in front of the GEMMs that read them.  A problem
-// the pool has no cell left for goes back to the fp32 MFMA (its slab count stays the plan's).
-void resolve_pool_amax(Run& r, gi_gemm_params* p, const unsigned char* want, int n, hipStream_t st) {
-    Run::AmaxPool& pool = r.pool;
-    gi_absmax_desc ad[GI_ABSMAX_MAX];
-    int na = 0;
-    auto flush = [&]() { if (na && r.ok()) r.chk(gi_absmax(ad, na, st)); na = 0; };
-    auto cell_of = [&](const float* x, int rows, int cols, int ld) -> float* {
-        for (int i = 0; i < pool.used; ++i) {
-            const Run::AmaxPool::Key& k = pool.have[i];
-            if (k.x == x && k.rows == rows && k.cols == cols && k.ld == ld) return k.cell;
-        }
-        if (!pool.base || pool.used >= AMAX_POOL_CELLS) return nullptr;
-        if (!pool.zeroed) {
-            r.chk((int)hipMemsetAsync(pool.base, 0, sizeof(float) * AMAX_POOL_CELLS * GI_AMAX_WORDS, st));
-            pool.zeroed = true; pool.st = st;
-        }
-        float* cell = pool.base + (long long)pool.used * GI_AMAX_WORDS;
-        pool.have[pool.used++] = Run::AmaxPool::Key{x, rows, cols, ld, cell};
-        if (na == GI_ABSMAX_MAX) flush();
-        ad[na].x = x; ad[na].rows = rows; ad[na].cols = cols; ad[na].ld = ld; ad[na].out = cell;
-        ++na;
-        return cell;
-    };
-    bool any = false;
-    for (int i = 0; i < n; ++i) any |= want && want[i];
-    if (!any) return;
-    if (pool.zeroed && pool.st != st) {            // (a second stream joins: order it behind the pool's kernels so far)
-        hipEvent_t e = nullptr;
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess) {
-            r.chk((int)hipEventRecord(e, pool.st));
-            r.chk((int)hipStreamWaitEvent(st, e, 0));
-            (void)hipEventDestroy(e);              // (destruction is deferred until the event has completed)
-        }
-        pool.st = st;
-    }
-    for (int i = 0; i < n; ++i) {
-        if (!want[i]) continue;
-        gi_gemm_params& q = p[i];
-        const int bcols = q.ones_col >= 0 ? q.ones_col : q.N;
-        if ((want[i] & 1) && !q.a_amax) q.a_amax = cell_of(q.A, q.K, q.M, q.lda);       // dZ [rows, n_out]
-        if ((want[i] & 2) && !q.b_amax) q.b_amax = cell_of(q.B, q.K, bcols, q.ldb);     // X  [rows, n_in]
-        if (!q.a_amax || !q.b_amax) {              // pool exhausted
-            q.flags &= ~(GI_GEMM_BF3 | GI_GEMM_X2); q.a_amax = q.b_amax = nullptr;
-        }
-    }
-    flush();
-}
-
-// consecutive queued problems, up to 8 per launch; the bf16x3 ones (one workgroup per CU, equal tiles) are packed
-// separately, biggest first, into launches of about one round of the device
-void launch_wgrad_batches(Run& r, Deferred& dq, int n, hipStream_t st) {
-    gi_gemm_params p[96];
-    for (int i = 0; i < n; ++i) p[i] = dq.p[i];
-    resolve_pool_amax(r, p, dq.want_amax, n, st);
-    // b3[0]: bf16x3; fp16x2: b3[1 + 1 (gathered B)] (a launch is ONE kernel instantiation)
-    gi_gemm_params rest[96], b3[3][96];
-    int nr = 0, n3[3] = {0, 0, 0};
-    for (int i = 0; i < n; ++i) {
-        if (p[i].flags & GI_GEMM_BF3) {
-            const int x = (p[i].flags & GI_GEMM_X2) ? 1 + (p[i].b_idx ? 1 : 0) : 0;
-            b3[x][n3[x]++] = p[i];
-        }
-        else rest[nr++] = p[i];
-    }
-    auto tiles = [](const gi_gemm_params& q) {
-        int zs = q.nsplit;
-        if (q.ngroups) { zs = 0; for (int g = 0; g < q.ngroups; ++g) zs += q.gsplit[g]; }
-        return gi_cdiv(q.M, 128) * gi_cdiv(q.N, 256) * zs;
-    };
-    static const int cus = [] {
-        int dev = 0, c = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c <= 0) c = 256;
-        return c;
-    }();
-    for (int x = 2; x >= 0; --x) {
-        gi_gemm_params* q = b3[x];
-        for (int i = 1; i < n3[x]; ++i)                           // stable insertion sort, most tiles first
-            for (int j = i; j > 0 && tiles(q[j]) > tiles(q[j - 1]); --j) std::swap(q[j], q[j - 1]);
-        for (int base = 0; base < n3[x] && r.ok();) {
-            int k = 0, t = 0;
-            while (base + k < n3[x] && k < 8 && (k == 0 || t + tiles(q[base + k]) <= cus)) { t += tiles(q[base + k]); ++k; }
-            r.chk(gi_gemm_batch(q + base, k, st));
-            base += k;
-        }
-    }
-    for (int base = 0; base < nr && r.ok(); base += 8) r.chk(gi_gemm_batch(rest + base, std::min(8, nr - base), st));   // (64x64 tiles)
-}
-
-void flush_deferred(Run& r, Deferred& q) {
-    launch_wgrad_batches(r, q, q.n, r.st);
-    q.n = 0;
-}
-
-// ---- weight gradients on a second stream --------------------------------------------------------
-// The dZ chain is a sequence of short dependent launches that leave MFMA slots idle (few blocks per
-// CU, all in prologue / epilogue at the same time); the weight-gradient GEMMs only feed the final
-// slab reduction.  With a caller-provided side stream they are launched there, 8 problems at a
-// time, as soon as their operands exist (event from the main stream), and run in the gaps of the
-// chain; the main stream joins before gi_reduce_slabs.
-struct SideStream {
-    hipStream_t st;
-    int used;
-    static constexpr int NEV = 48;
-    // one pool per device (events belong to the device that is current when they are created);
-    // callers hold the GIL / call from one thread per process, like every entry point of this ABI
-    static hipEvent_t* pool() {
-        constexpr int MAXDEV = 16;
-        static hipEvent_t ev[MAXDEV][NEV];
-        static bool made[MAXDEV] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        dev = (dev >= 0 && dev < MAXDEV) ? dev : 0;
-        if (!made[dev]) {
-            for (hipEvent_t& e : ev[dev]) (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
-            made[dev] = true;
-        }
-        return ev[dev];
-    }
-    hipEvent_t next() { return pool()[used++ % NEV]; }
-};
-
-// launch every complete batch of 8 queued problems (all of them when `all`) on the side stream
-void kick_deferred(Run& r, Deferred& q, SideStream* side, bool all) {
-    if (!side || !r.ok()) return;
-    const int n = all ? q.n : (q.n / WGRAD_KICK_N) * WGRAD_KICK_N;
-    if (n == 0) return;
-    hipEvent_t ready = side->next();
-    r.chk((int)hipEventRecord(ready, r.st));
-    r.chk((int)hipStreamWaitEvent(side->st, ready, 0));
-    launch_wgrad_batches(r, q, n, side->st);
-    // parameters whose last slab has just been queued: reduce them right behind, on the side stream
-    // too, so that only the final pass's gradients are left for the end of the backward
-    gi_reduce_desc descs[96 * GI_MAX_GROUPS > MAXPARAMS ? MAXPARAMS : 96 * GI_MAX_GROUPS];
-    int nd = 0;
-    for (int i = 0; i < n; ++i)
-        for (int k = 0; k < q.nw[i]; ++k) {
-            SlabEntry& e = r.sp->e[q.widx[i][k]];
-            if (++e.launched == e.calls && !e.reduced && nd < (int)(sizeof(descs) / sizeof(descs[0]))) {
-                e.reduced = 1;
-                descs[nd++] = reduce_desc(e, r.slabs, r.grads, q.widx[i][k]);
-            }
-        }
-    if (nd && r.ok()) r.chk(gi_reduce_slabs(descs, nd, side->st));
-    for (int i = n; i < q.n; ++i) {
-        q.p[i - n] = q.p[i];
-        q.nw[i - n] = q.nw[i];
-        q.want_amax[i - n] = q.want_amax[i];
-        for (int k = 0; k < q.nw[i]; ++k) q.widx[i - n][k] = q.widx[i][k];
-    }
-    q.n -= n;
-}
-
-void join_side(Run& r, SideStream* side) {
-    if (!side || !r.ok()) return;
-    hipEvent_t done = side->next();
-    r.chk((int)hipEventRecord(done, side->st));
-    r.chk((int)hipStreamWaitEvent(r.st, done, 0));
-}
-
-void mlp_jobs_forward(Run& r, float* ws, const MlpJob* jobs, int n) {
+void mlp_jobs_forward(Call& c, const MlpJob* jobs, int n) {
+    Run& r = c.r; float* const ws = c.ws;
     int maxL = 0;
     for (int j = 0; j < n; ++j) maxL = std::max(maxL, jobs[j].mlp->layers());
     for (int l = 0; l < maxL; ++l) {
@@ -1046,8 +1116,8 @@ void mlp_jobs_forward(Run& r, float* ws, const MlpJob* jobs, int n) {
 // Layers are aligned from the END (step s handles layer L_j-1-s of job j).  dZ of hidden layer l
 // goes to the job's dz buffer l; first-layer input gradients go to the jobs' (distinct) dX;
 // weight gradients are deferred.
-void mlp_jobs_backward(Run& r, float* ws, SlabPlan& sp, float* slabs, Deferred& dq,
-                       const MlpJob* jobs, int n) {
+void mlp_jobs_backward(Call& c, const MlpJob* jobs, int n) {
+    Run& r = c.r; float* const ws = c.ws;
     int maxL = 0;
     const Grp none{0, nullptr, 0};
     for (int j = 0; j < n; ++j) maxL = std::max(maxL, jobs[j].mlp->layers());
@@ -1061,8 +1131,7 @@ void mlp_jobs_backward(Run& r, float* ws, SlabPlan& sp, float* slabs, Deferred& 
             const int lddz = (l == L - 1) ? q.ldz : q.ldh;
             const float* Xl = (l == 0) ? q.X : ws + q.acts[l - 1];
             const int widx = q.mlp->w(l);
-            defer_wgrad(r, dq, sp, slabs, &widx, none, dZ, lddz, Xl, l == 0 ? q.ldx : q.ldh, nullptr,
-                        q.rows);
+            defer_wgrad(c, &widx, none, dZ, lddz, Xl, l == 0 ? q.ldx : q.ldh, nullptr, q.rows);
             if (l > 0) {
                 add_dgrad(bd, r, widx, q.mlp->fan_out(l), q.mlp->fan_in(l), q.mlp->fan_in(l), dZ, lddz,
                           q.rows, ws + q.dzs[l - 1], q.ldh, ws + q.acts[l - 1], q.ldh, false, q.mlp->w(l - 1));
@@ -1073,96 +1142,6 @@ void mlp_jobs_backward(Run& r, float* ws, SlabPlan& sp, float* slabs, Deferred& 
         }
         flush_batch(r, bd, false);
     }
-}
-
-int chain_bwd_params(gi_chain_params& c, const Run& r, float* ws, const Mlp* mlps, const Grp& g,
-                     const float* Zlast, int ldz, int rows, const long long* acts,
-                     const long long* dzs, int ldh, float* dX, int lddx, int dx_cols);
-void defer_stack_wgrads(Run& r, float* ws, SlabPlan& sp, float* slabs, Deferred& dq, const Mlp* mlps,
-                        const Grp& g, const float* X, int ldx, const int* a_idx, int rows,
-                        const long long* acts, const long long* dzs, int ldh, const float* Zlast,
-                        int ldz);
-
-void join_side(Run& r, SideStream* side);
-
-// The bond-type-grouped message MLP: dZ chain now, weight gradients deferred.
-// Zlast of a message stack = selu'(m) * (segmented sum of `vals` rows over the message CSR), formed in
-// place over the stack's forward output by its own launch (gi_seg_sum_dselu_f) in front of the dZ chain
-// (folding it into the chain launch was built and measured a tie in round 2: tools/experiments/README.md)
-struct SegIn { const float* vals; int ld; const int* idx; const int* off; };
-
-void seg_launch(Run& r, const SegIn* seg, int rows, int cols, float* y, int ldy) {
-    if (seg && seg->vals && r.ok())
-        r.chk(gi_seg_sum_dselu_f(seg->vals, seg->ld, seg->idx, seg->off, rows, cols, y, ldy, r.fshift, r.st));
-}
-
-void msg_backward(Run& r, float* ws, SlabPlan& sp, float* slabs, Deferred& dq, const Mlp* mlps,
-                  const Grp& g, const float* X, int ldx, const int* a_idx, int rows,
-                  const long long* acts, const long long* dzs, int ldh, const float* Zlast, int ldz,
-                  float* dX, int lddx, int dx_cols, const SegIn* seg = nullptr) {
-    const int L = mlps[0].layers();
-    if (g.n && r.ok() && rows > 0 && r.img_b[mlps == r.eatt0 ? 1 : 0] && dx_cols == mlps[0].in &&
-        ldz >= gi_r4(mlps[0].out)) {
-        gi_chain_params c;                      // the whole dZ chain in one launch, then the wgrads
-        seg_launch(r, seg, rows, mlps[0].out, const_cast<float*>(Zlast), ldz);
-        if (chain_bwd_params(c, r, ws, mlps, g, Zlast, ldz, rows, acts, dzs, ldh, dX, lddx, dx_cols))
-            r.chk(gi_mlp_chain(&c, 1, r.st));
-        r.hold_kicks = r.p0_on_main;
-        defer_stack_wgrads(r, ws, sp, slabs, dq, mlps, g, X, ldx, a_idx, rows, acts, dzs, ldh, Zlast,
-                           ldz);
-        return;
-    }
-    seg_launch(r, seg, rows, mlps[0].out, const_cast<float*>(Zlast), ldz);
-    for (int l = L - 1; l >= 0; --l) {
-        const float* dZ = (l == L - 1) ? Zlast : ws + dzs[l];
-        const int lddz = (l == L - 1) ? ldz : ldh;
-        const float* Xl = (l == 0) ? X : ws + acts[l - 1];
-        int widx[GI_MAX_GROUPS];
-        for (int t = 0; t < g.n; ++t) widx[t] = mlps[t].w(l);
-        defer_wgrad(r, dq, sp, slabs, widx, g, dZ, lddz, Xl, l == 0 ? ldx : ldh,
-                    l == 0 ? a_idx : nullptr, rows);
-        const Mlp& q = mlps[0];
-        if (l > 0)
-            linear_dgrad(r, widx, g, q.fan_out(l), q.fan_in(l), q.fan_in(l), dZ, lddz, rows,
-                         ws + dzs[l - 1], ldh, ws + acts[l - 1], ldh, false);
-        else if (dX)
-            linear_dgrad(r, widx, g, q.fan_out(0), q.fan_in(0), dx_cols, dZ, lddz, rows, dX,
-                         lddx, nullptr, 0, false);
-    }
-}
-
-// ---- resident-activation chains (gi_chain.hip) ---------------------------------------------------
-// The per-bond-type message / energy stacks run as ONE launch per direction when every layer fits
-// the chain kernel (<= GI_CHAIN_MAXL layers, widths 4..GI_CHAIN_MAXW); wider stacks take the
-// layer-by-layer GEMM path above (same arithmetic, more launches).
-bool chain_fits(const Mlp& q, int dx_cols) {
-    if (q.layers() > GI_CHAIN_MAXL) return false;
-    for (int l = 0; l < q.layers(); ++l)
-        if (q.fan_in(l) < 4 || q.fan_in(l) > GI_CHAIN_MAXW || q.fan_out(l) < 4 ||
-            q.fan_out(l) > GI_CHAIN_MAXW)
-            return false;
-    return dx_cols >= 4 && dx_cols <= GI_CHAIN_MAXW;
-}
-
-// skeleton (dims only) of a stack's chain, forward or backward order (backward: every layer, the
-// first Linear's input gradient last)
-void chain_dims(gi_chain_params& c, const Mlp& q, int groups, bool backward) {
-    memset(&c, 0, sizeof(c));
-    const int L = q.layers();
-    c.nlayers = L; c.ngroups = groups; c.backward = backward ? 1 : 0;
-    for (int i = 0; i < L; ++i) {
-        const int l = backward ? L - 1 - i : i;
-        c.layer[i].K = backward ? q.fan_out(l) : q.fan_in(l);
-        c.layer[i].N = backward ? q.fan_in(l) : q.fan_out(l);
-    }
-}
-
-long long chain_image_floats(const Mlp& q, int groups, bool backward, long long* stride) {
-    gi_chain_params c;
-    chain_dims(c, q, groups, backward);
-    const long long n = gi_mlp_chain_image_floats(&c);
-    if (stride) *stride = n > 0 ? n / groups : 0;
-    return n > 0 ? n : 0;
 }
 
 // write the packed weight image of the grouped stacks `mlps` (once per forward / backward call)
@@ -1184,9 +1163,9 @@ void chain_groups(gi_chain_params& c, const Grp& g, int rows) {
 }
 
 // Y = MLP(X[idx]) for the grouped stacks `mlps`; hidden activations -> acts, last layer -> final_dst
-void chain_fwd_params(gi_chain_params& c, const Run& r, float* ws, const Mlp* mlps, const Grp& g,
-                      const float* X, int ldx, const int* idx, int rows, const long long* acts,
-                      int ldh, float* final_dst, int ld_final) {
+void chain_fwd_params(gi_chain_params& c, const Call& k, const Mlp* mlps, const Grp& g, const float* X, int ldx,
+                      const int* idx, int rows, const long long* acts, int ldh, float* final_dst, int ld_final) {
+    const Run& r = k.r; float* const ws = k.ws;
     memset(&c, 0, sizeof(c));
     c.image = r.img_f[mlps == r.eatt0 ? 1 : 0];
     const Mlp& q = mlps[0];
@@ -1213,12 +1192,32 @@ void chain_fwd_params(gi_chain_params& c, const Run& r, float* ws, const Mlp* ml
     }
 }
 
+void mlp_forward(Call& c, const Mlp* mlps, const Grp& g, const float* X, int ldx, const int* a_idx, int rows,
+                 const long long* acts, int ldh, float* final_dst, int ld_final) {
+    Run& r = c.r; float* const ws = c.ws;
+    const int L = mlps[0].layers();
+    if (g.n && r.ok() && rows > 0 && r.img_f[mlps == r.eatt0 ? 1 : 0] && ldx >= gi_r4(mlps[0].in)) {
+        gi_chain_params cp;                     // the whole stack in one resident-activation launch
+        chain_fwd_params(cp, c, mlps, g, X, ldx, a_idx, rows, acts, ldh, final_dst, ld_final);
+        r.chk(gi_mlp_chain(&cp, 1, r.st));
+        return;
+    }
+    for (int l = 0; l < L; ++l) {
+        const float* src = (l == 0) ? X : ws + acts[l - 1];
+        float* dst = (l == L - 1) ? final_dst : ws + acts[l];
+        linear_fwd(r, mlps, l, g, src, l == 0 ? ldx : ldh, l == 0 ? a_idx : nullptr, rows, dst,
+                   l == L - 1 ? ld_final : ldh);
+        drop_site(r, mlps[0], l, r.pass, dst, l == L - 1 ? ld_final : ldh, rows, r.fshift);
+    }
+}
+
 // dZ chain of the same stacks: Zlast = dZ of the last layer; dZ of hidden layer l -> dzs[l]; the
 // first layer's input gradient (dx_cols leading columns) -> dX when dX != null.  Returns the number
 // of chain layers (0: nothing to launch).
-int chain_bwd_params(gi_chain_params& c, const Run& r, float* ws, const Mlp* mlps, const Grp& g,
-                     const float* Zlast, int ldz, int rows, const long long* acts,
-                     const long long* dzs, int ldh, float* dX, int lddx, int dx_cols) {
+int chain_bwd_params(gi_chain_params& c, const Call& k, const Mlp* mlps, const Grp& g, const float* Zlast, int ldz,
+                     int rows, const long long* acts, const long long* dzs, int ldh, float* dX, int lddx,
+                     int dx_cols) {
+    const Run& r = k.r; float* const ws = k.ws;
     memset(&c, 0, sizeof(c));
     const Mlp& q = mlps[0];
     const int L = q.layers();
@@ -1249,10 +1248,9 @@ int chain_bwd_params(gi_chain_params& c, const Run& r, float* ws, const Mlp* mlp
 }
 
 // weight gradients of every layer of a grouped stack (deferred), after its dZ chain was enqueued
-void defer_stack_wgrads(Run& r, float* ws, SlabPlan& sp, float* slabs, Deferred& dq, const Mlp* mlps,
-                        const Grp& g, const float* X, int ldx, const int* a_idx, int rows,
-                        const long long* acts, const long long* dzs, int ldh, const float* Zlast,
-                        int ldz) {
+void defer_stack_wgrads(Call& c, const Mlp* mlps, const Grp& g, const float* X, int ldx, const int* a_idx, int rows,
+                        const long long* acts, const long long* dzs, int ldh, const float* Zlast, int ldz) {
+    Run& r = c.r; float* const ws = c.ws;
     const int L = mlps[0].layers();
     for (int l = L - 1; l >= 0; --l) {
         const float* dZ = (l == L - 1) ? Zlast : ws + dzs[l];
@@ -1261,16 +1259,57 @@ void defer_stack_wgrads(Run& r, float* ws, SlabPlan& sp, float* slabs, Deferred&
         int widx[GI_MAX_GROUPS];
         for (int t = 0; t < g.n; ++t) widx[t] = mlps[t].w(l);
         float* const cells = g.dim_slot != 2 ? r.msg_cells[mlps == r.eatt0 ? 1 : 0] : nullptr;
-        defer_wgrad(r, dq, sp, slabs, widx, g, dZ, lddz, Xl, l == 0 ? ldx : ldh,
-                    l == 0 ? a_idx : nullptr, rows, msg_cell(cells, 1, l), msg_cell(cells, 0, l));
+        defer_wgrad(c, widx, g, dZ, lddz, Xl, l == 0 ? ldx : ldh, l == 0 ? a_idx : nullptr, rows,
+                    msg_cell(cells, 1, l), msg_cell(cells, 0, l));
+    }
+}
+
+// The bond-type-grouped message MLP: dZ chain now, weight gradients deferred.
+// Zlast of a message stack = selu'(m) * (segmented sum of `vals` rows over the message CSR), formed in
+// place over the stack's forward output by its own launch (gi_seg_sum_dselu_f) in front of the dZ chain
+// (folding it into the chain launch was built and measured a tie in round 2: tools/experiments/README.md)
+struct SegIn { const float* vals; int ld; const int* idx; const int* off; };
+
+void seg_launch(Run& r, const SegIn* seg, int rows, int cols, float* y, int ldy) {
+    if (seg && seg->vals && r.ok())
+        r.chk(gi_seg_sum_dselu_f(seg->vals, seg->ld, seg->idx, seg->off, rows, cols, y, ldy, r.fshift, r.st));
+}
+
+void msg_backward(Call& c, const Mlp* mlps, const Grp& g, const float* X, int ldx, const int* a_idx, int rows,
+                  const long long* acts, const long long* dzs, int ldh, const float* Zlast, int ldz, float* dX,
+                  int lddx, int dx_cols, const SegIn* seg = nullptr) {
+    Run& r = c.r; float* const ws = c.ws;
+    const int L = mlps[0].layers();
+    if (g.n && r.ok() && rows > 0 && r.img_b[mlps == r.eatt0 ? 1 : 0] && dx_cols == mlps[0].in &&
+        ldz >= gi_r4(mlps[0].out)) {
+        gi_chain_params cp;                     // the whole dZ chain in one launch, then the wgrads
+        seg_launch(r, seg, rows, mlps[0].out, const_cast<float*>(Zlast), ldz);
+        if (chain_bwd_params(cp, c, mlps, g, Zlast, ldz, rows, acts, dzs, ldh, dX, lddx, dx_cols))
+            r.chk(gi_mlp_chain(&cp, 1, r.st));
+        r.hold_kicks = r.p0_on_main;
+        defer_stack_wgrads(c, mlps, g, X, ldx, a_idx, rows, acts, dzs, ldh, Zlast, ldz);
+        return;
+    }
+    seg_launch(r, seg, rows, mlps[0].out, const_cast<float*>(Zlast), ldz);
+    for (int l = L - 1; l >= 0; --l) {
+        const float* dZ = (l == L - 1) ? Zlast : ws + dzs[l];
+        const int lddz = (l == L - 1) ? ldz : ldh;
+        const float* Xl = (l == 0) ? X : ws + acts[l - 1];
+        int widx[GI_MAX_GROUPS];
+        for (int t = 0; t < g.n; ++t) widx[t] = mlps[t].w(l);
+        defer_wgrad(c, widx, g, dZ, lddz, Xl, l == 0 ? ldx : ldh, l == 0 ? a_idx : nullptr, rows);
+        const Mlp& q = mlps[0];
+        if (l > 0)
+            linear_dgrad(r, widx, g, q.fan_out(l), q.fan_in(l), q.fan_in(l), dZ, lddz, rows,
+                         ws + dzs[l - 1], ldh, ws + acts[l - 1], ldh, false);
+        else if (dX)
+            linear_dgrad(r, widx, g, q.fan_out(0), q.fan_in(0), dx_cols, dZ, lddz, rows, dX,
+                         lddx, nullptr, 0, false);
     }
 }
 
 // ---- AttGGNN: the message MLP and the energy MLP of a pass are siblings (same input rows, same
 // bond-type grouping): layer l of both goes into one launch, like the readout's sibling stacks.
-struct SegIn;
-void seg_launch(Run& r, const SegIn* seg, int rows, int cols, float* y, int ldy);
-
 struct EdgeChain {
     const Mlp* mlps;               // [Fe] per-bond-type stacks
     const long long* acts;         // hidden activations (ws offsets)
@@ -1285,13 +1324,14 @@ void grouped_problem(gi_gemm_params& p, const Grp& g) {
     p.ngroups = g.n; p.grp_off = g.off; p.max_group_rows = g.max_rows;
 }
 
-void edge_chains_forward(Run& r, float* ws, const EdgeChain* ch, int n, const Grp& g,
-                         const float* X, int ldx, const int* a_idx, int rows) {
+void edge_chains_forward(Call& k, const EdgeChain* ch, int n, const Grp& g, const float* X, int ldx,
+                         const int* a_idx, int rows) {
+    Run& r = k.r; float* const ws = k.ws;
     if (n == 2 && r.ok() && rows > 0 && r.img_f[0] && r.img_f[1] && ldx >= gi_r4(ch[0].mlps[0].in)) {
         gi_chain_params c[2];                   // both stacks' whole forward in ONE launch
         for (int j = 0; j < 2; ++j)
-            chain_fwd_params(c[j], r, ws, ch[j].mlps, g, X, ldx, a_idx, rows, ch[j].acts, ch[j].ldh,
-                             ch[j].out, ch[j].ldout);
+            chain_fwd_params(c[j], k, ch[j].mlps, g, X, ldx, a_idx, rows, ch[j].acts, ch[j].ldh, ch[j].out,
+                             ch[j].ldout);
         r.chk(gi_mlp_chain(c, 2, r.st));
         return;
     }
@@ -1329,17 +1369,17 @@ void edge_chains_forward(Run& r, float* ws, const EdgeChain* ch, int n, const Gr
 }
 
 // layers aligned from the end; weight gradients deferred
-void edge_chains_backward(Run& r, float* ws, SlabPlan& sp, float* slabs, Deferred& dq,
-                          const EdgeChain* ch, int n, const Grp& g, const float* X, int ldx,
+void edge_chains_backward(Call& k, const EdgeChain* ch, int n, const Grp& g, const float* X, int ldx,
                           const int* a_idx, int rows, int lddx, int dx_cols) {
+    Run& r = k.r; float* const ws = k.ws;
     if (n == 2 && r.ok() && rows > 0 && r.img_b[0] && r.img_b[1] && dx_cols == ch[0].mlps[0].in &&
         dx_cols == ch[1].mlps[0].in && ch[0].ldout >= gi_r4(ch[0].mlps[0].out) &&
         ch[1].ldout >= gi_r4(ch[1].mlps[0].out)) {
         gi_chain_params c[2];                   // both dZ chains in ONE launch, then the wgrads
         int nl[2];
         for (int j = 0; j < 2; ++j) {
-            nl[j] = chain_bwd_params(c[j], r, ws, ch[j].mlps, g, ch[j].out, ch[j].ldout, rows,
-                                     ch[j].acts, ch[j].dzs, ch[j].ldh, ch[j].dX, lddx, dx_cols);
+            nl[j] = chain_bwd_params(c[j], k, ch[j].mlps, g, ch[j].out, ch[j].ldout, rows, ch[j].acts, ch[j].dzs,
+                                     ch[j].ldh, ch[j].dX, lddx, dx_cols);
             seg_launch(r, ch[j].seg, rows, ch[j].mlps[0].out, ch[j].out, ch[j].ldout);
         }
         if (nl[0] && nl[1]) r.chk(gi_mlp_chain(c, 2, r.st));
@@ -1347,8 +1387,8 @@ void edge_chains_backward(Run& r, float* ws, SlabPlan& sp, float* slabs, Deferre
         else if (nl[1]) r.chk(gi_mlp_chain(&c[1], 1, r.st));
         r.hold_kicks = r.p0_on_main;
         for (int j = 0; j < 2; ++j)
-            defer_stack_wgrads(r, ws, sp, slabs, dq, ch[j].mlps, g, X, ldx, a_idx, rows, ch[j].acts,
-                               ch[j].dzs, ch[j].ldh, ch[j].out, ch[j].ldout);
+            defer_stack_wgrads(k, ch[j].mlps, g, X, ldx, a_idx, rows, ch[j].acts, ch[j].dzs, ch[j].ldh, ch[j].out,
+                               ch[j].ldout);
         return;
     }
     for (int j = 0; j < n; ++j) seg_launch(r, ch[j].seg, rows, ch[j].mlps[0].out, ch[j].out, ch[j].ldout);
@@ -1366,8 +1406,7 @@ void edge_chains_backward(Run& r, float* ws, SlabPlan& sp, float* slabs, Deferre
             const float* Xl = (l == 0) ? X : ws + c.acts[l - 1];
             int widx[GI_MAX_GROUPS];
             for (int t = 0; t < g.n; ++t) widx[t] = c.mlps[t].w(l);
-            defer_wgrad(r, dq, sp, slabs, widx, g, dZ, lddz, Xl, l == 0 ? ldx : c.ldh,
-                        l == 0 ? a_idx : nullptr, rows);
+            defer_wgrad(k, widx, g, dZ, lddz, Xl, l == 0 ? ldx : c.ldh, l == 0 ? a_idx : nullptr, rows);
             if (l == 0 && !c.dX) continue;
             gi_gemm_params& p = bd.next();
             p.A = dZ; p.lda = lddz; p.M = rows; p.K = q.fan_out(l);
@@ -1385,32 +1424,34 @@ void edge_chains_backward(Run& r, float* ws, SlabPlan& sp, float* slabs, Deferre
     }
 }
 
-}  // namespace
-
-// ================================ C ABI ==========================================================
-// A stream of the lowest priority the device offers, for gi_ggnn_backward's side_stream: the
-// weight-gradient GEMMs should only fill what the dZ chain (on the caller's stream) leaves idle.
-extern "C" int gi_side_stream_create(void** out) {
-    if (!out) return GI_EINVAL;
-    int least = 0, greatest = 0;
-    hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
-    if (e != hipSuccess) return (int)e;
-    hipStream_t st = nullptr;
-    e = hipStreamCreateWithPriority(&st, hipStreamNonBlocking, least);
-    if (e != hipSuccess) return (int)e;
-    *out = (void*)st;
-    return 0;
-}
-
-extern "C" int gi_side_stream_destroy(void* stream) {
-    if (!stream) return 0;
-    return (int)hipStreamDestroy((hipStream_t)stream);
-}
-
-extern "C" int gi_ggnn_num_params(const gi_ggnn_dims* d) {
-    Model m;
-    const int rc = build_model(d, m);
-    return rc ? rc : m.nparams;
+// ---- the per-kind list of node-level readout stacks ---------------------------------------------
+// Where a model kind names its node-level stacks (one of the three places a kind plugs in, see the head comment): MNN
+// has fAddNet1 / fConnNet1, GGNN and AttentionGGNN add the gather's att / emb stacks.  Three orders, each fixed by
+// what it feeds (for MNN they coincide):
+//   STACKS_FWD       the forward's shared launches — widest stacks first: their workgroups run twice as long (K = 500
+//                    against 250), so the launch's last, partially filled round of workgroups consists of the short ones;
+//   STACKS_BWD       the backward's shared launches: stack i writes its own d h into the i-th of dh, dhb, dhc, dhd;
+//   STACKS_BY_PARAM  parameter order: the 16-bit-pipe layer table, the zero-row sums, the slab reductions.
+struct NodeStack {
+    const Mlp* mlp;
+    const long long* acts; const long long* dzs; int ldh;     // hidden activations / their dZ (ws offsets)
+    long long out; int ldo;                                   // the last layer's output; backward: its dZ, in place
+    long long zpart; int ldz;                                 // per-graph partial sums of the zero row's gradient
+};
+enum StackOrder { STACKS_FWD, STACKS_BWD, STACKS_BY_PARAM };
+int node_stacks(const Call& c, StackOrder order, NodeStack* s) {
+    const Model& m = c.m; const Ws& w = c.w;
+    const NodeStack add1{&m.add1, w.add1_act, w.add1_dz, w.ldM1, w.add1o, w.ldA, w.zpart_a, w.ldA};
+    const NodeStack conn1{&m.conn1, w.conn1_act, w.conn1_dz, w.ldM1, w.conn1o, w.ldC, w.zpart_c, w.ldC};
+    if (!m.gather()) { s[0] = add1; s[1] = conn1; return 2; }
+    const NodeStack att{&m.att, w.att_act, w.att_dz, w.ldAtt, w.en, w.ldG, w.zpart_g, w.ldZG};
+    const NodeStack emb{&m.emb, w.emb_act, w.emb_dz, w.ldEmb, w.embo, w.ldG, w.zpart_g + m.d.G, w.ldZG};
+    switch (order) {
+    case STACKS_FWD: s[0] = add1; s[1] = conn1; s[2] = att; s[3] = emb; break;
+    case STACKS_BWD: s[0] = add1; s[1] = conn1; s[2] = emb; s[3] = att; break;
+    case STACKS_BY_PARAM: s[0] = att; s[1] = emb; s[2] = add1; s[3] = conn1; break;
+    }
+    return 4;
 }
 
 // the layers of this call that run as bf16x3 / fp16x2 launches.  Builds the table the launches look their layer up in
@@ -1420,7 +1461,9 @@ extern "C" int gi_ggnn_num_params(const gi_ggnn_dims* d) {
 //   BF3_DO_PACK  the W^T images (the backward, or the forward on its side stream: GI_RUN_PREPACK_BWD).
 // `backward` selects which table is left in r (a forward that prepacks calls this twice: images first, then its own).
 enum { BF3_DO_AMAX = 1, BF3_DO_PACK = 2 };
-void bf3_prepare(Run& r, const Model& m, float* ws, const Ws& w, bool backward, int rows, int what, hipStream_t st) {
+void bf3_prepare(Call& c, bool backward, int what, hipStream_t st) {
+    Run& r = c.r; float* const ws = c.ws; const Ws& w = c.w;
+    const int rows = c.R;
     r.nbf3 = 0;
     if (!bf3_enabled() || r.drop || w.bf3_floats <= 0) return;
     // Too few rows for the 16-bit pipe: nothing to prepare — EXCEPT the max |W| cells of gi_graph.wcache when this forward
@@ -1428,7 +1471,8 @@ void bf3_prepare(Run& r, const Model& m, float* ws, const Ws& w, bool backward, 
     // a B = 1 forward followed by a B = 1000 one read cells nobody had written).
     const bool derive_only = rows < BF3_MIN_ROWS;
     if (derive_only && !(r.wc_bf3 && !r.wc_valid && (what & BF3_DO_AMAX) && !backward)) return;
-    const Mlp* t1[4] = {&m.att, &m.emb, &m.add1, &m.conn1};
+    NodeStack t1[4];
+    const int nt1 = node_stacks(c, STACKS_BY_PARAM, t1);
     gi_bf3_pack_desc d[GI_BF3_PACK_MAX];
     gi_absmax_desc ad[GI_BF3_PACK_MAX], wd[GI_BF3_PACK_MAX];       // (flattened for gi_absmax; [out][in] for the guard)
     unsigned short* img = reinterpret_cast<unsigned short*>(ws + w.bf3);
@@ -1436,8 +1480,9 @@ void bf3_prepare(Run& r, const Model& m, float* ws, const Ws& w, bool backward, 
     const bool x2 = r.x2 && gi_b3p_enable(-1);
     long long used = 0;
     int n = 0;
-    for (const Mlp* q : t1)
-        for (int l = 0; l < q->layers() && n < GI_BF3_PACK_MAX && (m.gather() || (q != &m.att && q != &m.emb)); ++l) {
+    for (int s = 0; s < nt1; ++s) {
+        const Mlp* q = t1[s].mlp;
+        for (int l = 0; l < q->layers() && n < GI_BF3_PACK_MAX; ++l) {
             if (!bf3_layer_ok(*q, l)) continue;
             const int fi = q->fan_in(l), fo = q->fan_out(l);
             d[n].W = r.P[q->w(l)]; d[n].ld = fi; d[n].transpose = backward ? 1 : 0;
@@ -1455,6 +1500,7 @@ void bf3_prepare(Run& r, const Model& m, float* ws, const Ws& w, bool backward, 
             used += std::max(gi_bf3_image_elems(fo, fi), gi_bf3_image_elems(fi, fo));
             ++n;
         }
+    }
     if (n && backward && (what & BF3_DO_PACK) && !derive_only) r.chk(gi_bf3_pack(d, n, st));
     if (n && x2 && (what & BF3_DO_AMAX)) {
         if (!derive_only) r.chk((int)hipMemsetAsync(am, 0, sizeof(float) * 4 * GI_AMAX_WORDS * n, st));      // (the activations' / dZ cells: every forward)
@@ -1511,6 +1557,774 @@ hipEvent_t prepack_lookup(const float* ws, bool x2) {     // (both calls of a tw
     for (PrepackEntry& e : g_prepack)
         if (e.valid && e.ws == ws && e.dev == dev && e.x2 == x2) return e.ev;
     return nullptr;
+}
+
+// AlphaDropout training mode needs the graph without row sharing (gi_compact_count_ex, nodedup): an
+// independent mask per padded slot and per edge
+static int dropout_graph_ok(const gi_ggnn_dims& d, int S, int E, int U, int D0) {
+    if (!d.dropout) return 0;
+    if (S != d.B * d.N || U != E || D0 != 0) return GI_EINVAL;
+    return 0;
+}
+
+// ---- opening a call ------------------------------------------------------------------------------
+// Builds the model, makes every argument check of a forward or backward call and derives what the stages read.  Every
+// refusal happens here, before the call's first HIP runtime call.  Checks that every kind makes come first; a check
+// that only some kinds make says which.  The caller has set c.out / c.ldout (forward) or c.slabs, c.y_out, c.d_out,
+// c.grads (backward).
+int open_call(Call& c, bool backward, const gi_ggnn_dims* dp, const float* const* params, const gi_graph* gp,
+              float* ws, void* stream, void* side_stream, bool no_x2) {
+    Model& m = c.m;
+    if (int rc = build_model(dp, m)) return rc;
+    if (!gp) return GI_EINVAL;
+    const gi_ggnn_dims& d = m.d;
+    const int S = gp->S, E = gp->E, U = gp->U, D0 = gp->D0;
+    const int* gfix = gp->gfix;
+    if (!params || !gfix || !ws || S < 0 || E < 0 || U < 0 || U > E || !gp->Ut) return GI_EINVAL;
+    if (backward ? (!c.slabs || !c.y_out || !c.d_out || !c.grads) : (!c.out || c.ldout < m.NA + m.NC + 1))
+        return GI_EINVAL;
+    if (E > 0 && (!gp->u_src || !gp->in_perm || U == 0)) return GI_EINVAL;
+    if (backward && E > 0 && (!gp->mu_off || !gp->mu_dst || !gp->out_perm)) return GI_EINVAL;
+    // (sizes finish()'s descriptor table: for every kind, though no MNN model that build_model accepts comes near it)
+    if (backward && m.nparams > MAXPARAMS) return GI_ELIMIT;
+    if (backward && gp->wcache) return GI_EINVAL;     // (a forward that used the weights cache left no max |W| cells in ws)
+    if (int rc = gi_compact_layout(d.B, d.N, d.Fe, &c.L)) return rc;
+    if (D0 < 0 || D0 > U) return GI_EINVAL;
+    if (int rc = dropout_graph_ok(d, S, E, U, D0)) return rc;
+    if (!backward && gp->bounded && d.dropout) return GI_EINVAL;   // (bounded: S, E, U, D0 are bounds)
+    c.attn = d.kind == GI_KIND_ATTGGNN;
+    if (!m.mnn) {       // GGNN and AttentionGGNN: the pass-0 class rows' operands; a bounded forward runs on class rows
+        if (D0 > 0 && (!gp->d_src || !gp->cmat || gp->ldc0 < D0)) return GI_EINVAL;
+        if (!backward && gp->bounded && D0 <= 0) return GI_EINVAL;
+        if (backward && E > 0 && !gp->mu_slot) return GI_EINVAL;
+        if (backward && m.nparams > MAXPARAMS) return GI_ELIMIT;
+    }
+    if (c.attn && D0 > 0 && (!gp->e2d || !gp->cls_off || !gp->cls_edges)) return GI_EINVAL;   // AttentionGGNN
+    if (m.mnn && backward && gp->bounded) return GI_EINVAL;       // MNN: no backward of a bounded forward
+    c.g = gp;
+    c.ws = ws;
+    make_ws(m, S, E, U, D0, c.w);
+    const Ws& w = c.w; const gi_compact_layout_t& L = c.L; Run& r = c.r;
+    r.st = (hipStream_t)stream; r.P = params; r.rc = 0;
+    r.drop = d.dropout != 0; r.seed = d.drop_seed; r.fshift = w.fshift;
+    r.skinny = ws + w.skinny; r.skinny_floats = w.skinny_floats;
+    r.x2 = x2_enabled() && !no_x2;
+    r.guard = gp->x2_guard;
+    r.guard_host = backward ? nullptr : gp->x2_guard_host;        // (the backward only counts: dZ rows never trip)
+    c.side = SideStream{(hipStream_t)side_stream, 0};
+    c.R = w.R; c.NA = m.NA; c.NC = m.NC;
+    c.nfam = m.mnn ? 0 : c.attn ? 2 : 1;
+    if (c.nfam) r.eatt0 = m.eatt;
+    c.seg_off = gfix + L.seg_off; c.src_off = gfix + L.src_off; c.cidx = gfix + L.cidx;
+    c.mask = gfix + L.node_mask; c.type_off = gfix + L.type_off;
+    int maxUt = 0;
+    for (int t = 0; t < d.Fe; ++t) maxUt = std::max(maxUt, gp->Ut[t]);
+    c.bytype = Grp{d.Fe, gfix + L.type_off, maxUt, gp->Ut};
+    c.bytype0 = Grp{d.Fe, gfix + L.type_off0, w.D0};              // pass-0 rows (upper bound per type: all)
+    c.bytype0.dim_slot = 2;                                       // (marks the pass-0 rows)
+    c.out_fshift = r.drop ? (long long)d.B * c.ldout : 0;
+    if (!backward) {
+        if (gp->bounded) { r.dims = gfix + L.dims; r.R_bound = c.R; }
+        if (gp->bounded && c.nfam) r.d0_dev = gfix + L.counts + 20;       // (the class rows' count, for the pass-0 GEMM)
+        // gi_graph.wcache: the weights-only data of this forward live in (and, when valid, come from) the caller's cache
+        wcache_layout(m, c.wc);
+        c.wcache = (gp->wcache && !r.drop && r.x2 && bf3_enabled()) ? gp->wcache : nullptr;
+        if (c.wcache && ((uintptr_t)c.wcache & 15)) return GI_EINVAL;
+        r.wc_valid = c.wcache && gp->wcache_valid != 0;
+        r.wc_bf3 = c.wcache ? c.wcache + c.wc.bf3_wamax : nullptr;
+        return 0;
+    }
+    plan_slabs(m, S, U, gp->Ut, c.sp);
+    r.wgrad_x2 = wgrad_x2_pool_possible(m, r.x2);
+    r.pool.base = r.wgrad_x2 ? ws + w.amax_pool : nullptr;
+    c.dh = ws + w.dh; c.dh2 = ws + w.dh2;
+    // every node-level stack writes its own d h of the last pass, the first into dh; without gather stacks the graph
+    // sum's takes the next buffer.  The last pass's gate backward sums them.
+    NodeStack s[4];
+    const int nsib = node_stacks(c, STACKS_BWD, s) - 1 + (m.gather() ? 0 : 1);
+    const long long sib[3] = {w.dhb, w.dhc, w.dhd};
+    for (int i = 0; i < nsib; ++i) c.dh_sib[i] = ws + sib[i];
+    return 0;
+}
+
+// the readout's parameters (weight indices) in parameter order
+template <class F>
+void for_readout_params(const Call& c, F&& fn) {
+    NodeStack s[4];
+    const int n = node_stacks(c, STACKS_BY_PARAM, s);
+    const Mlp* t2[3] = {&c.m.add2, &c.m.conn2, &c.m.term2};
+    for (int i = 0; i < n + 3; ++i) {
+        const Mlp* q = i < n ? s[i].mlp : t2[i - n];
+        for (int l = 0; l < q->layers(); ++l) fn(q->w(l));
+    }
+}
+
+// ================================ forward stages ==================================================
+// What a forward derives from the weights alone: the chain kernels' packed images, the amax cells, the fp16x2 weight
+// guard and — `prepack` (GI_RUN_PREPACK_BWD outside dropout mode) — the images of the backward.  A model without
+// message stacks (nfam == 0) has no chain images, message cells or chain weight guard.
+void weights_prologue_fwd(Call& c, bool prepack) {
+    Run& r = c.r; const Model& m = c.m; const Ws& w = c.w; const gi_ggnn_dims& d = m.d; float* const ws = c.ws;
+    float* const wcache = c.wcache;
+    const int E = c.g->E;
+    // Packed weight images of the chain kernel, once per forward.  A forward whose chains do not run (no edges) still
+    // derives the fp16x2 image, its cells and (below) its weight guard into a cache that is not valid yet: the caller
+    // marks the cache valid after this call, and a later forward with edges reads the image from it.
+    const bool chains_run = d.passes > 0 && E > 0;
+    float* guard_cells[2] = {nullptr, nullptr};     // the forward chains' max |W| cells packed by this call
+    for (int k = 0; k < c.nfam; ++k) {
+        if (w.img_f_n[k] <= 0) continue;
+        const bool fx = !r.drop && chain_x2_enabled(r.x2);      // the row-independent fp16x2 chain, not the fp32 one
+        const bool cached = fx && wcache && c.wc.img_fx[k] >= 0;
+        if (!chains_run && !(cached && !r.wc_valid)) continue;
+        if (fx) {
+            float* const img = cached ? wcache + c.wc.img_fx[k] : ws + w.img_fx[k];
+            float* const cells = cached ? wcache + c.wc.chain_amax_f[k] : ws + w.chain_amax_f[k];
+            if (!(r.wc_valid && cached)) {
+                Run rp = r;
+                rp.chain_amax[k] = cells;
+                chain_pack(rp, k ? m.eatt : m.msg, d.Fe, false, img);
+                r.chk(rp.rc);
+                guard_cells[k] = cells;
+            }
+            if (chains_run) {
+                r.img_fx[k] = img;
+                r.chain_amax_f[k] = cells;
+                r.img_f[k] = r.img_fx[k];                       // (nothing may read the fp32 image: it was not packed)
+            }
+        } else {
+            r.img_f[k] = ws + w.img_f[k];
+            chain_pack(r, k ? m.eatt : m.msg, d.Fe, false, r.img_f[k]);
+        }
+    }
+    // Everything else that depends on the weights only goes to the side stream when there is one: the amax cells of
+    // the fp16x2 layers (needed by the readout, hundreds of microseconds from here) and — `prepack` — the images the
+    // backward would otherwise pack at its start, in front of its first launches.
+    hipStream_t prep = r.st;
+    if (c.has_side()) {
+        hipEvent_t start = c.side.next();
+        r.chk((int)hipEventRecord(start, r.st));            // (the weights were last written on the caller's stream)
+        r.chk((int)hipStreamWaitEvent(c.side.st, start, 0));
+        prep = c.side.st;
+    }
+    // amax cells of the message / energy stacks' activations (this forward's chains publish into them, the backward's
+    // chains add the dZ maxima, its fp16x2 weight gradients read both): zeroed first thing on the side stream
+    if (E > 0 && d.passes > 0 && msg_wgrad_x2_possible(m, r.x2)) {
+        for (int k = 0; k < c.nfam; ++k)
+            if (w.img_f_n[k] > 0 && r.img_fx[k]) {
+                c.msg_cells_base[k] = ws + w.msg_amax[k];
+                r.chk((int)hipMemsetAsync(c.msg_cells_base[k], 0, sizeof(float) * MSG_CELLS_PER_PASS * d.passes, prep));
+            }
+        if (c.has_side()) {
+            c.msg_cells_ready = c.side.next();
+            r.chk((int)hipEventRecord(c.msg_cells_ready, c.side.st));
+        }
+    }
+    if (prepack) {
+        bf3_prepare(c, true, BF3_DO_PACK, prep);
+        if (chains_run)
+            for (int k = 0; k < c.nfam; ++k)
+                if (w.img_b_n[k] > 0) {
+                    Run rp = r;                                   // (chain_pack reads the stream and the flavour from its Run)
+                    rp.st = prep;
+                    rp.chain_amax[k] = chain_x2_enabled(r.x2) ? ws + w.chain_amax[k] : nullptr;
+                    chain_pack(rp, k ? m.eatt : m.msg, d.Fe, true, ws + w.img_b[k]);
+                    r.chk(rp.rc);
+                }
+    }
+    // the forward chains' weights through the fp16x2 guard (output channels / input columns below the per-tensor range)
+    if (r.guard && r.ok())
+        for (int k = 0; k < c.nfam; ++k)
+            if (guard_cells[k]) {
+                const Mlp* mlps = k ? m.eatt : m.msg;
+                gi_absmax_desc wd[GI_ABSMAX_MAX];
+                int n = 0;
+                const int L = mlps[0].layers();
+                for (int l = 0; l < L; ++l)
+                    for (int t = 0; t < d.Fe; ++t) {
+                        wd[n].x = r.P[mlps[t].w(l)]; wd[n].rows = mlps[0].fan_out(l); wd[n].cols = mlps[0].fan_in(l);
+                        wd[n].ld = wd[n].cols;
+                        wd[n].out = guard_cells[k] + ((long long)l * d.Fe + t) * GI_AMAX_WORDS;
+                        if (++n == GI_ABSMAX_MAX || (l == L - 1 && t == d.Fe - 1)) {
+                            r.chk(gi_x2_weight_guard(wd, n, r.guard + 1, r.guard_host, prep));
+                            n = 0;
+                        }
+                    }
+            }
+    bf3_prepare(c, false, BF3_DO_AMAX, prep);
+    if (prepack) c.packed = prepack_stamp(ws, r.x2);              // this workspace's "images written" event
+    else prepack_forget(ws);
+    if (c.has_side()) {
+        c.cells_ready = c.side.next();
+        r.chk((int)hipEventRecord(c.cells_ready, c.side.st));
+        if (c.packed) r.chk((int)hipEventRecord(c.packed, c.side.st));
+    } else if (c.packed) {
+        r.chk((int)hipEventRecord(c.packed, r.st));
+    }
+    // pass-0 row cache (inference loops): only in front of the one-launch stack path, whose kernel can skip
+    bool one_launch = c.nfam > 0 && w.ldhx >= gi_r4(m.msg[0].in);
+    for (int k = 0; k < c.nfam; ++k) one_launch = one_launch && r.img_f[k];
+    if (c.g->p0_cache && w.D0 > 0 && E > 0 && !r.drop && one_launch) c.p0c = static_cast<int*>(c.g->p0_cache);
+}
+
+// the amax cells this pass's message-row chains publish into (pass 0 on the class rows: one-slab fp32 weight
+// gradients, no cells)
+void pass_cells_fwd(Call& c, int p) {
+    Run& r = c.r;
+    r.pass = p;
+    for (int k = 0; k < 2; ++k)
+        r.msg_cells[k] = (c.msg_cells_base[k] && !(p == 0 && c.w.D0 > 0)) ? c.msg_cells_base[k] + p * MSG_CELLS_PER_PASS : nullptr;
+    if (c.msg_cells_ready && (r.msg_cells[0] || r.msg_cells[1])) {
+        r.chk((int)hipStreamWaitEvent(r.st, c.msg_cells_ready, 0));    // (zeroed ~100 us ago: never stalls)
+        c.msg_cells_ready = nullptr;
+    }
+}
+
+// ---- the message step of a pass, one body per model kind: agg[p] from hx[p] ----------------------
+// GGNN (gnn/mpnn.py:284-294 + the sum of gnn/summation_mpnn.py:141): m_u = MLP_type(u)(h_src(u)) once per message row,
+// a_v = the sum of v's incoming messages.  Returns true when the GRU update rode in the aggregation's launch.
+bool msg_fwd_ggnn(Call& c, int p) {
+    Run& r = c.r; const Model& m = c.m; const Ws& w = c.w; const gi_ggnn_dims& d = m.d; const gi_graph* gp = c.g;
+    float* const ws = c.ws; const float* hx = ws + w.hx[p];
+    const int R = c.R;
+    if (p == 0 && w.D0 > 0) {
+        // pass 0: h = [x | 0], one message row per (feature class, bond type); a_v = cmat . m0
+        if (c.p0c) {
+            r.chk(gi_p0_cache_lookup(gp->gfix, d.B, d.N, d.Fe, c.p0c, 1, ws + w.m[0], nullptr, w.ldM, r.st));
+            r.skip = c.p0c;
+        }
+        mlp_forward(c, m.msg, c.bytype0, hx, w.ldhx, gp->d_src, w.D0, w.eact[0], w.ldEh, ws + w.m[0], w.ldM);
+        if (c.p0c) {
+            r.skip = nullptr;
+            r.chk(gi_p0_cache_insert(gp->gfix, d.B, d.N, d.Fe, c.p0c, 1, ws + w.m[0], nullptr, w.ldM, r.st));
+        }
+        if (r.ok()) {
+            gi_gemm_params q;
+            gemm_defaults(q);
+            q.A = gp->cmat; q.lda = gp->ldc0; q.B = ws + w.m[0]; q.ldb = w.ldM; q.b_major = 1;
+            q.C = ws + w.agg[0]; q.ldc = w.ldM; q.M = R; q.N = d.M; q.K = w.D0;
+            q.m_dev = r.dims; q.k_dev = r.d0_dev;      // (bounded forward: R and D0 live on the device)
+            q.tm = 1; q.tn = 1;
+            r.chk(gi_gemm(&q, r.st));
+        }
+        return false;
+    }
+    if (gp->E > 0)
+        mlp_forward(c, m.msg, c.bytype, hx, w.ldhx, gp->u_src, gp->U, w.eact[p], w.ldEh, ws + w.m[p], w.ldM);
+    // a_v = sum of incoming messages: inside the GRU update's launch (GI_GLUE_GRU_AGG) ...
+    if ((gi_glue_flags() & GI_GLUE_GRU_AGG) && gi_gru_fused_agg_ok(d.H, d.M, w.ldM, w.ldhx, w.ld3H, w.ldM) &&
+        gi_gru_fused_agg_pays(R, d.H)) {
+        r.chk(gi_gru_fused_agg_fwd(ws + w.m[p], w.ldM, gp->in_perm, ws + w.agg[p], w.ldM, hx, w.ldhx, r.P[m.gru_wih],
+                                   r.P[m.gru_whh], r.P[m.gru_bih], r.P[m.gru_bhh], ws + w.gi[p], ws + w.gh[p], w.ld3H,
+                                   ws + w.hx[p + 1], c.seg_off, R, r.dims, d.H, d.M, r.st));
+        return true;
+    }
+    // ... or in a launch of its own
+    r.chk(gi_seg_sum_n(ws + w.m[p], w.ldM, gp->in_perm, c.seg_off, R, d.M, ws + w.agg[p], w.ldM, 0, r.dims, r.st));
+    return false;
+}
+
+// AttentionGGNN.aggregate_message (gnn/mpnn.py:370-389): message and energy MLPs of the edge's bond type on h_src(e),
+// softmax over each node's incoming edges, weighted sum.  Pass 0 (h = [x | 0]): both MLP families on the D0 (feature
+// class, bond type) rows, the softmax reads them through the edge -> pass-0 row index.
+void msg_fwd_attggnn(Call& c, int p) {
+    Run& r = c.r; const Model& m = c.m; const Ws& w = c.w; const gi_ggnn_dims& d = m.d; const gi_graph* gp = c.g;
+    float* const ws = c.ws; const float* hx = ws + w.hx[p];
+    const bool p0 = p == 0 && w.D0 > 0;
+    const int* in_perm = (gp->E == 0 && !gp->in_perm) ? gp->gfix : gp->in_perm;   // (no edges: never read)
+    if (p == 0 && c.p0c) {
+        r.chk(gi_p0_cache_lookup(gp->gfix, d.B, d.N, d.Fe, c.p0c, 2, ws + w.m[0], ws + w.een[0], w.ldM, r.st));
+        r.skip = c.p0c;
+    }
+    if (gp->E > 0) {
+        EdgeChain ch[2] = {
+            {m.msg, w.eact[p], w.edz[p], w.ldEh, ws + w.m[p], w.ldM, nullptr},
+            {m.eatt, w.aact[p], w.adz[p], w.ldEa, ws + w.een[p], w.ldM, nullptr}};
+        if (p0) edge_chains_forward(c, ch, 2, c.bytype0, hx, w.ldhx, gp->d_src, w.D0);
+        else edge_chains_forward(c, ch, 2, c.bytype, hx, w.ldhx, gp->u_src, gp->U);
+        if (p0 && c.p0c) {
+            r.skip = nullptr;
+            r.chk(gi_p0_cache_insert(gp->gfix, d.B, d.N, d.Fe, c.p0c, 2, ws + w.m[0], ws + w.een[0], w.ldM, r.st));
+        }
+    }
+    r.chk(gi_seg_softmax_fwd_n(ws + w.een[p], ws + w.m[p], w.ldM, p0 ? gp->e2d : in_perm, c.seg_off, c.R, d.M,
+                               ws + w.agg[p], w.ldM, r.dims, r.st));
+}
+
+// MNN (gnn/mpnn.py:58-63 + the sum of gnn/summation_mpnn.py:141), aggregate first: S_p = the typed sum of h_p over
+// each node's incoming edges [R, H Fe], messages = S_p . W.view(M, H Fe)^T — one fp32-MFMA GEMM on the parameter as
+// stored.
+void msg_fwd_mnn(Call& c, int p) {
+    Run& r = c.r; const Model& m = c.m; const Ws& w = c.w; const gi_ggnn_dims& d = m.d; float* const ws = c.ws;
+    const int HF = d.H * d.Fe;
+    r.chk(gi_typed_seg_sum_n(ws + w.hx[p], w.ldhx, c.g->u_src, c.g->in_perm, c.seg_off, c.type_off, c.R, d.H, d.Fe,
+                             ws + w.ssum[p], w.ldS, r.dims, r.st));
+    if (!r.ok()) return;
+    gi_gemm_params q;
+    gemm_defaults(q);
+    q.A = ws + w.ssum[p]; q.lda = w.ldS; q.B = r.P[m.mw]; q.ldb = HF;
+    q.C = ws + w.agg[p]; q.ldc = w.ldM; q.M = c.R; q.N = d.M; q.K = HF;
+    q.m_dev = r.dims;
+    pick_tile(c.R, d.M, q.tm, q.tn);
+    r.chk(gi_gemm(&q, r.st));
+}
+
+// GRU update (gnn/mpnn.py:296-297): hx[p + 1] from agg[p] and hx[p]
+void gru_update_fwd(Call& c, int p) {
+    Run& r = c.r; const Model& m = c.m; const Ws& w = c.w; const gi_ggnn_dims& d = m.d; float* const ws = c.ws;
+    const float* hx = ws + w.hx[p];
+    // projections + gates in ONE launch (gi_gru.hip, round 6) ...
+    if (gi_gru_fused_ok(d.H, d.M, w.ldM, w.ldhx, w.ld3H)) {
+        r.chk(gi_gru_fused_fwd(ws + w.agg[p], w.ldM, hx, w.ldhx, r.P[m.gru_wih], r.P[m.gru_whh], r.P[m.gru_bih],
+                               r.P[m.gru_bhh], ws + w.gi[p], ws + w.gh[p], w.ld3H, ws + w.hx[p + 1], c.seg_off, c.R,
+                               r.dims, d.H, d.M, r.st));
+        return;
+    }
+    // ... or (widths that are not multiples of 4): both input projections in one launch, then the gate kernel
+    Batch b;
+    add_fwd(b, r, r.P[m.gru_wih], r.P[m.gru_bih], d.M, 3 * d.H, ws + w.agg[p], w.ldM, c.R, ws + w.gi[p], w.ld3H, false);
+    add_fwd(b, r, r.P[m.gru_whh], r.P[m.gru_bhh], d.H, 3 * d.H, hx, w.ldhx, c.R, ws + w.gh[p], w.ld3H, false);
+    flush_batch(r, b, false);
+    r.chk(gi_gru_gates_fwd_n(ws + w.gi[p], ws + w.gh[p], w.ld3H, hx, ws + w.hx[p + 1], w.ldhx, c.seg_off, c.R, d.H,
+                             d.Fn, r.dims, r.st));
+}
+
+// ---- readout (gnn/mpnn.py:69-74, 299-303) ---------------------------------------------------------
+// the node-level stacks of the kind (node_stacks), layer by layer in shared launches
+void node_stacks_fwd(Call& c) {
+    const Ws& w = c.w;
+    const float* hx = c.ws + w.hx[c.m.d.passes];
+    NodeStack s[4];
+    const int n = node_stacks(c, STACKS_FWD, s);
+    MlpJob jobs[4] = {};
+    for (int i = 0; i < n; ++i) jobs[i] = {s[i].mlp, hx, w.ldhx, c.R, s[i].acts, s[i].ldh, c.ws + s[i].out, s[i].ldo};
+    mlp_jobs_forward(c, jobs, n);
+}
+
+// The graph embedding into the three places GlobalReadout reads it — the gather over a graph's nodes (GGNN,
+// AttentionGGNN) or the graph sum of every slot's h (MNN) — and the node-level outputs into their slots (tier-1 glue).
+void gather_fwd(Call& c) {
+    Run& r = c.r; const Model& m = c.m; const Ws& w = c.w; const gi_ggnn_dims& d = m.d; float* const ws = c.ws;
+    if (!m.gather()) {
+        if (r.ok())
+            r.chk(gi_graph_sum_fwd(ws + w.hx[d.passes], w.ldhx, c.cidx, d.B, d.N, d.H, ws + w.cat_add + c.NA, w.ldCA,
+                                   ws + w.cat_conn + c.NC, w.ldCC, ws + w.gemb, w.ldG, r.st));
+    } else if (gi_glue_flags() & GI_GLUE_READOUT_FWD) {     // gather + tier-1 expansion in one launch
+        r.chk(gi_readout_glue_fwd(ws + w.en, ws + w.embo, w.ldG, c.cidx, c.mask, d.B, d.N, d.G, d.big_positive,
+                                  ws + w.cat_add + c.NA, w.ldCA, ws + w.cat_conn + c.NC, w.ldCC, ws + w.gemb, w.ldG,
+                                  ws + w.add1o, w.ldA, d.A, ws + w.cat_add, w.ldCA, ws + w.conn1o, w.ldC, d.C,
+                                  ws + w.cat_conn, w.ldCC, r.st));
+        return;
+    } else {
+        r.chk(gi_gather_readout_fwd(ws + w.en, ws + w.embo, w.ldG, c.cidx, c.mask, d.B, d.N, d.G, d.big_positive,
+                                    ws + w.cat_add + c.NA, w.ldCA, ws + w.cat_conn + c.NC, w.ldCC, ws + w.gemb, w.ldG,
+                                    r.st));
+    }
+    if (gi_fuse_flags() & GI_FUSE_SLOTS) {
+        r.chk(gi_expand_slots2(ws + w.add1o, w.ldA, d.A, ws + w.cat_add, w.ldCA, ws + w.conn1o, w.ldC, d.C,
+                               ws + w.cat_conn, w.ldCC, c.cidx, d.B, d.N, r.st));
+    } else {
+        r.chk(gi_expand_slots(ws + w.add1o, w.ldA, c.cidx, d.B, d.N, d.A, ws + w.cat_add, w.ldCA, r.st));
+        r.chk(gi_expand_slots(ws + w.conn1o, w.ldC, c.cidx, d.B, d.N, d.C, ws + w.cat_conn, w.ldCC, r.st));
+    }
+}
+
+// the three graph-level stacks write straight into the logits
+void graph_stacks_fwd(Call& c) {
+    const Model& m = c.m; const Ws& w = c.w; float* const ws = c.ws;
+    const int B = m.d.B;
+    MlpJob jobs[3] = {};
+    jobs[0] = {&m.add2, ws + w.cat_add, w.ldCA, B, w.add2_act, w.ldM2, c.out, c.ldout};
+    jobs[1] = {&m.conn2, ws + w.cat_conn, w.ldCC, B, w.conn2_act, w.ldM2, c.out + c.NA, c.ldout};
+    jobs[2] = {&m.term2, ws + w.gemb, w.ldG, B, w.term2_act, w.ldM2, c.out + c.NA + c.NC, c.ldout};
+    // dropout mode: `out` is [2 B, ldout]; rows [B, 2 B) take the factors of the logits
+    for (MlpJob& j : jobs) j.out_fshift = c.out_fshift;
+    mlp_jobs_forward(c, jobs, 3);
+}
+
+int epilogue_fwd(Call& c) {
+    Run& r = c.r;
+    // Whatever the caller enqueues on `stream` after this call — the backward, or a kernel that reuses the workspace's
+    // memory because the tape was dropped without one — is ordered behind the side stream's packs into `ws` (they
+    // finished hundreds of microseconds ago: a wait that never stalls).  The caller therefore needs no cross-stream
+    // bookkeeping of its own for `ws` (torch: no Tensor.record_stream, which would keep the caching allocator from
+    // reusing the block until the low-priority side stream has drained).
+    if (c.has_side() && c.packed) r.chk((int)hipStreamWaitEvent(r.st, c.packed, 0));
+    if (!r.ok()) prepack_forget(c.ws);            // (a failed forward's images are not to be trusted)
+    return r.rc;
+}
+
+// ================================ backward stages =================================================
+// GI_BWD_PREPACKED: the images written by THIS workspace's forward (side stream)?  Waits for them, or returns false:
+// no such forward on record, pack here.
+bool await_prepack(Call& c) {
+    hipEvent_t ev = prepack_lookup(c.ws, c.r.x2);
+    if (ev) c.r.chk((int)hipStreamWaitEvent(c.r.st, ev, 0));
+    return ev != nullptr;
+}
+
+// ---- tier 2 (gnn/modules.py:265-279): dZ of the graph-level stacks' last layers from d_out and the logits
+void tier2_selu_bwd(Call& c) {
+    Run& r = c.r; const Ws& w = c.w; float* const ws = c.ws;
+    const int B = c.m.d.B, NA = c.NA, NC = c.NC;
+    if (gi_fuse_flags() & GI_FUSE_TIER2_DSELU) {
+        r.chk(gi_selu_bwd_cols3_f(c.d_out, c.lddout, c.y_out, c.ldout, c.out_fshift, B, NA, ws + w.dzA, w.ldNA, NC,
+                                  ws + w.dzC, w.ldNC, 1, ws + w.dzT, 4, r.st));
+        return;
+    }
+    r.chk(gi_selu_bwd_rows_f(c.d_out, c.lddout, nullptr, c.y_out, c.ldout, ws + w.dzA, w.ldNA, B, NA, c.out_fshift,
+                             r.st));
+    r.chk(gi_selu_bwd_rows_f(c.d_out + NA, c.lddout, nullptr, c.y_out + NA, c.ldout, ws + w.dzC, w.ldNC, B, NC,
+                             c.out_fshift, r.st));
+    r.chk(gi_selu_bwd_rows_f(c.d_out + NA + NC, c.lddout, nullptr, c.y_out + NA + NC, c.ldout, ws + w.dzT, 4, B, 1,
+                             c.out_fshift, r.st));
+}
+
+void graph_stacks_bwd(Call& c) {
+    const Model& m = c.m; const Ws& w = c.w; float* const ws = c.ws;
+    const int B = m.d.B, G = m.d.G;
+    MlpJob jobs[3] = {};
+    jobs[0] = {&m.add2, ws + w.cat_add, w.ldCA, B, w.add2_act, w.ldM2, nullptr, 0, w.add2_dz,
+               ws + w.dzA, w.ldNA, ws + w.dcat_add, w.ldCA, c.NA + G, false};
+    jobs[1] = {&m.conn2, ws + w.cat_conn, w.ldCC, B, w.conn2_act, w.ldM2, nullptr, 0, w.conn2_dz,
+               ws + w.dzC, w.ldNC, ws + w.dcat_conn, w.ldCC, c.NC + G, false};
+    jobs[2] = {&m.term2, ws + w.gemb, w.ldG, B, w.term2_act, w.ldM2, nullptr, 0, w.term2_dz,
+               ws + w.dzT, 4, ws + w.dgemb, w.ldG, G, false};
+    mlp_jobs_backward(c, jobs, 3);
+}
+
+// ---- gather + tier-1 glue: dZ of the node-level stacks' last layers, in place.  A model without gather stacks has
+// the slot compression only: its graph sum's backward needs no dZ and follows the node-level stacks (graph_sum_bwd).
+void gather_bwd(Call& c) {
+    Run& r = c.r; const Model& m = c.m; const Ws& w = c.w; const gi_ggnn_dims& d = m.d; float* const ws = c.ws;
+    const int S = c.g->S;
+    if (m.gather()) {
+        if (gi_glue_flags() & GI_GLUE_READOUT_BWD) {     // both in one launch
+            r.chk(gi_readout_glue_bwd_f(ws + w.en, ws + w.embo, w.ldG, c.cidx, c.mask, d.B, d.N, d.G, S, d.big_positive,
+                                        ws + w.dgemb, w.ldG, ws + w.dcat_add + c.NA, w.ldCA, ws + w.dcat_conn + c.NC,
+                                        w.ldCC, ws + w.zpart_g, ws + w.add1o, w.ldA, d.A, ws + w.dcat_add, w.ldCA,
+                                        ws + w.zpart_a, w.ldA, ws + w.conn1o, w.ldC, d.C, ws + w.dcat_conn, w.ldCC,
+                                        ws + w.zpart_c, w.ldC, r.fshift, r.st));
+            return;
+        }
+        r.chk(gi_gather_readout_bwd_f(ws + w.en, ws + w.embo, w.ldG, c.cidx, c.mask, d.B, d.N, d.G, S, d.big_positive,
+                                      ws + w.dgemb, w.ldG, ws + w.dcat_add + c.NA, w.ldCA, ws + w.dcat_conn + c.NC,
+                                      w.ldCC, ws + w.zpart_g, r.fshift, r.st));
+    }
+    if (gi_fuse_flags() & GI_FUSE_SLOTS) {
+        r.chk(gi_compress_slots2_f(ws + w.add1o, w.ldA, d.A, ws + w.dcat_add, w.ldCA, ws + w.zpart_a, w.ldA,
+                                   ws + w.conn1o, w.ldC, d.C, ws + w.dcat_conn, w.ldCC, ws + w.zpart_c, w.ldC, c.cidx,
+                                   d.B, d.N, S, r.fshift, r.st));
+    } else {
+        r.chk(gi_compress_slots_f(ws + w.add1o, w.ldA, c.cidx, d.B, d.N, d.A, S, ws + w.dcat_add, w.ldCA,
+                                  ws + w.zpart_a, w.ldA, r.fshift, r.st));
+        r.chk(gi_compress_slots_f(ws + w.conn1o, w.ldC, c.cidx, d.B, d.N, d.C, S, ws + w.dcat_conn, w.ldCC,
+                                  ws + w.zpart_c, w.ldC, r.fshift, r.st));
+    }
+}
+
+// graph sum (a model without gather stacks), behind the node-level stacks: every row of graph b gets d g[b] summed
+// over its three consumers (the zero row: 0), into the d h buffer after the stacks' own (open_call)
+void graph_sum_bwd(Call& c) {
+    Run& r = c.r; const Ws& w = c.w; const gi_ggnn_dims& d = c.m.d; float* const ws = c.ws;
+    NodeStack s[4];
+    float* const dh_out = c.dh_sib[node_stacks(c, STACKS_BWD, s) - 1];
+    if (r.ok())
+        r.chk(gi_graph_sum_bwd(ws + w.dgemb, w.ldG, ws + w.dcat_add + c.NA, w.ldCA, ws + w.dcat_conn + c.NC, w.ldCC,
+                               c.g->gfix + c.L.slot_of, c.g->S, d.N, d.H, dh_out, w.ldH, 0, r.st));
+}
+
+// zero-row gradients of the node-level stacks: per-graph partial sums -> row S, one launch
+void zero_row_colsums(Call& c) {
+    float* const ws = c.ws;
+    NodeStack s[4];
+    const int n = node_stacks(c, STACKS_BY_PARAM, s);
+    gi_colsum_desc cs[4];
+    for (int i = 0; i < n; ++i) {
+        float* z = ws + s[i].out + (long long)c.g->S * s[i].ldo;
+        cs[i] = gi_colsum_desc{ws + s[i].zpart, s[i].ldz, c.m.d.B, s[i].mlp->out, z, z};
+    }
+    c.r.chk(gi_colsum_multi(cs, n, c.r.st));
+}
+
+// ---- node-level readout MLPs -> dh: every sibling writes its own d h; the GRU-gate backward of the last pass sums them
+void node_stacks_bwd(Call& c) {
+    Run& r = c.r; const Ws& w = c.w; float* const ws = c.ws;
+    const float* hxP = ws + w.hx[c.m.d.passes];
+    NodeStack s[4];
+    const int n = node_stacks(c, STACKS_BWD, s);
+    MlpJob jobs[4] = {};
+    for (int i = 0; i < n; ++i)
+        jobs[i] = {s[i].mlp, hxP, w.ldhx, c.R, s[i].acts, s[i].ldh, nullptr, 0, s[i].dzs, ws + s[i].out, s[i].ldo,
+                   i == 0 ? c.dh : c.dh_sib[i - 1], w.ldH, c.m.d.H, false};
+    // No weight-gradient batches beside the node-level dgrad launches: those fill the device by
+    // themselves (2 760 workgroups each at the headline batch), two streams only contend there;
+    // everything queued goes out behind them, under the message passes' short launches (round 2: step
+    // 2.362 -> 2.344 ms, GEMM-family per-launch figure 0.349 -> 0.374 of peak; re-measured in round 3 with the
+    // dgrad launches on the bf16 pipe: 2.20 ms held against 2.25-2.28 released).
+    // Round 5, with the backward bound by the weight-gradient queue: holding still wins at the headline batch
+    // (7.3 k node rows: 1.935 against 1.944 ms) and loses from ~10 k rows on (B = 2000: 3.35 -> 3.24 ms, ZINC shape
+    // 4.05 -> 4.00, ChEMBL shape 3.24 -> 3.21, B = 4000 a tie; profiles/r05/ab/ab_hold_kicks.txt).
+    r.hold_kicks = c.R <= HOLD_KICKS_MAX_ROWS;
+    mlp_jobs_backward(c, jobs, n);
+    r.hold_kicks = false;
+    kick_deferred(c, false);
+}
+
+// packed weight images of the dZ chains, once per backward
+void pack_chains_bwd(Call& c, bool prepacked) {
+    Run& r = c.r; const Ws& w = c.w;
+    if (c.m.d.passes <= 0 || c.g->E <= 0) return;
+    for (int k = 0; k < c.nfam; ++k)
+        if (w.img_b_n[k] > 0) {
+            if (chain_x2_enabled(r.x2)) r.chain_amax[k] = c.ws + w.chain_amax[k];
+            r.img_b[k] = c.ws + w.img_b[k];
+            r.img_b_stride[k] = w.img_b_stride[k];
+            if (!prepacked) chain_pack(r, k ? c.m.eatt : c.m.msg, c.m.d.Fe, true, r.img_b[k]);
+        }
+}
+
+// the cells pass p's forward chains published into (pass_cells_fwd)
+void pass_cells_bwd(Call& c, int p) {
+    Run& r = c.r; const Ws& w = c.w;
+    const bool msgx = c.g->E > 0 && msg_wgrad_x2_possible(c.m, r.x2) && chain_x2_enabled(r.x2);
+    for (int k = 0; k < c.nfam; ++k)
+        r.msg_cells[k] = (msgx && w.img_b_n[k] > 0 && !(p == 0 && w.D0 > 0)) ? c.ws + w.msg_amax[k] + p * MSG_CELLS_PER_PASS : nullptr;
+}
+
+// GRU update of pass p, backward: the gate derivatives (d h of the pass below into dh2), the two deferred weight
+// gradients, and d agg[p] / d h_prev in one dgrad launch
+void gru_update_bwd(Call& c, int p) {
+    Run& r = c.r; const Model& m = c.m; const Ws& w = c.w; const gi_ggnn_dims& d = m.d; float* const ws = c.ws;
+    const Grp none{0, nullptr, 0};
+    const float* hx = ws + w.hx[p];
+    float* gi = ws + w.gi[p];
+    float* gh = ws + w.gh[p];
+    float* dagg = ws + w.dagg[p];
+    const bool last = (p == d.passes - 1);
+    const float* const sib0 = last ? c.dh_sib[0] : nullptr;
+    const float* const sib1 = last ? c.dh_sib[1] : nullptr;
+    const float* const sib2 = last ? c.dh_sib[2] : nullptr;
+    if (c.scat0) {      // the later pass's d h scatter rides in this launch (GI_FUSE_DH_SCATTER)
+        r.chk(gi_gru_gates_bwd_ex(gi, gh, w.ld3H, hx, w.ldhx, c.dh, sib0, sib1, sib2, c.dh2, w.ldH, c.seg_off, c.R, d.H,
+                                  c.scat0, c.scat1, w.ldH, c.g->out_perm, c.src_off, r.st));
+        c.scat0 = c.scat1 = nullptr;
+    } else {
+        r.chk(gi_gru_gates_bwd(gi, gh, w.ld3H, hx, w.ldhx, c.dh, sib0, sib1, sib2, c.dh2, w.ldH, c.seg_off, c.R, d.H,
+                               r.st));
+    }
+    // Pass 0 of the class-row path: the main queue has ~100 us of short launches left, the weight-gradient queue
+    // everything deferred so far: hand that over NOW and keep pass 0's own GRU weight gradients for the main queue's
+    // last launch (with the pass-0 message stack's), so that both queues end together.
+    if (p == 0 && w.D0 > 0 && c.has_side()) {
+        kick_deferred(c, true); r.hold_kicks = r.p0_on_main = true;
+    }
+    const int wih = m.gru_wih, whh = m.gru_whh;
+    defer_wgrad(c, &wih, none, gi, w.ld3H, ws + w.agg[p], w.ldM, nullptr, c.R);
+    defer_wgrad(c, &whh, none, gh, w.ld3H, hx, w.ldhx, nullptr, c.R);
+    // d agg = d gi W_ih;  d h_prev += d gh W_hh   (one launch)
+    Batch bd;
+    add_dgrad(bd, r, m.gru_wih, 3 * d.H, d.M, d.M, gi, w.ld3H, c.R, dagg, w.ldM, nullptr, 0, false);
+    if (p > 0) add_dgrad(bd, r, m.gru_whh, 3 * d.H, d.H, d.H, gh, w.ld3H, c.R, c.dh2, w.ldH, nullptr, 0, true);
+    flush_batch(r, bd, false);
+}
+
+// ---- the message step of a pass, backward, one body per model kind: d h of the pass below (+= into dh2) and the
+// message parameters' weight gradients from d agg[p].
+// d h scatter (segmented sum of the message stacks' input gradients over the source CSR): its own launch(es) behind the
+// pass's dZ chain, or — GI_FUSE_DH_SCATTER, vector gate kernel (H % 4 == 0) — folded into the gate backward of the
+// next iteration, which is the only reader of that sum
+bool fuse_dh_scatter(const Call& c) {
+    return (gi_fuse_flags() & GI_FUSE_DH_SCATTER) && (c.m.d.H & 3) == 0 && c.m.d.H >= 4;
+}
+
+// no edges: the message / energy stacks' weights still need zeroed slabs
+void zero_msg_slabs(Call& c) {
+    for (int k = 0; k < c.nfam; ++k)
+        for (int t = 0; t < c.m.d.Fe; ++t) {
+            const Mlp& q = k ? c.m.eatt[t] : c.m.msg[t];
+            for (int l = 0; l < q.layers(); ++l) {
+                SlabEntry& e = c.sp.e[q.w(l)];
+                c.r.chk((int)hipMemsetAsync(c.slabs + e.off + (long long)e.done * e.nsplit * e.stride, 0,
+                                            sizeof(float) * e.nsplit * e.stride, c.r.st));
+                e.done++;
+            }
+        }
+}
+
+void msg_bwd_ggnn(Call& c, int p) {
+    Run& r = c.r; const Model& m = c.m; const Ws& w = c.w; const gi_ggnn_dims& d = m.d; const gi_graph* gp = c.g;
+    float* const ws = c.ws; const float* hx = ws + w.hx[p];
+    float* dagg = ws + w.dagg[p];
+    if (p == 0 && w.D0 > 0) {
+        // pass 0: d m0 = selu'(m0) * (cmat^T . d agg): split-K over the R rows, slabs summed with
+        // the SELU backward folded in; then the MLP backward on the D0 class rows (no d h needed)
+        gi_gemm_params q;
+        gemm_defaults(q);
+        q.A = gp->cmat; q.lda = gp->ldc0; q.a_major = 1;
+        q.B = dagg; q.ldb = w.ldM; q.b_major = 1;
+        q.C = ws + w.p0slab; q.ldc = w.ldM; q.M = w.D0; q.N = d.M; q.K = c.R;
+        q.flags = GI_GEMM_SPLITK; q.nsplit = w.p0split;
+        q.c_split_stride = gi_r4l((long long)std::max(w.D0, 1) * w.ldM);
+        q.tm = 1; q.tn = 1;
+        r.chk(gi_gemm(&q, r.st));
+        r.chk(gi_slab_sum_dselu(ws + w.p0slab, w.p0split, q.c_split_stride, w.D0, d.M, w.ldM, ws + w.m[0], w.ldM, r.st));
+        msg_backward(c, m.msg, c.bytype0, hx, w.ldhx, gp->d_src, w.D0, w.eact[0], w.edz[0], w.ldEh, ws + w.m[0], w.ldM,
+                     nullptr, w.ldH, d.H);
+    } else if (gp->E > 0) {
+        // d m_u = selu'(m_u) * sum over the edges reading row u of d agg[dst(e)]
+        // (backward of the segmented sum + last SELU, over the message CSR)
+        const SegIn seg{dagg, w.ldM, gp->mu_dst, gp->mu_off};
+        msg_backward(c, m.msg, c.bytype, hx, w.ldhx, gp->u_src, gp->U, w.eact[p], w.edz[p], w.ldEh, ws + w.m[p], w.ldM,
+                     p > 0 ? ws + w.dxe : nullptr, w.ldH, d.H, &seg);
+        if (p > 0 && fuse_dh_scatter(c))
+            c.scat0 = ws + w.dxe;
+        else if (p > 0)   // scatter d h_src back to nodes: segmented sum over the source CSR
+            r.chk(gi_seg_sum(ws + w.dxe, w.ldH, gp->out_perm, c.src_off, c.R, d.H, c.dh2, w.ldH, 1, r.st));
+    } else {
+        zero_msg_slabs(c);
+    }
+}
+
+void msg_bwd_attggnn(Call& c, int p) {
+    Run& r = c.r; const Model& m = c.m; const Ws& w = c.w; const gi_ggnn_dims& d = m.d; const gi_graph* gp = c.g;
+    float* const ws = c.ws; const float* hx = ws + w.hx[p];
+    if (gp->E <= 0) { zero_msg_slabs(c); return; }
+    // backward of the softmax-weighted aggregation: per-edge contributions, then per message
+    // row their sum times the SELU derivative of both stacks' last layer (in place)
+    const bool p0 = p == 0 && w.D0 > 0;      // pass 0 ran on the class rows
+    r.chk(gi_seg_softmax_bwd(ws + w.een[p], ws + w.m[p], w.ldM, p0 ? gp->e2d : gp->in_perm, c.seg_off, c.R, d.M,
+                             ws + w.dagg[p], w.ldM, ws + w.tmp_en, ws + w.tmp_emb, w.ldM, r.st));
+    EdgeChain ch[2] = {
+        {m.msg, w.eact[p], w.edz[p], w.ldEh, ws + w.m[p], w.ldM, p > 0 ? ws + w.dxe : nullptr},
+        {m.eatt, w.aact[p], w.adz[p], w.ldEa, ws + w.een[p], w.ldM, p > 0 ? ws + w.dxa : nullptr}};
+    if (p0) {   // per class row: sum over its (hundreds of) edge slots, both stacks in one launch
+        r.chk(gi_class_sum_dselu(ws + w.tmp_emb, ws + w.tmp_en, w.ldM, gp->cls_edges, gp->cls_off, w.D0, d.M,
+                                 ws + w.m[p], ws + w.een[p], w.ldM, r.st));
+        edge_chains_backward(c, ch, 2, c.bytype0, hx, w.ldhx, gp->d_src, w.D0, w.ldH, d.H);
+    } else {
+        // per message row: the sum of its edges' contributions times the SELU derivative of the
+        // stack's last layer (own launches in front of the dZ chains, edge_chains_backward)
+        const SegIn seg_m{ws + w.tmp_emb, w.ldM, gp->mu_slot, gp->mu_off};
+        const SegIn seg_e{ws + w.tmp_en, w.ldM, gp->mu_slot, gp->mu_off};
+        ch[0].seg = &seg_m; ch[1].seg = &seg_e;
+        edge_chains_backward(c, ch, 2, c.bytype, hx, w.ldhx, gp->u_src, gp->U, w.ldH, d.H);
+    }
+    if (p > 0 && fuse_dh_scatter(c)) {
+        c.scat0 = ws + w.dxe; c.scat1 = ws + w.dxa;
+    } else if (p > 0) {
+        r.chk(gi_seg_sum(ws + w.dxe, w.ldH, gp->out_perm, c.src_off, c.R, d.H, c.dh2, w.ldH, 1, r.st));
+        r.chk(gi_seg_sum(ws + w.dxa, w.ldH, gp->out_perm, c.src_off, c.R, d.H, c.dh2, w.ldH, 1, r.st));
+    }
+}
+
+// MNN: dS = dagg . W.view(M, H Fe), then d h_src += the transposed typed sum of dS
+void msg_bwd_mnn(Call& c, int p) {
+    Run& r = c.r; const Ws& w = c.w; const gi_ggnn_dims& d = c.m.d; const gi_graph* gp = c.g; float* const ws = c.ws;
+    const int HF = d.H * d.Fe;
+    if (p == 0 || gp->E <= 0 || !r.ok()) return;
+    gi_gemm_params q;
+    gemm_defaults(q);
+    q.A = ws + w.dagg[p]; q.lda = w.ldM; q.B = r.P[c.m.mw]; q.ldb = HF; q.b_major = 1;
+    q.C = ws + w.dS; q.ldc = w.ldS; q.M = c.R; q.N = HF; q.K = d.M;
+    pick_tile(c.R, HF, q.tm, q.tn);
+    r.chk(gi_gemm(&q, r.st));
+    if (r.ok())
+        r.chk(gi_typed_seg_sum_t(ws + w.dS, w.ldS, gp->out_perm, c.src_off, gp->mu_off, gp->mu_dst, c.type_off, c.R, d.H,
+                                 d.Fe, c.dh2, w.ldH, 1, r.st));
+}
+
+// MNN, behind the passes: dW.view(M, H Fe) = sum over passes of dagg_p^T S_p: the passes' buffers are contiguous -> one
+// reduction of passes * R rows, split-K into slabs, summed in a fixed order
+void msg_wgrad_mnn(Call& c) {
+    Run& r = c.r; const Ws& w = c.w; const gi_ggnn_dims& d = c.m.d; float* const ws = c.ws;
+    const int HF = d.H * d.Fe;
+    float* const dW = c.grads[c.m.mw];
+    if (d.passes > 0 && r.ok()) {
+        gi_gemm_params q;
+        gemm_defaults(q);
+        q.A = ws + w.dagg[0]; q.lda = w.ldM; q.a_major = 1;
+        q.B = ws + w.ssum[0]; q.ldb = w.ldS; q.b_major = 1;
+        q.C = ws + w.mslab; q.ldc = w.ldS; q.M = d.M; q.N = HF; q.K = d.passes * c.R;
+        q.flags = GI_GEMM_SPLITK; q.nsplit = w.mslab_split; q.c_split_stride = w.mslab_stride;
+        q.tm = 1; q.tn = 1;
+        r.chk(gi_gemm(&q, r.st));
+        if (r.ok())
+            r.chk(gi_slab_epilogue(ws + w.mslab, w.mslab_split, w.mslab_stride, d.M, HF, w.ldS, 0, nullptr, nullptr, 0,
+                                   dW, HF, r.st));
+    } else if (r.ok()) {
+        r.chk((int)hipMemsetAsync(dW, 0, sizeof(float) * (size_t)d.M * HF, r.st));
+    }
+}
+
+// The end of a backward call: launch what is still deferred, then reduce the slabs nobody reduced yet.
+//   GI_BWD_READOUT: finish the readout parameters now — their weight-gradient GEMMs and slab reductions are queued
+//     (side stream if there is one) so that the caller can start exchanging the gradients of these parameters while
+//     the message passes are still being differentiated;
+//   otherwise: all weight-gradient GEMMs, 8 problems per launch, the side stream joined, then slabs -> parameter
+//     gradients of whatever has not been reduced on the side stream yet.
+void finish(Call& c, int phase) {
+    Run& r = c.r; const Model& m = c.m;
+    hipStream_t rst = r.st;
+    if (phase == GI_BWD_READOUT) {
+        if (c.has_side()) { kick_deferred(c, true); rst = c.side.st; }      // (also reduces every finished parameter)
+        else flush_deferred(c);
+    } else if (c.has_side() && r.p0_on_main) {
+        flush_deferred(c);                // a dozen workgroups, right behind their chain: no hand-over to wait for
+        join_side(c);
+    } else if (c.has_side()) {
+        kick_deferred(c, true);
+        join_side(c);
+    } else {
+        flush_deferred(c);
+    }
+    gi_reduce_desc descs[MAXPARAMS];
+    int nd = 0;
+    auto add_desc = [&](int widx) {
+        SlabEntry& e = c.sp.e[widx];
+        if (e.reduced) return;
+        e.reduced = 1;
+        descs[nd++] = reduce_desc(e, c.slabs, c.grads, widx);
+    };
+    if (phase != GI_BWD_READOUT) {
+        for (int k = 0; k < c.nfam; ++k)
+            for (int t = 0; t < m.d.Fe; ++t) {
+                const Mlp& q = k ? m.eatt[t] : m.msg[t];
+                for (int l = 0; l < q.layers(); ++l) add_desc(q.w(l));
+            }
+        add_desc(m.gru_wih);
+        add_desc(m.gru_whh);
+    }
+    for_readout_params(c, add_desc);
+    if (nd && r.ok()) r.chk(gi_reduce_slabs(descs, nd, rst));
+}
+
+}  // namespace
+
+// ================================ C ABI ==========================================================
+// A stream of the lowest priority the device offers, for gi_ggnn_backward's side_stream: the
+// weight-gradient GEMMs should only fill what the dZ chain (on the caller's stream) leaves idle.
+extern "C" int gi_side_stream_create(void** out) {
+    if (!out) return GI_EINVAL;
+    int least = 0, greatest = 0;
+    hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
+    if (e != hipSuccess) return (int)e;
+    hipStream_t st = nullptr;
+    e = hipStreamCreateWithPriority(&st, hipStreamNonBlocking, least);
+    if (e != hipSuccess) return (int)e;
+    *out = (void*)st;
+    return 0;
+}
+
+extern "C" int gi_side_stream_destroy(void* stream) {
+    if (!stream) return 0;
+    return (int)hipStreamDestroy((hipStream_t)stream);
+}
+
+extern "C" int gi_ggnn_num_params(const gi_ggnn_dims* d) {
+    Model m;
+    const int rc = build_model(d, m);
+    return rc ? rc : m.nparams;
 }
 
 static bool sizes_ok(int S, int E, int U, int D0) {
@@ -1584,319 +2398,6 @@ extern "C" int gi_ggnn_ws_query(const gi_ggnn_dims* d, int S, int E, int U, int 
     return GI_EINVAL;
 }
 
-// AlphaDropout training mode needs the graph without row sharing (gi_compact_count_ex, nodedup): an
-// independent mask per padded slot and per edge
-static int dropout_graph_ok(const gi_ggnn_dims& d, int S, int E, int U, int D0) {
-    if (!d.dropout) return 0;
-    if (S != d.B * d.N || U != E || D0 != 0) return GI_EINVAL;
-    return 0;
-}
-
-// ================================ MNN (GI_KIND_MNN) ===============================================
-// `MNN.forward` = SummationMPNN.forward with the MNN hooks (gnn/summation_mpnn.py:80-149, gnn/mpnn.py:58-74), aggregate
-// first: per pass S_p = gi_typed_seg_sum(h_p) [R, H Fe], messages = S_p . W.view(M, H Fe)^T (one fp32-MFMA GEMM on the
-// parameter as stored), the GRU update of GGNN; readout = the node-level fAddNet1 / fConnNet1 stacks + the graph sum of
-// every slot's h (gi_graph_sum_fwd) into the three places GlobalReadout reads the graph embedding.  The readout keeps
-// GGNN's routes (bf16x3 / fp16x2 layers, dropout sites, split-K graph-level layers).
-static int mnn_forward(const Model& m, const float* const* params, const gi_graph* gp, float* ws, float* out,
-                       int ldout, hipStream_t stream, hipStream_t side_stream, int run_flags) {
-    const gi_ggnn_dims& d = m.d;
-    const int S = gp->S, E = gp->E, U = gp->U;
-    const int* gfix = gp->gfix;
-    if (!params || !gfix || !ws || !out || S < 0 || E < 0 || U < 0 || U > E || !gp->Ut) return GI_EINVAL;
-    if (E > 0 && (!gp->u_src || !gp->in_perm || U == 0)) return GI_EINVAL;
-    if (ldout < m.NA + m.NC + 1 || gp->D0 < 0 || gp->D0 > U) return GI_EINVAL;
-    gi_compact_layout_t L;
-    if (int rc = gi_compact_layout(d.B, d.N, d.Fe, &L)) return rc;
-    if (int drc = dropout_graph_ok(d, S, E, U, gp->D0)) return drc;
-    if (gp->bounded && d.dropout) return GI_EINVAL;
-    Ws w;
-    make_ws(m, S, E, U, gp->D0, w);
-    Run r{stream, params, 0};
-    r.drop = d.dropout != 0; r.seed = d.drop_seed; r.fshift = w.fshift;
-    r.skinny = ws + w.skinny; r.skinny_floats = w.skinny_floats;
-    r.x2 = x2_enabled() && !(run_flags & GI_RUN_NO_X2);
-    r.guard = gp->x2_guard; r.guard_host = gp->x2_guard_host;
-    const int R = w.R;
-    if (gp->bounded) { r.dims = gfix + L.dims; r.R_bound = R; }
-    Wc wc;
-    wcache_layout(m, wc);
-    float* const wcache = (gp->wcache && !r.drop && r.x2 && bf3_enabled()) ? gp->wcache : nullptr;
-    if (wcache && ((uintptr_t)wcache & 15)) return GI_EINVAL;
-    r.wc_valid = wcache && gp->wcache_valid != 0;
-    r.wc_bf3 = wcache ? wcache + wc.bf3_wamax : nullptr;
-    // what depends on the weights only goes to the side stream when there is one (as in gi_ggnn_forward_ex)
-    SideStream fside{side_stream, 0};
-    hipStream_t prep = r.st;
-    if (side_stream) {
-        hipEvent_t start = fside.next();
-        r.chk((int)hipEventRecord(start, r.st));
-        r.chk((int)hipStreamWaitEvent(fside.st, start, 0));
-        prep = fside.st;
-    }
-    if ((run_flags & GI_RUN_PREPACK_BWD) && !r.drop) bf3_prepare(r, m, ws, w, true, R, BF3_DO_PACK, prep);
-    bf3_prepare(r, m, ws, w, false, R, BF3_DO_AMAX, prep);
-    hipEvent_t packed = nullptr, cells_ready = nullptr;
-    if ((run_flags & GI_RUN_PREPACK_BWD) && !r.drop) packed = prepack_stamp(ws, r.x2);
-    else prepack_forget(ws);
-    if (side_stream) {
-        cells_ready = fside.next();
-        r.chk((int)hipEventRecord(cells_ready, fside.st));
-        if (packed) r.chk((int)hipEventRecord(packed, fside.st));
-    } else if (packed) {
-        r.chk((int)hipEventRecord(packed, r.st));
-    }
-    const int* seg_off = gfix + L.seg_off;
-    const int* cidx = gfix + L.cidx;
-    const int* type_off = gfix + L.type_off;
-    const int HF = d.H * d.Fe;
-    // ---- message passes ---------------------------------------------------------------------------
-    for (int p = 0; p < d.passes; ++p) {
-        const float* hx = ws + w.hx[p];
-        r.pass = p;
-        r.chk(gi_typed_seg_sum_n(hx, w.ldhx, gp->u_src, gp->in_perm, seg_off, type_off, R, d.H, d.Fe, ws + w.ssum[p],
-                                 w.ldS, r.dims, r.st));
-        if (r.ok()) {   // messages = S_p . W.view(M, H Fe)^T   (gnn/mpnn.py:58-63 + the sum of :141)
-            gi_gemm_params q;
-            gemm_defaults(q);
-            q.A = ws + w.ssum[p]; q.lda = w.ldS; q.B = params[m.mw]; q.ldb = HF;
-            q.C = ws + w.agg[p]; q.ldc = w.ldM; q.M = R; q.N = d.M; q.K = HF;
-            q.m_dev = r.dims;
-            pick_tile(R, d.M, q.tm, q.tn);
-            r.chk(gi_gemm(&q, r.st));
-        }
-        if (gi_gru_fused_ok(d.H, d.M, w.ldM, w.ldhx, w.ld3H)) {
-            r.chk(gi_gru_fused_fwd(ws + w.agg[p], w.ldM, hx, w.ldhx, params[m.gru_wih], params[m.gru_whh],
-                                   params[m.gru_bih], params[m.gru_bhh], ws + w.gi[p], ws + w.gh[p], w.ld3H,
-                                   ws + w.hx[p + 1], seg_off, R, r.dims, d.H, d.M, r.st));
-            continue;
-        }
-        {
-            Batch b;
-            add_fwd(b, r, params[m.gru_wih], params[m.gru_bih], d.M, 3 * d.H, ws + w.agg[p], w.ldM, R,
-                    ws + w.gi[p], w.ld3H, false);
-            add_fwd(b, r, params[m.gru_whh], params[m.gru_bhh], d.H, 3 * d.H, hx, w.ldhx, R,
-                    ws + w.gh[p], w.ld3H, false);
-            flush_batch(r, b, false);
-        }
-        r.chk(gi_gru_gates_fwd_n(ws + w.gi[p], ws + w.gh[p], w.ld3H, hx, ws + w.hx[p + 1], w.ldhx,
-                                 seg_off, R, d.H, d.Fn, r.dims, r.st));
-    }
-    // ---- readout (gnn/mpnn.py:69-74) ----------------------------------------------------------------
-    if (cells_ready) r.chk((int)hipStreamWaitEvent(r.st, cells_ready, 0));
-    const float* hx = ws + w.hx[d.passes];
-    {
-        MlpJob jobs[2] = {};
-        jobs[0] = {&m.add1, hx, w.ldhx, R, w.add1_act, w.ldM1, ws + w.add1o, w.ldA};
-        jobs[1] = {&m.conn1, hx, w.ldhx, R, w.conn1_act, w.ldM1, ws + w.conn1o, w.ldC};
-        mlp_jobs_forward(r, ws, jobs, 2);
-    }
-    if (r.ok())
-        r.chk(gi_graph_sum_fwd(hx, w.ldhx, cidx, d.B, d.N, d.H, ws + w.cat_add + m.NA, w.ldCA, ws + w.cat_conn + m.NC,
-                               w.ldCC, ws + w.gemb, w.ldG, r.st));
-    if (gi_fuse_flags() & GI_FUSE_SLOTS) {
-        r.chk(gi_expand_slots2(ws + w.add1o, w.ldA, d.A, ws + w.cat_add, w.ldCA, ws + w.conn1o, w.ldC, d.C,
-                               ws + w.cat_conn, w.ldCC, cidx, d.B, d.N, r.st));
-    } else {
-        r.chk(gi_expand_slots(ws + w.add1o, w.ldA, cidx, d.B, d.N, d.A, ws + w.cat_add, w.ldCA, r.st));
-        r.chk(gi_expand_slots(ws + w.conn1o, w.ldC, cidx, d.B, d.N, d.C, ws + w.cat_conn, w.ldCC, r.st));
-    }
-    {
-        MlpJob jobs[3] = {};
-        jobs[0] = {&m.add2, ws + w.cat_add, w.ldCA, d.B, w.add2_act, w.ldM2, out, ldout};
-        jobs[1] = {&m.conn2, ws + w.cat_conn, w.ldCC, d.B, w.conn2_act, w.ldM2, out + m.NA, ldout};
-        jobs[2] = {&m.term2, ws + w.gemb, w.ldG, d.B, w.term2_act, w.ldM2, out + m.NA + m.NC, ldout};
-        for (MlpJob& j : jobs) j.out_fshift = r.drop ? (long long)d.B * ldout : 0;
-        mlp_jobs_forward(r, ws, jobs, 3);
-    }
-    if (side_stream && packed) r.chk((int)hipStreamWaitEvent(r.st, packed, 0));
-    if (!r.ok()) prepack_forget(ws);
-    return r.rc;
-}
-
-// The MNN backward, in the phases of gi_ggnn_backward_phase: GI_BWD_READOUT = GlobalReadout + the graph sum (d h of the
-// last pass: dh, dhb from the two node-level stacks, dhc from the graph sum), GI_BWD_PASSES = the GRU, the message
-// GEMMs and the transposed typed sum, then dW = sum over passes of dagg_p^T S_p as ONE split-K GEMM over all passes.
-static int mnn_backward(const Model& m, const float* const* params, const gi_graph* gp, float* ws, float* slabs,
-                        const float* y_out, int ldout, const float* d_out, int lddout, float* const* grads,
-                        hipStream_t stream, hipStream_t side_stream, int phase, bool prepacked, bool no_x2) {
-    const gi_ggnn_dims& d = m.d;
-    const int S = gp->S, E = gp->E, U = gp->U;
-    const int* gfix = gp->gfix;
-    const int* Ut = gp->Ut;
-    if (!params || !gfix || !ws || !slabs || !y_out || !d_out || !grads || S < 0 || E < 0 || U < 0 || U > E || !Ut)
-        return GI_EINVAL;
-    if (E > 0 && (!gp->u_src || !gp->in_perm || !gp->mu_off || !gp->mu_dst || !gp->out_perm || U == 0))
-        return GI_EINVAL;
-    if (gp->wcache || gp->bounded || gp->D0 < 0 || gp->D0 > U) return GI_EINVAL;
-    gi_compact_layout_t L;
-    if (int rc = gi_compact_layout(d.B, d.N, d.Fe, &L)) return rc;
-    if (int drc = dropout_graph_ok(d, S, E, U, gp->D0)) return drc;
-    Ws w;
-    make_ws(m, S, E, U, gp->D0, w);
-    SlabPlan sp;
-    plan_slabs(m, S, U, Ut, sp);
-    Run r{stream, params, 0};
-    r.drop = d.dropout != 0; r.seed = d.drop_seed; r.fshift = w.fshift;
-    r.skinny = ws + w.skinny; r.skinny_floats = w.skinny_floats;
-    r.x2 = x2_enabled() && !no_x2;
-    r.guard = gp->x2_guard; r.guard_host = nullptr;
-    if (prepacked) {
-        if (hipEvent_t ev = prepack_lookup(ws, r.x2)) r.chk((int)hipStreamWaitEvent(r.st, ev, 0));
-        else prepacked = false;
-    }
-    const long long out_fshift = r.drop ? (long long)d.B * ldout : 0;
-    const int R = w.R;
-    const int* seg_off = gfix + L.seg_off;
-    const int* src_off = gfix + L.src_off;
-    const int* cidx = gfix + L.cidx;
-    const int* type_off = gfix + L.type_off;
-    const int NA = m.NA, NC = m.NC, HF = d.H * d.Fe;
-    Deferred dq;
-    SideStream side_obj{side_stream, 0};
-    r.side = side_stream ? &side_obj : nullptr;
-    r.sp = &sp; r.slabs = slabs; r.grads = grads;
-    r.wgrad_x2 = wgrad_x2_pool_possible(m, r.x2);
-    r.pool.base = r.wgrad_x2 ? ws + w.amax_pool : nullptr;
-    const Grp none{0, nullptr, 0};
-    const float* hxP = ws + w.hx[d.passes];
-    float* dh = ws + w.dh;
-    float* dh2 = ws + w.dh2;
-    float* dhb = ws + w.dhb;
-    float* dhc = ws + w.dhc;
-    auto readout_params = [&](auto&& fn) {
-        const Mlp* stacks[] = {&m.add1, &m.conn1, &m.add2, &m.conn2, &m.term2};
-        for (const Mlp* q : stacks)
-            for (int l = 0; l < q->layers(); ++l) fn(q->w(l));
-    };
-    if (phase == GI_BWD_PASSES) readout_params([&](int widx) { sp.e[widx].reduced = 1; });
-    if (phase != GI_BWD_PASSES) {
-        bf3_prepare(r, m, ws, w, true, S + 1, prepacked ? 0 : BF3_DO_PACK, r.st);
-        r.chk(gi_selu_bwd_cols3_f(d_out, lddout, y_out, ldout, out_fshift, d.B, NA, ws + w.dzA, w.ldNA, NC,
-                                  ws + w.dzC, w.ldNC, 1, ws + w.dzT, 4, r.st));
-        {
-            MlpJob jobs[3] = {};
-            jobs[0] = {&m.add2, ws + w.cat_add, w.ldCA, d.B, w.add2_act, w.ldM2, nullptr, 0, w.add2_dz,
-                       ws + w.dzA, w.ldNA, ws + w.dcat_add, w.ldCA, NA + d.G, false};
-            jobs[1] = {&m.conn2, ws + w.cat_conn, w.ldCC, d.B, w.conn2_act, w.ldM2, nullptr, 0,
-                       w.conn2_dz, ws + w.dzC, w.ldNC, ws + w.dcat_conn, w.ldCC, NC + d.G, false};
-            jobs[2] = {&m.term2, ws + w.gemb, w.ldG, d.B, w.term2_act, w.ldM2, nullptr, 0, w.term2_dz,
-                       ws + w.dzT, 4, ws + w.dgemb, w.ldG, d.G, false};
-            mlp_jobs_backward(r, ws, sp, slabs, dq, jobs, 3);
-        }
-        r.chk(gi_compress_slots2_f(ws + w.add1o, w.ldA, d.A, ws + w.dcat_add, w.ldCA, ws + w.zpart_a, w.ldA,
-                                   ws + w.conn1o, w.ldC, d.C, ws + w.dcat_conn, w.ldCC, ws + w.zpart_c,
-                                   w.ldC, cidx, d.B, d.N, S, r.fshift, r.st));
-        {   // zero-row gradients of the two node-level stacks: per-graph partial sums -> row S
-            float* add_z = ws + w.add1o + (long long)S * w.ldA;
-            float* conn_z = ws + w.conn1o + (long long)S * w.ldC;
-            const gi_colsum_desc cs[2] = {
-                {ws + w.zpart_a, w.ldA, d.B, d.A, add_z, add_z},
-                {ws + w.zpart_c, w.ldC, d.B, d.C, conn_z, conn_z}};
-            r.chk(gi_colsum_multi(cs, 2, r.st));
-        }
-        {
-            MlpJob jobs[2] = {};
-            jobs[0] = {&m.add1, hxP, w.ldhx, R, w.add1_act, w.ldM1, nullptr, 0, w.add1_dz, ws + w.add1o,
-                       w.ldA, dh, w.ldH, d.H, false};
-            jobs[1] = {&m.conn1, hxP, w.ldhx, R, w.conn1_act, w.ldM1, nullptr, 0, w.conn1_dz,
-                       ws + w.conn1o, w.ldC, dhb, w.ldH, d.H, false};
-            r.hold_kicks = R <= HOLD_KICKS_MAX_ROWS;
-            mlp_jobs_backward(r, ws, sp, slabs, dq, jobs, 2);
-            r.hold_kicks = false;
-            if (r.side) kick_deferred(r, dq, r.side, false);
-        }
-        // graph sum: every row of graph b gets d g[b] summed over its three consumers (dhc; the zero row: 0)
-        if (r.ok())
-            r.chk(gi_graph_sum_bwd(ws + w.dgemb, w.ldG, ws + w.dcat_add + NA, w.ldCA, ws + w.dcat_conn + NC, w.ldCC,
-                                   gfix + L.slot_of, S, d.N, d.H, dhc, w.ldH, 0, r.st));
-    }
-    if (phase == GI_BWD_READOUT) {
-        hipStream_t rst = r.side ? r.side->st : r.st;
-        if (r.side) kick_deferred(r, dq, r.side, true);
-        else flush_deferred(r, dq);
-        gi_reduce_desc descs[MAXPARAMS];
-        int nd = 0;
-        readout_params([&](int widx) {
-            if (sp.e[widx].reduced) return;
-            sp.e[widx].reduced = 1;
-            descs[nd++] = reduce_desc(sp.e[widx], slabs, grads, widx);
-        });
-        if (nd && r.ok()) r.chk(gi_reduce_slabs(descs, nd, rst));
-        return r.rc;
-    }
-    // ---- message passes, reversed -------------------------------------------------------------------
-    for (int p = d.passes - 1; p >= 0; --p) {
-        const float* hx = ws + w.hx[p];
-        float* gi = ws + w.gi[p];
-        float* gh = ws + w.gh[p];
-        float* agg = ws + w.agg[p];
-        float* dagg = ws + w.dagg[p];
-        const bool last = (p == d.passes - 1);
-        r.chk(gi_gru_gates_bwd(gi, gh, w.ld3H, hx, w.ldhx, dh, last ? dhb : nullptr, last ? dhc : nullptr, nullptr,
-                               dh2, w.ldH, seg_off, R, d.H, r.st));
-        {
-            const int wih = m.gru_wih, whh = m.gru_whh;
-            defer_wgrad(r, dq, sp, slabs, &wih, none, gi, w.ld3H, agg, w.ldM, nullptr, R);
-            defer_wgrad(r, dq, sp, slabs, &whh, none, gh, w.ld3H, hx, w.ldhx, nullptr, R);
-            Batch bd;
-            add_dgrad(bd, r, m.gru_wih, 3 * d.H, d.M, d.M, gi, w.ld3H, R, dagg, w.ldM, nullptr, 0, false);
-            if (p > 0)
-                add_dgrad(bd, r, m.gru_whh, 3 * d.H, d.H, d.H, gh, w.ld3H, R, dh2, w.ldH, nullptr, 0, true);
-            flush_batch(r, bd, false);
-        }
-        if (p > 0 && E > 0 && r.ok()) {
-            // dS = dagg . W.view(M, H Fe), then d h_src += the transposed typed sum of dS
-            gi_gemm_params q;
-            gemm_defaults(q);
-            q.A = dagg; q.lda = w.ldM; q.B = params[m.mw]; q.ldb = HF; q.b_major = 1;
-            q.C = ws + w.dS; q.ldc = w.ldS; q.M = R; q.N = HF; q.K = d.M;
-            pick_tile(R, HF, q.tm, q.tn);
-            r.chk(gi_gemm(&q, r.st));
-            if (r.ok())
-                r.chk(gi_typed_seg_sum_t(ws + w.dS, w.ldS, gp->out_perm, src_off, gp->mu_off, gp->mu_dst, type_off, R,
-                                         d.H, d.Fe, dh2, w.ldH, 1, r.st));
-        }
-        std::swap(dh, dh2);
-    }
-    // dW.view(M, H Fe) = sum over passes of dagg_p^T S_p: the passes' buffers are contiguous -> one reduction of
-    // passes * R rows, split-K into slabs, summed in a fixed order
-    if (d.passes > 0 && r.ok()) {
-        gi_gemm_params q;
-        gemm_defaults(q);
-        q.A = ws + w.dagg[0]; q.lda = w.ldM; q.a_major = 1;
-        q.B = ws + w.ssum[0]; q.ldb = w.ldS; q.b_major = 1;
-        q.C = ws + w.mslab; q.ldc = w.ldS; q.M = d.M; q.N = HF; q.K = d.passes * R;
-        q.flags = GI_GEMM_SPLITK; q.nsplit = w.mslab_split; q.c_split_stride = w.mslab_stride;
-        q.tm = 1; q.tn = 1;
-        r.chk(gi_gemm(&q, r.st));
-        if (r.ok())
-            r.chk(gi_slab_epilogue(ws + w.mslab, w.mslab_split, w.mslab_stride, d.M, HF, w.ldS, 0, nullptr, nullptr, 0,
-                                   grads[m.mw], HF, r.st));
-    } else if (r.ok()) {
-        r.chk((int)hipMemsetAsync(grads[m.mw], 0, sizeof(float) * (size_t)d.M * HF, r.st));
-    }
-    if (r.side) {
-        kick_deferred(r, dq, r.side, true);
-        join_side(r, r.side);
-    } else {
-        flush_deferred(r, dq);
-    }
-    gi_reduce_desc descs[MAXPARAMS];
-    int nd = 0;
-    auto add_desc = [&](int widx) {
-        SlabEntry& e = sp.e[widx];
-        if (e.reduced) return;
-        e.reduced = 1;
-        descs[nd++] = reduce_desc(e, slabs, grads, widx);
-    };
-    add_desc(m.gru_wih);
-    add_desc(m.gru_whh);
-    readout_params([&](int widx) { add_desc(widx); });
-    if (nd && r.ok()) r.chk(gi_reduce_slabs(descs, nd, r.st));
-    return r.rc;
-}
-
 extern "C" int gi_ggnn_forward(const gi_ggnn_dims* dp, const float* const* params,
                                const gi_graph* gp, float* ws, float* out, int ldout, void* stream) {
     return gi_ggnn_forward_ex(dp, params, gp, ws, out, ldout, stream, nullptr, 0);
@@ -1907,295 +2408,25 @@ extern "C" int gi_ggnn_forward_ex(const gi_ggnn_dims* dp, const float* const* pa
                                   void* side_stream, int run_flags) {
     (void)hipGetLastError();   // drop stale errors of earlier, unrelated runtime calls
     if (run_flags & ~(GI_RUN_PREPACK_BWD | GI_RUN_NO_X2)) return GI_EINVAL;
-    Model m;
-    int rc = build_model(dp, m);
-    if (rc) return rc;
-    if (!gp) return GI_EINVAL;
-    if (m.mnn) return mnn_forward(m, params, gp, ws, out, ldout, (hipStream_t)stream, (hipStream_t)side_stream, run_flags);
-    const int S = gp->S, E = gp->E, U = gp->U;
-    const int* gfix = gp->gfix;
-    const int* u_src = gp->u_src;
-    const int* in_perm = gp->in_perm;
-    const int* Ut = gp->Ut;
-    if (!params || !gfix || !ws || !out || S < 0 || E < 0 || U < 0 || U > E || !Ut) return GI_EINVAL;
-    if (E > 0 && (!u_src || !in_perm || U == 0)) return GI_EINVAL;
-    const gi_ggnn_dims& d = m.d;
-    if (ldout < m.NA + m.NC + 1) return GI_EINVAL;
-    if (d.kind == GI_KIND_ATTGGNN && E == 0) in_perm = in_perm ? in_perm : gfix;   // never read
-    gi_compact_layout_t L;
-    rc = gi_compact_layout(d.B, d.N, d.Fe, &L);
-    if (rc) return rc;
-    Ws w;
-    if (gp->D0 < 0 || gp->D0 > U || (gp->D0 > 0 && (!gp->d_src || !gp->cmat || gp->ldc0 < gp->D0)))
-        return GI_EINVAL;
-    if (d.kind == GI_KIND_ATTGGNN && gp->D0 > 0 && (!gp->e2d || !gp->cls_off || !gp->cls_edges))
-        return GI_EINVAL;
-    if (int drc = dropout_graph_ok(d, S, E, U, gp->D0)) return drc;
-    if (gp->bounded && (d.dropout || gp->D0 <= 0)) return GI_EINVAL;   // (bounded: S, E, U, D0 are bounds)
-    make_ws(m, S, E, U, gp->D0, w);
-    Run r{(hipStream_t)stream, params, 0};
-    r.drop = d.dropout != 0; r.seed = d.drop_seed; r.fshift = w.fshift;
-    r.skinny = ws + w.skinny; r.skinny_floats = w.skinny_floats;
-    r.x2 = x2_enabled() && !(run_flags & GI_RUN_NO_X2);
-    r.guard = gp->x2_guard; r.guard_host = gp->x2_guard_host;
-    const int R = w.R;
-    if (gp->bounded) { r.dims = gfix + L.dims; r.d0_dev = gfix + L.counts + 20; r.R_bound = R; }
-    int maxUt = 0;
-    for (int t = 0; t < d.Fe; ++t) maxUt = std::max(maxUt, Ut[t]);
-    const Grp bytype{d.Fe, gfix + L.type_off, maxUt, Ut};
-    Grp bytype0{d.Fe, gfix + L.type_off0, w.D0};   // pass-0 rows (upper bound per type: all)
-    bytype0.dim_slot = 2;
-    const int* seg_off = gfix + L.seg_off;
-    const int* cidx = gfix + L.cidx;
-    const int* mask = gfix + L.node_mask;
-    const bool attn = d.kind == GI_KIND_ATTGGNN;
-
-    r.eatt0 = m.eatt;
-    // gi_graph.wcache: the weights-only data of this forward live in (and, when valid, come from) the caller's cache
-    Wc wc;
-    wcache_layout(m, wc);
-    float* const wcache = (gp->wcache && !r.drop && r.x2 && bf3_enabled()) ? gp->wcache : nullptr;
-    if (wcache && ((uintptr_t)wcache & 15)) return GI_EINVAL;
-    r.wc_valid = wcache && gp->wcache_valid != 0;
-    r.wc_bf3 = wcache ? wcache + wc.bf3_wamax : nullptr;
-    // Packed weight images of the chain kernel, once per forward.  A forward whose chains do not run (no edges) still
-    // derives the fp16x2 image, its cells and (below) its weight guard into a cache that is not valid yet: the caller
-    // marks the cache valid after this call, and a later forward with edges reads the image from it.
-    const bool chains_run = d.passes > 0 && E > 0;
-    float* guard_cells[2] = {nullptr, nullptr};     // the forward chains' max |W| cells packed by this call
-    for (int k = 0; k < (attn ? 2 : 1); ++k) {
-        if (w.img_f_n[k] <= 0) continue;
-        const bool fx = !r.drop && chain_x2_enabled(r.x2);      // the row-independent fp16x2 chain, not the fp32 one
-        const bool cached = fx && wcache && wc.img_fx[k] >= 0;
-        if (!chains_run && !(cached && !r.wc_valid)) continue;
-        if (fx) {
-            float* const img = cached ? wcache + wc.img_fx[k] : ws + w.img_fx[k];
-            float* const cells = cached ? wcache + wc.chain_amax_f[k] : ws + w.chain_amax_f[k];
-            if (!(r.wc_valid && cached)) {
-                Run rp = r;
-                rp.chain_amax[k] = cells;
-                chain_pack(rp, k ? m.eatt : m.msg, d.Fe, false, img);
-                r.chk(rp.rc);
-                guard_cells[k] = cells;
-            }
-            if (chains_run) {
-                r.img_fx[k] = img;
-                r.chain_amax_f[k] = cells;
-                r.img_f[k] = r.img_fx[k];                       // (nothing may read the fp32 image: it was not packed)
-            }
-        } else {
-            r.img_f[k] = ws + w.img_f[k];
-            chain_pack(r, k ? m.eatt : m.msg, d.Fe, false, r.img_f[k]);
-        }
-    }
-    // Everything else that depends on the weights only goes to the side stream when there is one: the amax cells of
-    // the fp16x2 layers (needed by the readout, hundreds of microseconds from here) and — GI_RUN_PREPACK_BWD — the
-    // images the backward would otherwise pack at its start, in front of its first launches.
-    SideStream fside{(hipStream_t)side_stream, 0};
-    hipStream_t prep = r.st;
-    hipEvent_t cells_ready = nullptr;
-    if (side_stream) {
-        hipEvent_t start = fside.next();
-        r.chk((int)hipEventRecord(start, r.st));            // (the weights were last written on the caller's stream)
-        r.chk((int)hipStreamWaitEvent(fside.st, start, 0));
-        prep = fside.st;
-    }
-    // amax cells of the message / energy stacks' activations (this forward's chains publish into them, the backward's
-    // chains add the dZ maxima, its fp16x2 weight gradients read both): zeroed first thing on the side stream
-    const bool msgx = E > 0 && d.passes > 0 && msg_wgrad_x2_possible(m, r.x2);
-    float* msg_cells_base[2] = {nullptr, nullptr};
-    hipEvent_t msg_cells_ready = nullptr;
-    if (msgx) {
-        for (int k = 0; k < (attn ? 2 : 1); ++k)
-            if (w.img_f_n[k] > 0 && r.img_fx[k]) {
-                msg_cells_base[k] = ws + w.msg_amax[k];
-                r.chk((int)hipMemsetAsync(msg_cells_base[k], 0, sizeof(float) * MSG_CELLS_PER_PASS * d.passes, prep));
-            }
-        if (side_stream) {
-            msg_cells_ready = fside.next();
-            r.chk((int)hipEventRecord(msg_cells_ready, fside.st));
-        }
-    }
-    if ((run_flags & GI_RUN_PREPACK_BWD) && !r.drop) {
-        bf3_prepare(r, m, ws, w, true, R, BF3_DO_PACK, prep);
-        if (d.passes > 0 && E > 0)
-            for (int k = 0; k < (attn ? 2 : 1); ++k)
-                if (w.img_b_n[k] > 0) {
-                    Run rp = r;                                   // (chain_pack reads the stream and the flavour from its Run)
-                    rp.st = prep;
-                    rp.chain_amax[k] = chain_x2_enabled(r.x2) ? ws + w.chain_amax[k] : nullptr;
-                    chain_pack(rp, k ? m.eatt : m.msg, d.Fe, true, ws + w.img_b[k]);
-                    r.chk(rp.rc);
-                }
-    }
-    // the forward chains' weights through the fp16x2 guard (output channels / input columns below the per-tensor range)
-    if (r.guard && r.ok())
-        for (int k = 0; k < (attn ? 2 : 1); ++k)
-            if (guard_cells[k]) {
-                const Mlp* mlps = k ? m.eatt : m.msg;
-                gi_absmax_desc wd[GI_ABSMAX_MAX];
-                int n = 0;
-                const int L = mlps[0].layers();
-                for (int l = 0; l < L; ++l)
-                    for (int t = 0; t < d.Fe; ++t) {
-                        wd[n].x = r.P[mlps[t].w(l)]; wd[n].rows = mlps[0].fan_out(l); wd[n].cols = mlps[0].fan_in(l);
-                        wd[n].ld = wd[n].cols;
-                        wd[n].out = guard_cells[k] + ((long long)l * d.Fe + t) * GI_AMAX_WORDS;
-                        if (++n == GI_ABSMAX_MAX || (l == L - 1 && t == d.Fe - 1)) {
-                            r.chk(gi_x2_weight_guard(wd, n, r.guard + 1, r.guard_host, prep));
-                            n = 0;
-                        }
-                    }
-            }
-    bf3_prepare(r, m, ws, w, false, R, BF3_DO_AMAX, prep);
-    hipEvent_t packed = nullptr;                  // this workspace's "images written" event (prepack_stamp)
-    if ((run_flags & GI_RUN_PREPACK_BWD) && !r.drop) packed = prepack_stamp(ws, r.x2);
-    else prepack_forget(ws);
-    if (side_stream) {
-        cells_ready = fside.next();
-        r.chk((int)hipEventRecord(cells_ready, fside.st));
-        if (packed) r.chk((int)hipEventRecord(packed, fside.st));
-    } else if (packed) {
-        r.chk((int)hipEventRecord(packed, r.st));
-    }
-    // pass-0 row cache (inference loops): only in front of the one-launch stack path, whose kernel can skip
-    int* const p0c = static_cast<int*>(gp->p0_cache);
-    const bool p0cache = p0c && w.D0 > 0 && E > 0 && !r.drop && r.img_f[0] && (!attn || r.img_f[1]) &&
-                         w.ldhx >= gi_r4(m.msg[0].in);
+    Call c;
+    c.out = out; c.ldout = ldout;
+    if (int rc = open_call(c, false, dp, params, gp, ws, stream, side_stream, (run_flags & GI_RUN_NO_X2) != 0)) return rc;
+    Run& r = c.r;
+    weights_prologue_fwd(c, (run_flags & GI_RUN_PREPACK_BWD) && !r.drop);
     // ---- message passes (gnn/summation_mpnn.py:128-144) ----------------------------------------
-    for (int p = 0; p < d.passes; ++p) {
-        const float* hx = ws + w.hx[p];
-        r.pass = p;
-        for (int k = 0; k < 2; ++k)     // (pass 0 on the class rows: one-slab fp32 weight gradients, no cells)
-            r.msg_cells[k] = (msg_cells_base[k] && !(p == 0 && w.D0 > 0)) ? msg_cells_base[k] + p * MSG_CELLS_PER_PASS : nullptr;
-        if (msg_cells_ready && (r.msg_cells[0] || r.msg_cells[1])) {
-            r.chk((int)hipStreamWaitEvent(r.st, msg_cells_ready, 0));    // (zeroed ~100 us ago: never stalls)
-            msg_cells_ready = nullptr;
-        }
-        if (p == 0 && p0cache) {
-            r.chk(gi_p0_cache_lookup(gfix, d.B, d.N, d.Fe, p0c, attn ? 2 : 1, ws + w.m[0],
-                                     attn ? ws + w.een[0] : nullptr, w.ldM, r.st));
-            r.skip = p0c;
-        }
-        if (attn) {
-            // AttentionGGNN.aggregate_message (gnn/mpnn.py:370-389): message and energy MLPs of the
-            // edge's bond type on h_src(e), softmax over each node's incoming edges, weighted sum
-            // pass 0 (h = [x | 0]): both MLP families on the D0 (feature class, bond type) rows, the
-            // softmax reads them through the edge -> pass-0 row index
-            const bool p0 = p == 0 && w.D0 > 0;
-            if (E > 0) {
-                EdgeChain ch[2] = {
-                    {m.msg, w.eact[p], w.edz[p], w.ldEh, ws + w.m[p], w.ldM, nullptr},
-                    {m.eatt, w.aact[p], w.adz[p], w.ldEa, ws + w.een[p], w.ldM, nullptr}};
-                if (p0) edge_chains_forward(r, ws, ch, 2, bytype0, hx, w.ldhx, gp->d_src, w.D0);
-                else edge_chains_forward(r, ws, ch, 2, bytype, hx, w.ldhx, u_src, U);
-                if (p0 && p0cache) {
-                    r.skip = nullptr;
-                    r.chk(gi_p0_cache_insert(gfix, d.B, d.N, d.Fe, p0c, 2, ws + w.m[0], ws + w.een[0], w.ldM, r.st));
-                }
-            }
-            r.chk(gi_seg_softmax_fwd_n(ws + w.een[p], ws + w.m[p], w.ldM, p0 ? gp->e2d : in_perm, seg_off,
-                                       R, d.M, ws + w.agg[p], w.ldM, r.dims, r.st));
-        } else if (p == 0 && w.D0 > 0) {
-            // pass 0: h = [x | 0], one message row per (feature class, bond type); a_v = cmat . m0
-            mlp_forward(r, ws, m.msg, bytype0, hx, w.ldhx, gp->d_src, w.D0, w.eact[0], w.ldEh,
-                        ws + w.m[0], w.ldM);
-            if (p0cache) {
-                r.skip = nullptr;
-                r.chk(gi_p0_cache_insert(gfix, d.B, d.N, d.Fe, p0c, 1, ws + w.m[0], nullptr, w.ldM, r.st));
-            }
-            if (r.ok()) {
-                gi_gemm_params q;
-                gemm_defaults(q);
-                q.A = gp->cmat; q.lda = gp->ldc0; q.B = ws + w.m[0]; q.ldb = w.ldM; q.b_major = 1;
-                q.C = ws + w.agg[0]; q.ldc = w.ldM; q.M = R; q.N = d.M; q.K = w.D0;
-                q.m_dev = r.dims; q.k_dev = r.d0_dev;      // (bounded forward: R and D0 live on the device)
-                q.tm = 1; q.tn = 1;
-                r.chk(gi_gemm(&q, r.st));
-            }
-        } else {
-            if (E > 0)   // m_u = MLP_type(u)(h_src(u)), gnn/mpnn.py:284-294, once per message row
-                mlp_forward(r, ws, m.msg, bytype, hx, w.ldhx, u_src, U, w.eact[p], w.ldEh,
-                            ws + w.m[p], w.ldM);
-            // a_v = sum of incoming messages (:141): inside the GRU update's launch (GI_GLUE_GRU_AGG) ...
-            if ((gi_glue_flags() & GI_GLUE_GRU_AGG) && gi_gru_fused_agg_ok(d.H, d.M, w.ldM, w.ldhx, w.ld3H, w.ldM) &&
-                gi_gru_fused_agg_pays(R, d.H)) {
-                r.chk(gi_gru_fused_agg_fwd(ws + w.m[p], w.ldM, in_perm, ws + w.agg[p], w.ldM, hx, w.ldhx,
-                                           params[m.gru_wih], params[m.gru_whh], params[m.gru_bih], params[m.gru_bhh],
-                                           ws + w.gi[p], ws + w.gh[p], w.ld3H, ws + w.hx[p + 1], seg_off, R, r.dims,
-                                           d.H, d.M, r.st));
-                continue;
-            }
-            // ... or in a launch of its own
-            r.chk(gi_seg_sum_n(ws + w.m[p], w.ldM, in_perm, seg_off, R, d.M, ws + w.agg[p], w.ldM, 0, r.dims,
-                               r.st));
-        }
-        // GRU update (gnn/mpnn.py:296-297): projections + gates in ONE launch (gi_gru.hip, round 6) ...
-        if (gi_gru_fused_ok(d.H, d.M, w.ldM, w.ldhx, w.ld3H)) {
-            r.chk(gi_gru_fused_fwd(ws + w.agg[p], w.ldM, hx, w.ldhx, params[m.gru_wih], params[m.gru_whh],
-                                   params[m.gru_bih], params[m.gru_bhh], ws + w.gi[p], ws + w.gh[p], w.ld3H,
-                                   ws + w.hx[p + 1], seg_off, R, r.dims, d.H, d.M, r.st));
-            continue;
-        }
-        // ... or (widths that are not multiples of 4): both input projections in one launch, then the gate kernel
-        {
-            Batch b;
-            add_fwd(b, r, params[m.gru_wih], params[m.gru_bih], d.M, 3 * d.H, ws + w.agg[p], w.ldM, R,
-                    ws + w.gi[p], w.ld3H, false);
-            add_fwd(b, r, params[m.gru_whh], params[m.gru_bhh], d.H, 3 * d.H, hx, w.ldhx, R,
-                    ws + w.gh[p], w.ld3H, false);
-            flush_batch(r, b, false);
-        }
-        r.chk(gi_gru_gates_fwd_n(ws + w.gi[p], ws + w.gh[p], w.ld3H, hx, ws + w.hx[p + 1], w.ldhx,
-                                 seg_off, R, d.H, d.Fn, r.dims, r.st));
+    for (int p = 0; p < c.m.d.passes; ++p) {
+        pass_cells_fwd(c, p);
+        if (c.m.mnn) msg_fwd_mnn(c, p);
+        else if (c.attn) msg_fwd_attggnn(c, p);
+        else if (msg_fwd_ggnn(c, p)) continue;
+        gru_update_fwd(c, p);
     }
-    // ---- readout (gnn/mpnn.py:299-303) -----------------------------------------------------------
-    if (cells_ready) r.chk((int)hipStreamWaitEvent(r.st, cells_ready, 0));     // amax cells zeroed, max |W| in them
-    const float* hx = ws + w.hx[d.passes];
-    {   // the four node-level stacks, layer by layer in shared launches
-        MlpJob jobs[4] = {};
-        // widest stacks first: their workgroups run twice as long (K = 500 against 250), so the
-        // launch's last, partially filled round of workgroups consists of the short ones
-        jobs[0] = {&m.add1, hx, w.ldhx, R, w.add1_act, w.ldM1, ws + w.add1o, w.ldA};
-        jobs[1] = {&m.conn1, hx, w.ldhx, R, w.conn1_act, w.ldM1, ws + w.conn1o, w.ldC};
-        jobs[2] = {&m.att, hx, w.ldhx, R, w.att_act, w.ldAtt, ws + w.en, w.ldG};
-        jobs[3] = {&m.emb, hx, w.ldhx, R, w.emb_act, w.ldEmb, ws + w.embo, w.ldG};
-        mlp_jobs_forward(r, ws, jobs, 4);
-    }
-    if (gi_glue_flags() & GI_GLUE_READOUT_FWD) {     // gather + tier-1 expansion in one launch
-        r.chk(gi_readout_glue_fwd(ws + w.en, ws + w.embo, w.ldG, cidx, mask, d.B, d.N, d.G, d.big_positive,
-                                  ws + w.cat_add + m.NA, w.ldCA, ws + w.cat_conn + m.NC, w.ldCC, ws + w.gemb, w.ldG,
-                                  ws + w.add1o, w.ldA, d.A, ws + w.cat_add, w.ldCA, ws + w.conn1o, w.ldC, d.C,
-                                  ws + w.cat_conn, w.ldCC, r.st));
-    } else {
-        r.chk(gi_gather_readout_fwd(ws + w.en, ws + w.embo, w.ldG, cidx, mask, d.B, d.N, d.G,
-                                    d.big_positive, ws + w.cat_add + m.NA, w.ldCA,
-                                    ws + w.cat_conn + m.NC, w.ldCC, ws + w.gemb, w.ldG, r.st));
-        if (gi_fuse_flags() & GI_FUSE_SLOTS) {
-            r.chk(gi_expand_slots2(ws + w.add1o, w.ldA, d.A, ws + w.cat_add, w.ldCA, ws + w.conn1o, w.ldC, d.C,
-                                   ws + w.cat_conn, w.ldCC, cidx, d.B, d.N, r.st));
-        } else {
-            r.chk(gi_expand_slots(ws + w.add1o, w.ldA, cidx, d.B, d.N, d.A, ws + w.cat_add, w.ldCA, r.st));
-            r.chk(gi_expand_slots(ws + w.conn1o, w.ldC, cidx, d.B, d.N, d.C, ws + w.cat_conn, w.ldCC, r.st));
-        }
-    }
-    {   // the three graph-level stacks write straight into the logits
-        MlpJob jobs[3] = {};
-        jobs[0] = {&m.add2, ws + w.cat_add, w.ldCA, d.B, w.add2_act, w.ldM2, out, ldout};
-        jobs[1] = {&m.conn2, ws + w.cat_conn, w.ldCC, d.B, w.conn2_act, w.ldM2, out + m.NA, ldout};
-        jobs[2] = {&m.term2, ws + w.gemb, w.ldG, d.B, w.term2_act, w.ldM2, out + m.NA + m.NC, ldout};
-        // dropout mode: `out` is [2 B, ldout]; rows [B, 2 B) take the factors of the logits
-        for (MlpJob& j : jobs) j.out_fshift = r.drop ? (long long)d.B * ldout : 0;
-        mlp_jobs_forward(r, ws, jobs, 3);
-    }
-    // Whatever the caller enqueues on `stream` after this call — the backward, or a kernel that reuses the workspace's
-    // memory because the tape was dropped without one — is ordered behind the side stream's packs into `ws` (they
-    // finished hundreds of microseconds ago: a wait that never stalls).  The caller therefore needs no cross-stream
-    // bookkeeping of its own for `ws` (torch: no Tensor.record_stream, which would keep the caching allocator from
-    // reusing the block until the low-priority side stream has drained).
-    if (side_stream && packed) r.chk((int)hipStreamWaitEvent(r.st, packed, 0));
-    if (!r.ok()) prepack_forget(ws);              // (a failed forward's images are not to be trusted)
-    return r.rc;
+    // ---- readout ---------------------------------------------------------------------------------
+    if (c.cells_ready) r.chk((int)hipStreamWaitEvent(r.st, c.cells_ready, 0));     // amax cells zeroed, max |W| in them
+    node_stacks_fwd(c);
+    gather_fwd(c);
+    graph_stacks_fwd(c);
+    return epilogue_fwd(c);
 }
 
 // fp16x2 instead of bf16x3 on the GI_GEMM_BF3 launches of gi_ggnn_forward / backward (environment GI_X2, default 1):
@@ -2244,353 +2475,35 @@ extern "C" int gi_ggnn_backward_phase(const gi_ggnn_dims* dp, const float* const
     phase &= ~(GI_BWD_PREPACKED | GI_BWD_NO_X2);
     if (phase != GI_BWD_ALL && phase != GI_BWD_READOUT && phase != GI_BWD_PASSES) return GI_EINVAL;
     (void)hipGetLastError();   // drop stale errors of earlier, unrelated runtime calls
-    Model m;
-    int rc = build_model(dp, m);
-    if (rc) return rc;
-    if (!gp) return GI_EINVAL;
-    if (m.mnn)
-        return mnn_backward(m, params, gp, ws, slabs, y_out, ldout, d_out, lddout, grads, (hipStream_t)stream,
-                            (hipStream_t)side_stream, phase, prepacked, no_x2);
-    const int S = gp->S, E = gp->E, U = gp->U;
-    const int* gfix = gp->gfix;
-    const int* u_src = gp->u_src;
-    const int* in_perm = gp->in_perm;
-    const int* mu_off = gp->mu_off;
-    const int* mu_dst = gp->mu_dst;
-    const int* mu_slot = gp->mu_slot;
-    const int* out_perm = gp->out_perm;
-    const int* Ut = gp->Ut;
-    if (!params || !gfix || !ws || !slabs || !y_out || !d_out || !grads || S < 0 || E < 0 || U < 0 ||
-        U > E || !Ut)
-        return GI_EINVAL;
-    if (E > 0 && (!u_src || !in_perm || !mu_off || !mu_dst || !mu_slot || !out_perm || U == 0))
-        return GI_EINVAL;
-    if (m.nparams > MAXPARAMS) return GI_ELIMIT;
-    if (gp->wcache) return GI_EINVAL;     // (a forward that used the weights cache left no max |W| cells in ws)
-    const gi_ggnn_dims& d = m.d;
-    gi_compact_layout_t L;
-    rc = gi_compact_layout(d.B, d.N, d.Fe, &L);
-    if (rc) return rc;
-    Ws w;
-    if (gp->D0 < 0 || gp->D0 > U || (gp->D0 > 0 && (!gp->d_src || !gp->cmat || gp->ldc0 < gp->D0)))
-        return GI_EINVAL;
-    if (d.kind == GI_KIND_ATTGGNN && gp->D0 > 0 && (!gp->e2d || !gp->cls_off || !gp->cls_edges))
-        return GI_EINVAL;
-    if (int drc = dropout_graph_ok(d, S, E, U, gp->D0)) return drc;
-    make_ws(m, S, E, U, gp->D0, w);
-    SlabPlan sp;
-    plan_slabs(m, S, U, Ut, sp);
-    Grp bytype0{d.Fe, gfix + L.type_off0, w.D0};
-    bytype0.dim_slot = 2;                                  // (marks the pass-0 rows)
-    Run r{(hipStream_t)stream, params, 0};
-    r.drop = d.dropout != 0; r.seed = d.drop_seed; r.fshift = w.fshift;
-    r.skinny = ws + w.skinny; r.skinny_floats = w.skinny_floats;
-    r.x2 = x2_enabled() && !no_x2;
-    r.guard = gp->x2_guard; r.guard_host = nullptr;       // (the backward only counts: dZ rows never trip)
-    if (prepacked) {                                      // images written by THIS workspace's forward (side stream)?
-        if (hipEvent_t ev = prepack_lookup(ws, r.x2)) r.chk((int)hipStreamWaitEvent(r.st, ev, 0));
-        else prepacked = false;                           // no such forward on record: pack here
+    Call c;
+    c.slabs = slabs; c.grads = grads; c.y_out = y_out; c.ldout = ldout; c.d_out = d_out; c.lddout = lddout;
+    if (int rc = open_call(c, true, dp, params, gp, ws, stream, side_stream, no_x2)) return rc;
+    Run& r = c.r;
+    prepacked = prepacked && await_prepack(c);
+    if (phase == GI_BWD_PASSES) {        // the readout half ran (and was reduced) in an earlier call
+        for_readout_params(c, [&](int widx) { c.sp.e[widx].reduced = 1; });
+    } else {                             // GI_BWD_READOUT: the readout, down to the last pass's d h
+        bf3_prepare(c, true, prepacked ? 0 : BF3_DO_PACK, r.st);
+        tier2_selu_bwd(c);
+        graph_stacks_bwd(c);
+        gather_bwd(c);
+        zero_row_colsums(c);
+        node_stacks_bwd(c);
+        if (!c.m.gather()) graph_sum_bwd(c);
     }
-    const long long out_fshift = r.drop ? (long long)d.B * ldout : 0;   // logits -> their factors
-    const int R = w.R;
-    int maxUt = 0;
-    for (int t = 0; t < d.Fe; ++t) maxUt = std::max(maxUt, Ut[t]);
-    const Grp bytype{d.Fe, gfix + L.type_off, maxUt, Ut};
-    const int* seg_off = gfix + L.seg_off;
-    const int* src_off = gfix + L.src_off;
-    const int* cidx = gfix + L.cidx;
-    const int* mask = gfix + L.node_mask;
-    const int NA = m.NA, NC = m.NC;
-    const bool attn = d.kind == GI_KIND_ATTGGNN;
-
-    Deferred dq;
-    SideStream side_obj{(hipStream_t)side_stream, 0};
-    SideStream* const passes_side = side_stream ? &side_obj : nullptr;
-    r.side = passes_side;
-    r.sp = &sp; r.slabs = slabs; r.grads = grads;
-    r.wgrad_x2 = wgrad_x2_pool_possible(m, r.x2);
-    r.pool.base = r.wgrad_x2 ? ws + w.amax_pool : nullptr;
-    const Grp none{0, nullptr, 0};
-    const float* hxP = ws + w.hx[d.passes];
-    float* dh = ws + w.dh;
-    float* dh2 = ws + w.dh2;
-    float* dhb = ws + w.dhb;
-    float* dhc = ws + w.dhc;
-    float* dhd = ws + w.dhd;
-    auto readout_params = [&](auto&& fn) {
-        const Mlp* stacks[] = {&m.att, &m.emb, &m.add1, &m.conn1, &m.add2, &m.conn2, &m.term2};
-        for (const Mlp* q : stacks)
-            for (int l = 0; l < q->layers(); ++l) fn(q->w(l));
-    };
-    if (phase == GI_BWD_PASSES)          // the readout half ran (and was reduced) in an earlier call
-        readout_params([&](int widx) { sp.e[widx].reduced = 1; });
-    if (phase != GI_BWD_PASSES) {
-    bf3_prepare(r, m, ws, w, true, S + 1, prepacked ? 0 : BF3_DO_PACK, r.st);
-    // ---- tier 2 (gnn/modules.py:265-279) ---------------------------------------------------------
-    if (gi_fuse_flags() & GI_FUSE_TIER2_DSELU) {
-        r.chk(gi_selu_bwd_cols3_f(d_out, lddout, y_out, ldout, out_fshift, d.B, NA, ws + w.dzA, w.ldNA, NC,
-                                  ws + w.dzC, w.ldNC, 1, ws + w.dzT, 4, r.st));
-    } else {
-        r.chk(gi_selu_bwd_rows_f(d_out, lddout, nullptr, y_out, ldout, ws + w.dzA, w.ldNA, d.B, NA,
-                                 out_fshift, r.st));
-        r.chk(gi_selu_bwd_rows_f(d_out + NA, lddout, nullptr, y_out + NA, ldout, ws + w.dzC, w.ldNC, d.B,
-                                 NC, out_fshift, r.st));
-        r.chk(gi_selu_bwd_rows_f(d_out + NA + NC, lddout, nullptr, y_out + NA + NC, ldout, ws + w.dzT, 4,
-                                 d.B, 1, out_fshift, r.st));
-    }
-    {
-        MlpJob jobs[3] = {};
-        jobs[0] = {&m.add2, ws + w.cat_add, w.ldCA, d.B, w.add2_act, w.ldM2, nullptr, 0, w.add2_dz,
-                   ws + w.dzA, w.ldNA, ws + w.dcat_add, w.ldCA, NA + d.G, false};
-        jobs[1] = {&m.conn2, ws + w.cat_conn, w.ldCC, d.B, w.conn2_act, w.ldM2, nullptr, 0,
-                   w.conn2_dz, ws + w.dzC, w.ldNC, ws + w.dcat_conn, w.ldCC, NC + d.G, false};
-        jobs[2] = {&m.term2, ws + w.gemb, w.ldG, d.B, w.term2_act, w.ldM2, nullptr, 0, w.term2_dz,
-                   ws + w.dzT, 4, ws + w.dgemb, w.ldG, d.G, false};
-        mlp_jobs_backward(r, ws, sp, slabs, dq, jobs, 3);
-    }
-    // ---- gather + tier-1 glue: dZ of the last att/emb/add1/conn1 layers, in place ----------------
-    if (gi_glue_flags() & GI_GLUE_READOUT_BWD) {     // both in one launch
-        r.chk(gi_readout_glue_bwd_f(ws + w.en, ws + w.embo, w.ldG, cidx, mask, d.B, d.N, d.G, S, d.big_positive,
-                                    ws + w.dgemb, w.ldG, ws + w.dcat_add + NA, w.ldCA, ws + w.dcat_conn + NC, w.ldCC,
-                                    ws + w.zpart_g, ws + w.add1o, w.ldA, d.A, ws + w.dcat_add, w.ldCA, ws + w.zpart_a,
-                                    w.ldA, ws + w.conn1o, w.ldC, d.C, ws + w.dcat_conn, w.ldCC, ws + w.zpart_c, w.ldC,
-                                    r.fshift, r.st));
-    } else {
-        r.chk(gi_gather_readout_bwd_f(ws + w.en, ws + w.embo, w.ldG, cidx, mask, d.B, d.N, d.G, S,
-                                      d.big_positive, ws + w.dgemb, w.ldG, ws + w.dcat_add + NA, w.ldCA,
-                                      ws + w.dcat_conn + NC, w.ldCC, ws + w.zpart_g, r.fshift, r.st));
-        if (gi_fuse_flags() & GI_FUSE_SLOTS) {
-            r.chk(gi_compress_slots2_f(ws + w.add1o, w.ldA, d.A, ws + w.dcat_add, w.ldCA, ws + w.zpart_a, w.ldA,
-                                       ws + w.conn1o, w.ldC, d.C, ws + w.dcat_conn, w.ldCC, ws + w.zpart_c,
-                                       w.ldC, cidx, d.B, d.N, S, r.fshift, r.st));
-        } else {
-            r.chk(gi_compress_slots_f(ws + w.add1o, w.ldA, cidx, d.B, d.N, d.A, S, ws + w.dcat_add, w.ldCA,
-                                      ws + w.zpart_a, w.ldA, r.fshift, r.st));
-            r.chk(gi_compress_slots_f(ws + w.conn1o, w.ldC, cidx, d.B, d.N, d.C, S, ws + w.dcat_conn, w.ldCC,
-                                      ws + w.zpart_c, w.ldC, r.fshift, r.st));
+    if (phase != GI_BWD_READOUT) {       // GI_BWD_PASSES: the message passes, reversed
+        pack_chains_bwd(c, prepacked);
+        for (int p = c.m.d.passes - 1; p >= 0; --p) {
+            pass_cells_bwd(c, p);
+            gru_update_bwd(c, p);
+            if (c.m.mnn) msg_bwd_mnn(c, p);
+            else if (c.attn) msg_bwd_attggnn(c, p);
+            else msg_bwd_ggnn(c, p);
+            r.hold_kicks = false;
+            std::swap(c.dh, c.dh2);
         }
+        if (c.m.mnn) msg_wgrad_mnn(c);
     }
-    {   // zero-row gradients of the four stacks: per-graph partial sums -> row S, one launch
-        float* en_z = ws + w.en + (long long)S * w.ldG;
-        float* emb_z = ws + w.embo + (long long)S * w.ldG;
-        float* add_z = ws + w.add1o + (long long)S * w.ldA;
-        float* conn_z = ws + w.conn1o + (long long)S * w.ldC;
-        const gi_colsum_desc cs[4] = {
-            {ws + w.zpart_g, w.ldZG, d.B, d.G, en_z, en_z},
-            {ws + w.zpart_g + d.G, w.ldZG, d.B, d.G, emb_z, emb_z},
-            {ws + w.zpart_a, w.ldA, d.B, d.A, add_z, add_z},
-            {ws + w.zpart_c, w.ldC, d.B, d.C, conn_z, conn_z}};
-        r.chk(gi_colsum_multi(cs, 4, r.st));
-    }
-    // ---- node-level readout MLPs -> dh -------------------------------------------------------------
-    {   // every sibling writes its own d h; the GRU-gate backward of the last pass sums the four
-        MlpJob jobs[4] = {};
-        jobs[0] = {&m.add1, hxP, w.ldhx, R, w.add1_act, w.ldM1, nullptr, 0, w.add1_dz, ws + w.add1o,
-                   w.ldA, dh, w.ldH, d.H, false};
-        jobs[1] = {&m.conn1, hxP, w.ldhx, R, w.conn1_act, w.ldM1, nullptr, 0, w.conn1_dz,
-                   ws + w.conn1o, w.ldC, dhb, w.ldH, d.H, false};
-        jobs[2] = {&m.emb, hxP, w.ldhx, R, w.emb_act, w.ldEmb, nullptr, 0, w.emb_dz, ws + w.embo,
-                   w.ldG, dhc, w.ldH, d.H, false};
-        jobs[3] = {&m.att, hxP, w.ldhx, R, w.att_act, w.ldAtt, nullptr, 0, w.att_dz, ws + w.en, w.ldG,
-                   dhd, w.ldH, d.H, false};
-        // No weight-gradient batches beside the node-level dgrad launches: those fill the device by
-        // themselves (2 760 workgroups each at the headline batch), two streams only contend there;
-        // everything queued goes out behind them, under the message passes' short launches (round 2: step
-        // 2.362 -> 2.344 ms, GEMM-family per-launch figure 0.349 -> 0.374 of peak; re-measured in round 3 with the
-        // dgrad launches on the bf16 pipe: 2.20 ms held against 2.25-2.28 released).
-        // Round 5, with the backward bound by the weight-gradient queue: holding still wins at the headline batch
-        // (7.3 k node rows: 1.935 against 1.944 ms) and loses from ~10 k rows on (B = 2000: 3.35 -> 3.24 ms, ZINC shape
-        // 4.05 -> 4.00, ChEMBL shape 3.24 -> 3.21, B = 4000 a tie; profiles/r05/ab/ab_hold_kicks.txt).
-        r.hold_kicks = R <= HOLD_KICKS_MAX_ROWS;
-        mlp_jobs_backward(r, ws, sp, slabs, dq, jobs, 4);
-        r.hold_kicks = false;
-        if (r.side) kick_deferred(r, dq, r.side, false);
-    }
-    }   // phase != GI_BWD_PASSES
-    if (phase == GI_BWD_READOUT) {
-        // finish the readout parameters now: their weight-gradient GEMMs and slab reductions are
-        // queued (side stream if there is one) so that the caller can start exchanging the gradients
-        // of these parameters while the message passes are still being differentiated
-        if (r.side) {
-            kick_deferred(r, dq, r.side, true);          // also reduces every finished parameter
-            gi_reduce_desc descs[MAXPARAMS];
-            int nd = 0;
-            readout_params([&](int widx) {
-                if (sp.e[widx].reduced) return;
-                sp.e[widx].reduced = 1;
-                descs[nd++] = reduce_desc(sp.e[widx], slabs, grads, widx);
-            });
-            if (nd && r.ok()) r.chk(gi_reduce_slabs(descs, nd, r.side->st));
-        } else {
-            flush_deferred(r, dq);
-            gi_reduce_desc descs[MAXPARAMS];
-            int nd = 0;
-            readout_params([&](int widx) {
-                sp.e[widx].reduced = 1;
-                descs[nd++] = reduce_desc(sp.e[widx], slabs, grads, widx);
-            });
-            if (r.ok()) r.chk(gi_reduce_slabs(descs, nd, r.st));
-        }
-        return r.rc;
-    }
-    r.eatt0 = m.eatt;
-    if (d.passes > 0 && E > 0)          // packed weight images of the dZ chains, once per backward
-        for (int k = 0; k < (attn ? 2 : 1); ++k)
-            if (w.img_b_n[k] > 0) {
-                if (chain_x2_enabled(r.x2)) r.chain_amax[k] = ws + w.chain_amax[k];
-                r.img_b[k] = ws + w.img_b[k];
-                r.img_b_stride[k] = w.img_b_stride[k];
-                if (!prepacked) chain_pack(r, k ? m.eatt : m.msg, d.Fe, true, r.img_b[k]);
-            }
-    // ---- message passes, reversed -------------------------------------------------------------------
-    // d h scatter (segmented sum of the message stacks' input gradients over the source CSR): its own
-    // launch(es) behind the pass's dZ chain, or — GI_FUSE_DH_SCATTER, vector gate kernel (H % 4 == 0) —
-    // folded into the gate backward of the next iteration, which is the only reader of that sum
-    const bool fuse_scatter = (gi_fuse_flags() & GI_FUSE_DH_SCATTER) && (d.H & 3) == 0 && d.H >= 4;
-    const float* scat0 = nullptr;
-    const float* scat1 = nullptr;
-    const bool msgx = E > 0 && msg_wgrad_x2_possible(m, r.x2) && chain_x2_enabled(r.x2);
-    for (int p = d.passes - 1; p >= 0; --p) {
-        for (int k = 0; k < (attn ? 2 : 1); ++k)   // the cells this pass's forward chains published into (gi_ggnn_forward_ex)
-            r.msg_cells[k] = (msgx && w.img_b_n[k] > 0 && !(p == 0 && w.D0 > 0)) ? ws + w.msg_amax[k] + p * MSG_CELLS_PER_PASS : nullptr;
-        const float* hx = ws + w.hx[p];
-        float* gi = ws + w.gi[p];
-        float* gh = ws + w.gh[p];
-        float* agg = ws + w.agg[p];
-        const bool last = (p == d.passes - 1);
-        if (scat0) {    // the later pass's d h scatter rides in this launch (GI_FUSE_DH_SCATTER)
-            r.chk(gi_gru_gates_bwd_ex(gi, gh, w.ld3H, hx, w.ldhx, dh, last ? dhb : nullptr,
-                                      last ? dhc : nullptr, last ? dhd : nullptr, dh2, w.ldH, seg_off, R,
-                                      d.H, scat0, scat1, w.ldH, out_perm, src_off, r.st));
-            scat0 = scat1 = nullptr;
-        } else {
-            r.chk(gi_gru_gates_bwd(gi, gh, w.ld3H, hx, w.ldhx, dh, last ? dhb : nullptr,
-                                   last ? dhc : nullptr, last ? dhd : nullptr, dh2, w.ldH, seg_off, R,
-                                   d.H, r.st));
-        }
-        float* dagg = ws + w.dagg[p];
-        // Pass 0 of the class-row path: the main queue has ~100 us of short launches left, the weight-gradient queue
-        // everything deferred so far: hand that over NOW and keep pass 0's own GRU weight gradients for the main queue's
-        // last launch (with the pass-0 message stack's), so that both queues end together.
-        if (p == 0 && w.D0 > 0 && r.side) {
-            kick_deferred(r, dq, r.side, true); r.hold_kicks = r.p0_on_main = true;
-        }
-        {
-            const int wih = m.gru_wih, whh = m.gru_whh;
-            defer_wgrad(r, dq, sp, slabs, &wih, none, gi, w.ld3H, agg, w.ldM, nullptr, R);
-            defer_wgrad(r, dq, sp, slabs, &whh, none, gh, w.ld3H, hx, w.ldhx, nullptr, R);
-            // d agg = d gi W_ih;  d h_prev += d gh W_hh   (one launch)
-            Batch bd;
-            add_dgrad(bd, r, m.gru_wih, 3 * d.H, d.M, d.M, gi, w.ld3H, R, dagg, w.ldM, nullptr, 0,
-                      false);
-            if (p > 0)
-                add_dgrad(bd, r, m.gru_whh, 3 * d.H, d.H, d.H, gh, w.ld3H, R, dh2, w.ldH, nullptr,
-                          0, true);
-            flush_batch(r, bd, false);
-        }
-        if (E > 0 && attn) {
-            // backward of the softmax-weighted aggregation: per-edge contributions, then per message
-            // row their sum times the SELU derivative of both stacks' last layer (in place)
-            const bool p0 = p == 0 && w.D0 > 0;      // pass 0 ran on the class rows
-            r.chk(gi_seg_softmax_bwd(ws + w.een[p], ws + w.m[p], w.ldM, p0 ? gp->e2d : in_perm, seg_off,
-                                     R, d.M, dagg, w.ldM, ws + w.tmp_en, ws + w.tmp_emb, w.ldM, r.st));
-            EdgeChain ch[2] = {
-                {m.msg, w.eact[p], w.edz[p], w.ldEh, ws + w.m[p], w.ldM, p > 0 ? ws + w.dxe : nullptr},
-                {m.eatt, w.aact[p], w.adz[p], w.ldEa, ws + w.een[p], w.ldM,
-                 p > 0 ? ws + w.dxa : nullptr}};
-            if (p0) {   // per class row: sum over its (hundreds of) edge slots, both stacks in one launch
-                r.chk(gi_class_sum_dselu(ws + w.tmp_emb, ws + w.tmp_en, w.ldM, gp->cls_edges,
-                                         gp->cls_off, w.D0, d.M, ws + w.m[p], ws + w.een[p], w.ldM,
-                                         r.st));
-                edge_chains_backward(r, ws, sp, slabs, dq, ch, 2, bytype0, hx, w.ldhx, gp->d_src, w.D0,
-                                     w.ldH, d.H);
-            } else {
-                // per message row: the sum of its edges' contributions times the SELU derivative of the
-                // stack's last layer (own launches in front of the dZ chains, edge_chains_backward)
-                const SegIn seg_m{ws + w.tmp_emb, w.ldM, mu_slot, mu_off};
-                const SegIn seg_e{ws + w.tmp_en, w.ldM, mu_slot, mu_off};
-                ch[0].seg = &seg_m; ch[1].seg = &seg_e;
-                edge_chains_backward(r, ws, sp, slabs, dq, ch, 2, bytype, hx, w.ldhx, u_src, U, w.ldH,
-                                     d.H);
-            }
-            if (p > 0 && fuse_scatter) {
-                scat0 = ws + w.dxe; scat1 = ws + w.dxa;
-            } else if (p > 0) {
-                r.chk(gi_seg_sum(ws + w.dxe, w.ldH, out_perm, src_off, R, d.H, dh2, w.ldH, 1, r.st));
-                r.chk(gi_seg_sum(ws + w.dxa, w.ldH, out_perm, src_off, R, d.H, dh2, w.ldH, 1, r.st));
-            }
-        } else if (p == 0 && w.D0 > 0) {
-            // pass 0: d m0 = selu'(m0) * (cmat^T . d agg): split-K over the R rows, slabs summed with
-            // the SELU backward folded in; then the MLP backward on the D0 class rows (no d h needed)
-            gi_gemm_params q;
-            gemm_defaults(q);
-            q.A = gp->cmat; q.lda = gp->ldc0; q.a_major = 1;
-            q.B = dagg; q.ldb = w.ldM; q.b_major = 1;
-            q.C = ws + w.p0slab; q.ldc = w.ldM; q.M = w.D0; q.N = d.M; q.K = R;
-            q.flags = GI_GEMM_SPLITK; q.nsplit = w.p0split;
-            q.c_split_stride = gi_r4l((long long)std::max(w.D0, 1) * w.ldM);
-            q.tm = 1; q.tn = 1;
-            r.chk(gi_gemm(&q, r.st));
-            r.chk(gi_slab_sum_dselu(ws + w.p0slab, w.p0split, q.c_split_stride, w.D0, d.M, w.ldM,
-                                    ws + w.m[0], w.ldM, r.st));
-            msg_backward(r, ws, sp, slabs, dq, m.msg, bytype0, hx, w.ldhx, gp->d_src, w.D0, w.eact[0],
-                         w.edz[0], w.ldEh, ws + w.m[0], w.ldM, nullptr, w.ldH, d.H);
-        } else if (E > 0) {
-            // d m_u = selu'(m_u) * sum over the edges reading row u of d agg[dst(e)]
-            // (backward of the segmented sum + last SELU, over the message CSR)
-            const SegIn seg{dagg, w.ldM, mu_dst, mu_off};
-            msg_backward(r, ws, sp, slabs, dq, m.msg, bytype, hx, w.ldhx, u_src, U, w.eact[p],
-                         w.edz[p], w.ldEh, ws + w.m[p], w.ldM, p > 0 ? ws + w.dxe : nullptr, w.ldH,
-                         d.H, &seg);
-            if (p > 0 && fuse_scatter)
-                scat0 = ws + w.dxe;
-            else if (p > 0)   // scatter d h_src back to nodes: segmented sum over the source CSR
-                r.chk(gi_seg_sum(ws + w.dxe, w.ldH, out_perm, src_off, R, d.H, dh2, w.ldH, 1, r.st));
-        } else {
-            // no edges: the message MLP weights still need zeroed slabs
-            for (int k = 0; k < (attn ? 2 : 1); ++k)
-                for (int t = 0; t < d.Fe; ++t) {
-                    const Mlp& q = k ? m.eatt[t] : m.msg[t];
-                    for (int l = 0; l < q.layers(); ++l) {
-                        SlabEntry& e = sp.e[q.w(l)];
-                        r.chk((int)hipMemsetAsync(
-                            slabs + e.off + (long long)e.done * e.nsplit * e.stride, 0,
-                            sizeof(float) * e.nsplit * e.stride, r.st));
-                        e.done++;
-                    }
-                }
-        }
-        r.hold_kicks = false;
-        std::swap(dh, dh2);
-    }
-    // ---- all weight-gradient GEMMs, 8 problems per launch, then slabs -> parameter gradients -------
-    if (r.side && r.p0_on_main) {
-        flush_deferred(r, dq);            // a dozen workgroups, right behind their chain: no hand-over to wait for
-        join_side(r, r.side);
-    } else if (r.side) {
-        kick_deferred(r, dq, r.side, true);
-        join_side(r, r.side);
-    } else {
-        flush_deferred(r, dq);
-    }
-    gi_reduce_desc descs[MAXPARAMS];            // whatever has not been reduced on the side stream yet
-    int nd = 0;
-    auto add_desc = [&](int widx, int) {
-        SlabEntry& e = sp.e[widx];
-        if (e.reduced) return;
-        e.reduced = 1;
-        descs[nd++] = reduce_desc(e, slabs, grads, widx);
-    };
-    auto add_mlp_desc = [&](const Mlp& q) {
-        for (int l = 0; l < q.layers(); ++l) add_desc(q.w(l), q.b(l));
-    };
-    for (int t = 0; t < d.Fe; ++t) add_mlp_desc(m.msg[t]);
-    if (attn)
-        for (int t = 0; t < d.Fe; ++t) add_mlp_desc(m.eatt[t]);
-    add_desc(m.gru_wih, m.gru_bih);
-    add_desc(m.gru_whh, m.gru_bhh);
-    add_mlp_desc(m.att); add_mlp_desc(m.emb); add_mlp_desc(m.add1); add_mlp_desc(m.conn1);
-    add_mlp_desc(m.add2); add_mlp_desc(m.conn2); add_mlp_desc(m.term2);
-    if (r.ok()) r.chk(gi_reduce_slabs(descs, nd, r.st));
+    finish(c, phase);
     return r.rc;
 }

@@ -519,7 +519,10 @@ int gi_gru_gates_bwd(float* gi, float* gh, int ldg, const float* hx_prev, int ld
  *                `nodes[edge_batch_nghb_idc]`, gnn/summation_mpnn.py:131-133) folded into the
  *                gi_gru_gates_bwd_ex launch of the next (earlier) message pass
  *   TIER2_DSELU  the SELU backward of the three logit column ranges in one launch (gi_selu_bwd_cols3_f)
- *   SLOTS        fAddNet1 / fConnNet1 glue in one launch each way (gi_expand_slots2, gi_compress_slots2_f) */
+ *   SLOTS        fAddNet1 / fConnNet1 glue in one launch each way (gi_expand_slots2, gi_compress_slots2_f)
+ * Every model kind follows the mask in both directions: the forward and the backward of GGNN, AttentionGGNN and MNN
+ * share one driver.  (The MNN backward used to run the TIER2_DSELU and SLOTS launches whatever the mask said; with a
+ * bit cleared it now runs the unfused launches, like the other kinds.  Nothing changes under the default mask.) */
 #define GI_FUSE_GATES_V4    1
 #define GI_FUSE_DH_SCATTER  2
 #define GI_FUSE_TIER2_DSELU 4

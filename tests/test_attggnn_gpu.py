@@ -17,6 +17,7 @@ from oracle import ggnn_oracle as O
 from tests import pins
 from tests import ref_dataflow as D
 from tests.golden.spec import TINY_ATT, tiny_inputs
+from tests.two_call import check_two_call_backward
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -220,6 +221,20 @@ def test_full_dims_logits_and_branch_pinned_gradients(shape, B, over):
     assert len(names) == len(grads) == len(g64)
     for k, g in zip(names, grads):
         assert rel(g, g64[k]) < TOL, k
+
+
+@pytest.mark.parametrize("side_stream", [True, False])
+@pytest.mark.parametrize("passes", [0, 1, 3])
+def test_two_call_backward_is_bitwise_the_single_call_backward(passes, side_stream, monkeypatch):
+    """gi_ggnn_backward_phase(READOUT) + (PASSES) must give exactly the gradients of the single call (the body of the
+    GGNN test of this name in test_model_gpu.py), with the weight gradients on their side stream and on one stream.
+    (1 pass: pass 0 is also the last pass; 0 passes: the second phase has nothing to do.)"""
+    monkeypatch.setattr(mpnn, "WGRAD_SIDE_STREAM", side_stream)
+    sh = synthetic.SHAPES["gdb13"]
+    cfg = O.shaped_config(sh["n_atom_types"], sh["n_formal_charge"], sh["max_n_nodes"], message_passes=passes)
+    model = make_model(cfg, O.init_params(cfg, seed=2, model=MODEL))
+    nodes, edges, tgt = to_dev(*synthetic.make_batch(16, **sh, seed=31))
+    check_two_call_backward(model, L.KIND_ATTGGNN, nodes, edges, tgt)
 
 
 def test_batch_without_any_edge_and_module_surface():

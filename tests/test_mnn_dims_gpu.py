@@ -1,7 +1,7 @@
 """-m gpu: the MNN model across dimensions, depths and pass counts, and its kernels at their edges.
 
 tests/test_mnn_gpu.py runs MNN at two shapes (the tiny golden; GDB-13 defaults, H = M = 100, Fe = 3, 3 passes, depth 4).
-Its driver (csrc/gi_model.hip mnn_forward / mnn_backward) and its kernels (csrc/gi_mnn.hip, templated on Fe = 1 .. 8)
+Its message steps in the shared driver (csrc/gi_model.hip msg_fwd_mnn / msg_bwd_mnn / msg_wgrad_mnn) and its kernels (csrc/gi_mnn.hip, templated on Fe = 1 .. 8)
 branch on more than that:
 
   fe1 / fe4 / fe8   every bond-type count the templates are built for, with EVERY type present (synthetic.make_batch
@@ -258,7 +258,7 @@ UNUSED_AT_0_PASSES = {"message_weights", "gru.weight_ih", "gru.weight_hh", "gru.
 
 def test_zero_passes_leave_the_message_parameters_without_gradient():
     """tests/test_depths_gpu.py's protocol for MNN: at 0 passes message_weights and gru.* keep .grad None on both
-    autograd paths (mnn_backward's memset of dW must not surface), a held gradient is untouched, torch.optim.Adam
+    autograd paths (msg_wgrad_mnn's memset of dW must not surface), a held gradient is untouched, torch.optim.Adam
     leaves them where they are, every other gradient is within 1e-4 of the oracle's."""
     cfg, (n8, e8, a8) = case("passes0")
     P = MO.init_params(cfg, seed=32)

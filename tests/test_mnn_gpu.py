@@ -17,6 +17,7 @@ from graphinvent_amd.gnn import mpnn
 from oracle import ggnn_oracle as O
 from tests import mnn_oracle as MO
 from tests.golden.spec import digest
+from tests.two_call import check_two_call_backward
 from tests.ref_dataflow import compact
 
 pytestmark = pytest.mark.gpu
@@ -286,6 +287,20 @@ def test_sync_free_forward_equals_plain_forward(B):
     assert model.last_bounded_error() == 0
     assert float((free - plain).abs().max()) <= 1e-5 * float(plain.abs().max())
     assert torch.equal(free, free2)
+
+
+@pytest.mark.parametrize("side_stream", [True, False])
+@pytest.mark.parametrize("passes", [0, 1, 3])
+def test_two_call_backward_is_bitwise_the_single_call_backward(passes, side_stream, monkeypatch):
+    """gi_ggnn_backward_phase(READOUT) + (PASSES) must give exactly the gradients of the single call (the body of the
+    GGNN test of this name in test_model_gpu.py), with the weight gradients on their side stream and on one stream.
+    (1 pass: pass 0 is also the last pass; 0 passes: the second phase has nothing to do.)"""
+    monkeypatch.setattr(mpnn, "WGRAD_SIDE_STREAM", side_stream)
+    sh = synthetic.SHAPES["gdb13"]
+    cfg = MO.mnn_config(sh["n_atom_types"], sh["n_formal_charge"], sh["max_n_nodes"], message_passes=passes)
+    model = _model(cfg, MO.init_params(cfg, seed=2))
+    nodes, edges, tgt = (torch.from_numpy(x).float().to(DEV) for x in synthetic.make_batch(16, **sh, seed=31))
+    check_two_call_backward(model, L.KIND_MNN, nodes, edges, tgt)
 
 
 def test_fused_adam_tracks_oracle_adam():

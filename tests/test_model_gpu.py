@@ -22,6 +22,7 @@ from oracle import ggnn_oracle as O
 from tests import pins
 from tests import ref_dataflow as D
 from tests.golden.spec import TINY, digest, tiny_inputs
+from tests.two_call import check_two_call_backward
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -684,31 +685,25 @@ def test_compaction_prefetched_one_batch_ahead_is_bitwise_identical():
 
 
 @pytest.mark.parametrize("passes", [0, 1, 3])
-def test_two_call_backward_is_bitwise_the_single_call_backward(passes):
+def test_two_call_backward_is_bitwise_the_single_call_backward(passes, monkeypatch):
     """gi_ggnn_backward_phase(READOUT) + (PASSES) — what the overlapped data-parallel exchange uses —
     must give exactly the gradients of the single call, and the hook must see the readout tail.  (1 pass: the
-    second phase differentiates pass 0 alone, which is also the last pass; 0 passes: it has nothing to do.)"""
+    second phase differentiates pass 0 alone, which is also the last pass; 0 passes: it has nothing to do.)
+    With the weight gradients on their side stream and with everything on one stream.  (AttentionGGNN and MNN:
+    the tests of the same name in test_attggnn_gpu.py / test_mnn_gpu.py.)"""
     cfg = O.make_config(message_passes=passes)
     P = O.init_params(cfg, seed=2)
     model = make_model(cfg, P)
     params = list(model.parameters())
     n8, e8, a8 = synthetic.make_batch(200, **synthetic.SHAPES["gdb13"], seed=31)
     nodes, edges, tgt = to_dev(n8, e8, a8)
-    results = []
-    seen = {}
-    for hook in (None, lambda gflat, split, ev: seen.update(split=split, n=gflat.numel(), ev=ev)):
-        out, tape = mpnn.ggnn_forward_raw(model.constants, nodes, edges, params)
-        o = out.detach().clone().requires_grad_(True)
-        O.kl_loss(o, tgt).backward()
-        grads, gflat = mpnn.ggnn_backward_raw(tape, out, o.grad, params, early_hook=hook)
-        torch.cuda.synchronize()
-        results.append([g.clone() for g in grads])            # (the bucket's 16-byte padding is not data)
-    assert all(torch.equal(a, b) for a, b in zip(*results))
-    names = [k for k, _ in model.named_parameters()]
-    first = names.index("gather.att_nn.seq.0.weight")
-    assert seen["split"] == sum((p.numel() + 3) & ~3 for p in params[:first])
-    assert 0.8 < 1 - seen["split"] / seen["n"] < 0.9           # the tail is most of the bucket
-    seen["ev"].synchronize()
+    for side_stream in (True, False):
+        monkeypatch.setattr(mpnn, "WGRAD_SIDE_STREAM", side_stream)
+        seen = check_two_call_backward(model, L.KIND_GGNN, nodes, edges, tgt)
+        names = [k for k, _ in model.named_parameters()]
+        first = names.index("gather.att_nn.seq.0.weight")
+        assert seen["split"] == sum((p.numel() + 3) & ~3 for p in params[:first])
+        assert 0.8 < 1 - seen["split"] / seen["n"] < 0.9           # the tail is most of the bucket
 
 
 def test_direct_gradient_writeback_has_autograd_accumulate_semantics():
