@@ -41,7 +41,7 @@ import torch
 
 from . import lib as L
 from . import routes as R
-from .sampler import _add_dims, _SampleRL, sample_actions_raw
+from .sampler import ActionConstraint, _add_dims, _MaskActions, _SampleRL, mask_actions_raw, sample_actions_raw
 
 #: the generator tensors the step reads and writes, in gi_grow_desc's order, with their dtypes
 _STATE_TENSORS = (("nodes", torch.float32), ("edges", torch.float32), ("n_nodes", torch.int8),
@@ -164,6 +164,55 @@ def _check_gen_seed(gen_seed: Optional[torch.Tensor], Cg: int, device) -> None:
     if gen_seed is not None and (gen_seed.dtype != torch.int32 or tuple(gen_seed.shape) != (Cg,) or
                                  not gen_seed.is_contiguous() or gen_seed.device != device):
         raise ValueError(f"generated_seed must be a contiguous int32 [{Cg}] tensor on {device}")
+
+
+class _Masker:
+    """The mask step of a constrained loop: ``constraint`` checked against the generator tensors ``t`` once, the running
+    figures (``stats``) allocated before any round — and so before a capture — and kept on the device.  ``raw`` /
+    ``rl`` enqueue one gi_action_mask launch on the graphs' current state and one small launch that adds the round to
+    the figures unless the growth ``state`` shows a frozen round (graph 0, the dummy, is left out of them)."""
+
+    def __init__(self, constraint, t: dict, state: torch.Tensor):
+        if not isinstance(constraint, ActionConstraint):
+            raise TypeError(f"constraint must be a sampler.ActionConstraint, got {type(constraint).__name__}")
+        nodes, edges = t["nodes"], t["edges"]
+        c = constraint
+        if nodes.dim() != 3 or edges.dim() != 4 or tuple(nodes.shape[1:]) != (c.N, c.Fn) or \
+                tuple(edges.shape[1:]) != (c.N, c.N, c.Fe):
+            raise ValueError(f"the constraint was built for N, Fn, Fe = {(c.N, c.Fn, c.Fe)}, the generator's tensors "
+                             f"are nodes {tuple(nodes.shape)} / edges {tuple(edges.shape)}")
+        if nodes.device != c.device:
+            raise ValueError(f"the constraint's rules are on {c.device}, the generator's tensors on {nodes.device}")
+        self.c, self.t, self.state, self.device = c, t, state, nodes.device
+        self.counts = torch.zeros(2, dtype=torch.int32, device=self.device)
+        self.mass = torch.zeros(1, dtype=torch.float32, device=self.device)
+
+    @property
+    def stats(self) -> dict:
+        return {"rounds": self.counts[0], "graph_rounds_masked": self.counts[1], "mass_removed": self.mass[0]}
+
+    def _account(self, removed: torch.Tensor) -> None:
+        B = removed.shape[0]
+        with torch.cuda.device(self.device):
+            L.check(L.load().gi_action_mask_stats(B - 1, removed.data_ptr() + 4, self.state.data_ptr(),
+                                                  self.counts.data_ptr(), self.mass.data_ptr(),
+                                                  torch.cuda.current_stream(self.device).cuda_stream),
+                    "gi_action_mask_stats")
+
+    def raw(self, logits: torch.Tensor, account: bool = True) -> torch.Tensor:
+        t = self.t
+        masked, _, _, _, _, removed = mask_actions_raw(logits, t["n_nodes"], t["nodes"], t["edges"], self.c,
+                                                       bits=False, removed=True)
+        if account:
+            self._account(removed)
+        return masked
+
+    def rl(self, agent_logits: torch.Tensor, prior_logits: torch.Tensor):
+        t = self.t
+        masked_a, masked_p, _, _, _, removed = _MaskActions.apply(agent_logits, prior_logits, t["n_nodes"], t["nodes"],
+                                                                 t["edges"], self.c, False, False, True)
+        self._account(removed)
+        return masked_a, masked_p
 
 
 class _Grower:
@@ -330,7 +379,7 @@ def _host_sync_allowed():
 
 def build_graphs(gen, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], *, uniforms: Optional[torch.Tensor] = None,
                  generator: Optional[torch.Generator] = None, poll_every: int = 8, capture: bool = False,
-                 seeds: Optional[SeedBank] = None) -> int:
+                 seeds: Optional[SeedBank] = None, constraint: Optional[ActionConstraint] = None) -> int:
     """Drop-in for ``GraphGenerator.build_graphs`` (GraphGenerator.py:99-161): ``gen`` is the reference's generator
     (duck-typed: ``model``, ``batch_size`` and the tensors its ``__init__`` allocates), mutated in place; returns
     ``n_generated_so_far`` and sets ``gen.generation_rounds`` (rounds applied).
@@ -346,7 +395,19 @@ def build_graphs(gen, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], *, un
     leaves them; one launch fills slot ``g >= 1`` with seed ``(g - 1) mod S``, every graph written out restarts from
     seed ``(B - 1 + row) mod S`` (``row`` its index in ``generated_*``), and ``gen.generated_seed`` (int32 [C], on the
     device, -1 past the rows written) names the seed each generated row was grown from.  The generated likelihood
-    rows hold the actions sampled after the (re)start only: the likelihood of the completion given the seed."""
+    rows hold the actions sampled after the (re)start only: the likelihood of the completion given the seed.
+
+    ``constraint`` (a ``sampler.ActionConstraint``): constrained generation, in every mode and together with ``seeds``.
+    One more launch per round (``gi_action_mask``, part of the captured round and of its warm-up) sets every
+    inadmissible action to -inf in a copy of the logits, and the draw is taken from the renormalised distribution: no
+    attach to an empty slot, no second bond on a pair, no add to a full graph, no atom over the largest valence of
+    the rules' table (the library's own, not RDKit's).  With valid seeds every generated row is then valid under
+    ``analyze.validity`` and properly terminated.  **The likelihoods written are those of the constrained policy**, not
+    the unconstrained model's (``likelihood.molecule_log_likelihood`` still scores the latter).  A molecule can take
+    more actions than ``2 N``: size the likelihood columns for it, or the documented ``IndexError`` is raised.
+    ``gen.constraint_stats`` (device tensors, nothing read back in the loop): ``rounds`` applied,
+    ``graph_rounds_masked`` (graph-rounds in which probability mass was removed) and ``mass_removed`` (its sum),
+    graph 0 left out.  ``None`` (the default) adds no launch."""
     if poll_every < 1:
         raise ValueError("poll_every must be >= 1")
     model, B = gen.model, int(gen.batch_size)
@@ -367,10 +428,15 @@ def build_graphs(gen, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], *, un
     mirror = _HostMirror(B)
     try:
         grower = _Grower(t, dim_f_add, dim_f_conn, state, mirror.dev.value, seeds, gen_seed)
+        masker = _Masker(constraint, t, state) if constraint is not None else None
     except Exception:
         mirror.close()
         raise
     nodes, edges, n_nodes, A = t["nodes"], t["edges"], t["n_nodes"], grower.A
+    if masker is None:
+        logits_of = lambda warm=False: model(nodes, edges)                              # noqa: E731
+    else:
+        logits_of = lambda warm=False: masker.raw(model(nodes, edges), not warm)        # noqa: E731
     stream = torch.cuda.current_stream(dev)
     sync_free = capture or bool(getattr(model, "sync_free", False))
     prev_sync_free = getattr(model, "sync_free", None)
@@ -385,13 +451,13 @@ def build_graphs(gen, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], *, un
                 side = torch.cuda.Stream(device=dev)
                 side.wait_stream(stream)
                 with torch.cuda.stream(side):            # warm-up: the model's persistent device state; no round applied
-                    sample_actions_raw(model(nodes, edges), n_nodes, edges, A, uniform=u_buf)
+                    sample_actions_raw(logits_of(True), n_nodes, edges, A, uniform=u_buf)
                 stream.wait_stream(side)
                 with _host_sync_allowed():                   # (set-up: the capture synchronises on entry)
                     torch.cuda.synchronize(dev)
                     graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(graph):
-                        grower.step(*sample_actions_raw(model(nodes, edges), n_nodes, edges, A, uniform=u_buf))
+                        grower.step(*sample_actions_raw(logits_of(), n_nodes, edges, A, uniform=u_buf))
             pending = collections.deque()
             r = 0
             while uniforms is None or r < uniforms.shape[0]:
@@ -403,7 +469,7 @@ def build_graphs(gen, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], *, un
                     graph.replay()
                 else:
                     u = uniforms[r] if uniforms is not None else torch.rand(B, device=dev, generator=generator)
-                    grower.step(*sample_actions_raw(model(nodes, edges), n_nodes, edges, A, uniform=u))
+                    grower.step(*sample_actions_raw(logits_of(), n_nodes, edges, A, uniform=u))
                 r += 1
                 ev = torch.cuda.Event()
                 ev.record(stream)
@@ -432,6 +498,8 @@ def build_graphs(gen, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], *, un
     gen.generation_rounds = rounds
     if seeds is not None:
         gen.generated_seed = gen_seed
+    if masker is not None:
+        gen.constraint_stats = masker.stats
     _raise_for_outcome("build_graphs", n, rounds, target, err, t["likelihoods"], uniforms)
     return n
 
@@ -611,7 +679,8 @@ class _TrajGather(torch.autograd.Function):
 
 def build_graphs_rl(gen, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], *,
                     uniforms: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
-                    poll_every: int = 1, seeds: Optional[SeedBank] = None) -> int:
+                    poll_every: int = 1, seeds: Optional[SeedBank] = None,
+                    constraint: Optional[ActionConstraint] = None) -> int:
     """Drop-in for ``GraphGeneratorRL.build_graphs`` (GraphGeneratorRL.py:109-172): ``gen`` is the reference's RL
     generator (duck-typed: ``agent_model``, ``prior_model``, ``batch_size`` and the tensors of its
     ``allocate_graph_tensors`` / ``initialize_graph_batch``), mutated in place; returns ``n_generated_so_far`` and
@@ -629,7 +698,13 @@ def build_graphs_rl(gen, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], *,
 
     ``seeds`` (a SeedBank): seeded generation as in ``build_graphs`` — the first fill, restarts from seed
     ``(B - 1 + row) mod S``, ``gen.generated_seed``; both likelihood streams and their gradients are those of the
-    completions given the seeds."""
+    completions given the seeds.
+
+    ``constraint`` (a ``sampler.ActionConstraint``): constrained generation as in ``build_graphs`` — ONE mask launch per
+    round writes the masked copies of the agent's and the prior's logits, the draw is taken from the agent's
+    renormalised distribution, and BOTH likelihood streams are those of the constrained policies.  The gradients reach
+    the models through the mask: the sampler's backward already writes exact zeros at masked columns, so the mask
+    hands its upstream gradient through.  ``gen.constraint_stats`` as in ``build_graphs`` (of the agent's logits)."""
     if poll_every < 1:
         raise ValueError("poll_every must be >= 1")
     agent, prior, B = gen.agent_model, gen.prior_model, int(gen.batch_size)
@@ -649,6 +724,7 @@ def build_graphs_rl(gen, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], *,
     mirror = _HostMirror(B)
     try:
         grower = _GrowerRL(t, prior_t, traj, dim_f_add, dim_f_conn, state, mirror.dev.value, seeds, gen_seed)
+        masker = _Masker(constraint, t, state) if constraint is not None else None
         nodes, edges, n_nodes, A = t["nodes"], t["edges"], t["n_nodes"], grower.A
         stream = torch.cuda.current_stream(dev)
         likes_a, likes_p = [], []
@@ -660,8 +736,10 @@ def build_graphs_rl(gen, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], *,
             r = 0
             while uniforms is None or r < uniforms.shape[0]:
                 u = uniforms[r] if uniforms is not None else torch.rand(B, device=dev, generator=generator)
-                action, like_a, like_p, flags = _SampleRL.apply(agent(nodes, edges), prior(nodes, edges), n_nodes,
-                                                                edges, A, u, None)
+                out_a, out_p = agent(nodes, edges), prior(nodes, edges)
+                if masker is not None:
+                    out_a, out_p = masker.rl(out_a, out_p)
+                action, like_a, like_p, flags = _SampleRL.apply(out_a, out_p, n_nodes, edges, A, u, None)
                 grower.step(action, like_a, like_p, flags)
                 likes_a.append(like_a)
                 likes_p.append(like_p)
@@ -688,6 +766,8 @@ def build_graphs_rl(gen, dim_f_add: Sequence[int], dim_f_conn: Sequence[int], *,
     gen.generation_rounds = rounds
     if seeds is not None:
         gen.generated_seed = gen_seed
+    if masker is not None:
+        gen.constraint_stats = masker.stats
     _raise_for_outcome("build_graphs_rl", n, rounds, target, err, t["likelihoods"], uniforms)
     del likes_a[rounds:], likes_p[rounds:]               # frozen rounds leave the autograd graph with these
     gen_a, gen_p = _TrajGather.apply(torch.stack(likes_a), torch.stack(likes_p), traj, n, L_cols)

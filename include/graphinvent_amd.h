@@ -1472,6 +1472,63 @@ int gi_smiles_read_arom(int G, int N, int Fn, int Fe, const unsigned char* text,
                         const unsigned char* symbols, int none_chirality, int drop_stereo, int aromatic,
                         signed char* nodes, signed char* edges, int* n_nodes, int* status, int* atom_pos, void* stream);
 
+/* Constrained generation: the action mask between the forward and the draw of a generation round, in ONE launch with
+ * no read-back (recordable into a hipGraph).  For each of B graphs (nodes [B, N, Fn] / edges [B, N, N, Fe], GI_DTYPE;
+ * n_nodes [B], an entry of n_nodes_bytes = 1, 4 or 8 bytes, required) a COPY of its logits row is written in which
+ * every inadmissible action is -inf and every other column keeps the input's bits:
+ *   masked[b, j] = admissible(b, j) ? logits[b, j] : -inf,   j < W = N A + N Fe + 1,  A = prod(group) * Fe
+ * (row pitches ldl / ldm >= W), and the same for an optional second matrix logits2 -> masked2 (the prior of RL
+ * fine-tuning; its own pitches; both NULL: skipped).  gi_sample_actions / gi_sample_actions_rl, unchanged, then draw
+ * from the renormalised distribution: their likelihoods are those of the CONSTRAINED policy.  A masked copy must not
+ * be the matrix it is made from (GI_EINVAL): a model's backward reads its output.
+ * THE VALENCE TABLE IS THE CALLER'S (allowed, order2, h_values as at gi_mol_valence), NOT RDKit'S SANITISATION.
+ *
+ * Columns, as gi_sample_actions decodes them: add(i, rem) at i A + rem, rem ravelled over (group[0], ..., group[n_groups
+ * - 1], Fe) — the node-feature groups in node-row order (group[0] = n_types, group[1] = n_charges, group[2] = n_imp_h if
+ * n_imp_h > 0, then whatever follows, e.g. chirality; sum = Fn), the bond type f last, as gi_grow_graphs unravels it;
+ * connect(i, f) at N A + i Fe + f; terminate at W - 1.  n = n_nodes[b] clamped to [0, N].
+ *
+ * The state is WELL-FORMED when the labelled read (gi_mol_valence's) sets none of GI_MOL_ONEHOT, _BOND_PAST_N, _VALUE,
+ * _MULTI_BOND, _ASYMMETRIC, _NODE_PAST_N and no GI_VAL_SELF_LOOP.  For such a state and an atom i < n, in integers:
+ *   budget2(i) = 2 vmax(type_i, charge_i) - o2_i - 2 s_i
+ * o2_i = sum_t order2[t] * #{j : edges[i, j, t]}, vmax the largest allowed valence (none allowed: -1), s_i the stored
+ * hydrogen count h_values[.] (n_imp_h == 0: 0).
+ * Structural rules, always applied:
+ *   add(i, ...)    n < N, and i == 0 if n == 0, else i < n
+ *   connect(i, f)  n >= 2, i < n - 1, no set entry in edges[b, i, n - 1, :]
+ *   terminate      n >= 1, or allow_empty
+ * Valence rules, for a well-formed state and valence = 1:
+ *   add(i, type, charge, [h], ..., f), n >= 1   order2[f] <= budget2(i)  and  order2[f] + 2 h <= 2 vmax(type, charge)
+ *   add, n == 0                                 2 h <= 2 vmax(type, charge), any f (the growth step sets no bond)
+ *   connect(i, f)                               order2[f] <= budget2(i)  and  order2[f] <= budget2(n - 1)
+ * A state that is not well-formed (the reference's dummy graph 0 always) gets the structural rules only.
+ * With valid seeds this keeps flags & 1 of the sampler clear and every atom at or below its largest valence.
+ *
+ * Outputs: n_admissible [B]; status [B] = the malformed / self-loop bits above, plus GI_MASK_STRUCTURAL when any is set;
+ * bits (optional) [B, ceil(W / 32)], column j = bit j & 31 of word j >> 5, zero past W; removed (optional) [B] fp32 =
+ * the softmax mass of logits[b] (the first matrix) on the inadmissible columns (the only output not decided in
+ * integers; 0 for a row without positive mass).  16-byte accesses where base and pitch allow, element-wise otherwise.
+ * Limits: N <= GI_MAX_NODES, Fe <= GI_MAX_GROUPS, n_groups <= GI_GROW_MAX_GROUPS (GI_EINVAL); Fn <= GI_ANALYZE_MAX_FN,
+ * n_types * n_charges * max(n_imp_h, 1) <= GI_MASK_MAX_COMBOS, W < 2^31 - 1024 (GI_ELIMIT); no limit on W of its own
+ * beyond that (the sampler keeps its row limit).  `group` is a host array.  B = 0 returns 0 and touches nothing.  No
+ * global atomics, no scratch, no memset; every loop is bounded by N, Fn, Fe, W.
+ * tests/action_mask_model.py is the Python specification. */
+#define GI_MASK_STRUCTURAL (1 << 20)    /* the state is not well-formed: structural rules only */
+#define GI_MASK_MAX_COMBOS 4096
+int gi_action_mask(int B, int N, int Fn, int Fe, const void* nodes, const void* edges, int dtype,
+                   const void* n_nodes, int n_nodes_bytes, int n_groups, const int* group, int n_types,
+                   int n_charges, int n_imp_h, const unsigned short* allowed, const signed char* order2,
+                   const signed char* h_values, int valence, int allow_empty, const float* logits, int ldl,
+                   float* masked, int ldm, const float* logits2, int ldl2, float* masked2, int ldm2,
+                   int* n_admissible, int* status, unsigned* bits, float* removed, void* stream);
+
+/* Running figures of a constrained generation loop, one small launch, nothing read back: unless grow_state (the growth
+ * step's state words, optional) shows a frozen round (state[0] >= state[2] or state[3] != 0),
+ *   acc_counts[0] += 1,  acc_counts[1] += #{b : removed[b] > 0},  acc_mass[0] += sum_b removed[b]
+ * in a fixed order of additions.  Calls on one accumulator must be ordered (one stream).  B = 0 returns 0. */
+int gi_action_mask_stats(int B, const float* removed, const int* grow_state, int* acc_counts, float* acc_mass,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
