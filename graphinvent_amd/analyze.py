@@ -1592,3 +1592,323 @@ def read_smi(path, rules: ValenceRules, max_n_nodes: int, *, batch: int = 8192, 
         return SmiMolecules(one.nodes, one.edges, one.n_nodes, one.status, names)
     return SmiMolecules(*(torch.cat([getattr(p, name) for p in parts]) for name in ("nodes", "edges", "n_nodes", "status")),
                         names)
+
+
+# ---- substructure search ---------------------------------------------------------------------------------------------
+#: status bits of ``substructure`` beyond the malformed bits of ``VALIDITY_STATUS_MESSAGES``
+SUBSTRUCTURE_STATUS_MESSAGES = {
+    **{bit: VALIDITY_STATUS_MESSAGES[bit] for bit in (L.MOL_ONEHOT, L.MOL_BOND_PAST_N, L.MOL_VALUE, L.MOL_MULTI_BOND,
+                                                      L.MOL_ASYMMETRIC, L.MOL_NODE_PAST_N)},
+    L.VAL_EMPTY: "the molecule has no atoms: it matches nothing",
+    L.VAL_SELF_LOOP: "an atom is bonded to itself: the molecule matches nothing",
+    L.SUB_STEP_LIMIT: "an anchor was given up after max_steps steps (counted in n_limited; it counts as no match)",
+    L.SUB_PATTERN_INDEX: "pattern_index is outside [0, P): no match",
+}
+_SUB_HDR, _SUB_REC, _SUB_ROW = 8, 4, 8                       # words of the table's header, a record's and a row's head
+
+
+def _sub_array(what: str, name: str, x, ndim: int) -> np.ndarray:
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    x = np.asarray(x)
+    if x.ndim != ndim or x.dtype == object:
+        raise ValueError(f"{what}: {name} must be a {ndim}-dimensional array, got shape {x.shape}")
+    return x
+
+
+class SubstructureSet:
+    """P patterns for ``substructure``, validated, planned and packed ONCE (``table``, int32, on the host and on
+    ``device``; the layout is in include/graphinvent_amd.h at ``gi_mol_substructure``).
+
+    **A PATTERN IS NOT SMARTS**: a connected labelled graph of 1 to 32 atoms.  ``type_mask`` [P, Np_max, A] and
+    ``charge_mask`` [P, Np_max, C]: per atom a 0 / 1 row over the atom types / formal charges of the rules the molecules
+    are read with (all zero: any; several ones: any of these).  ``bond_mask`` [P, Np_max, Np_max, Fe], symmetric: per
+    atom pair a 0 / 1 row over the bond types (all zero: no pattern bond; several ones: any of these).  ``degree`` /
+    ``min_h`` [P, Np_max] (optional): the exact number of bonded partners / at least this many hydrogens by the rules'
+    fill (``validity``'s ``atom_h``), -1: any.  Patterns of different sizes share the arrays: Np of a pattern is one past
+    its last atom that has a bond or a predicate, at least 1; what lies behind is padding.  ``names``: P strings.
+
+    An empty set, an atom on its own diagonal, an asymmetric ``bond_mask`` and a pattern that is not connected raise
+    ``ValueError``.  ``order`` / ``parent`` / ``back`` hold every pattern's plan: its atoms in breadth-first order from
+    atom 0 (neighbours ascending), every position's parent position and its other bonds to earlier positions.
+    ``device=None`` keeps the host table only (``substructure`` refuses such a set)."""
+
+    def __init__(self, type_mask, charge_mask, bond_mask, *, degree=None, min_h=None, names=None, device="cuda"):
+        what = "SubstructureSet"
+        tm, cm = _sub_array(what, "type_mask", type_mask, 3) != 0, _sub_array(what, "charge_mask", charge_mask, 3) != 0
+        bm = _sub_array(what, "bond_mask", bond_mask, 4) != 0
+        P, Npm, A = tm.shape
+        if P < 1 or Npm < 1 or A < 1:
+            raise ValueError(f"{what}: at least one pattern of at least one atom is needed, got type_mask {tm.shape}")
+        if cm.shape[:2] != (P, Npm) or cm.shape[2] < 1 or bm.shape[:3] != (P, Npm, Npm) or bm.shape[3] < 1:
+            raise ValueError(f"{what}: charge_mask {cm.shape} / bond_mask {bm.shape} do not match type_mask {tm.shape} "
+                             "([P, Np, A], [P, Np, C], [P, Np, Np, Fe])")
+        C_, Fe = cm.shape[2], bm.shape[3]
+        if Npm > L.SUB_MAX_ATOMS or P > L.SUB_MAX_PATTERNS or Fe > L.GI_MAX_GROUPS or A + C_ > L.ANALYZE_MAX_FN:
+            raise ValueError(f"{what}: at most {L.SUB_MAX_ATOMS} atoms per pattern, {L.SUB_MAX_PATTERNS} patterns, "
+                             f"{L.GI_MAX_GROUPS} bond types and {L.ANALYZE_MAX_FN} node entries; got Np {Npm}, P {P}, "
+                             f"Fe {Fe}, A + C {A + C_}")
+        extra = []
+        for name, x, hi in (("degree", degree, L.GI_MAX_NODES - 1), ("min_h", min_h, 15)):
+            if x is None:
+                x = np.full((P, Npm), -1, np.int64)
+            else:
+                x = _sub_array(what, name, x, 2)
+                if x.shape != (P, Npm) or not np.issubdtype(x.dtype, np.integer) or x.min() < -1 or x.max() > hi:
+                    raise ValueError(f"{what}: {name} must be integers in [-1, {hi}] of shape ({P}, {Npm})")
+            extra.append(x.astype(np.int64))
+        deg, mh = extra
+        if names is not None and (len(names) != P or len(set(names)) != P):
+            raise ValueError(f"{what}: names must be {P} different strings")
+        self.names = None if names is None else [str(s) for s in names]
+        if (bm != bm.transpose(0, 2, 1, 3)).any():
+            raise ValueError(f"{what}: bond_mask must be symmetric in its two atom axes")
+        if bm[:, np.arange(Npm), np.arange(Npm)].any():
+            raise ValueError(f"{what}: bond_mask has an atom bonded to itself")
+        bonded = bm.any(axis=3)
+        marked = bonded.any(axis=2) | tm.any(axis=2) | cm.any(axis=2) | (deg >= 0) | (mh >= 0)
+        self.n_atoms = [max(1, int(np.flatnonzero(marked[p])[-1]) + 1 if marked[p].any() else 1) for p in range(P)]
+        self.order, self.parent, self.back = [], [], []
+        for p in range(P):
+            order, parent, back = self._plan(bonded[p], self.n_atoms[p], p if self.names is None else self.names[p])
+            self.order.append(order), self.parent.append(parent), self.back.append(back)
+        self.dims, self.Np_max = (A, C_, Fe), Npm
+        TW, CW = (A + 31) // 32, (C_ + 31) // 32
+        Bmax = -(-max(sum(len(b) for b in back) for back in self.back) // 4) * 4
+        R = _SUB_ROW + -(-(TW + CW) // 4) * 4
+        S = _SUB_REC + Npm * R + Bmax
+        table = np.zeros(_SUB_HDR + P * S, np.int64)
+        table[:_SUB_HDR] = [P, Npm, A, C_, Fe, TW, CW, Bmax]
+        bits = lambda row, words, size: [sum(1 << int(b - 32 * w) for b in (np.flatnonzero(row) if row.any()
+                                                                            else range(size)) if 32 * w <= b < 32 * w + 32)
+                                         for w in range(words)]
+        word = lambda row: sum(1 << int(t) for t in np.flatnonzero(row))
+        for p in range(P):
+            rec = _SUB_HDR + p * S
+            table[rec] = self.n_atoms[p]
+            n_back = 0
+            for k, atom in enumerate(self.order[p]):
+                row = rec + _SUB_REC + k * R
+                par = self.parent[p][k]
+                table[row:row + 8] = [par, word(bm[p, atom, self.order[p][par]]) if k else 0, n_back,
+                                      len(self.back[p][k]), atom, deg[p, atom], mh[p, atom], 0]
+                table[row + 8:row + 8 + TW] = bits(tm[p, atom], TW, A)
+                table[row + 8 + TW:row + 8 + TW + CW] = bits(cm[p, atom], CW, C_)
+                for q in self.back[p][k]:
+                    table[rec + _SUB_REC + Npm * R + n_back] = q | (word(bm[p, atom, self.order[p][q]]) << 8)
+                    n_back += 1
+        self.table = (table & 0xffffffff).astype(np.uint32).view(np.int32)
+        self.device = None if device is None else torch.device(device)
+        self.table_dev = None
+        if self.device is not None:
+            if self.device.type != "cuda":
+                raise RuntimeError(f"{what} needs a CUDA (ROCm) device, got {self.device}: the MI355X HIP path has no CPU "
+                                   "fallback (device=None keeps the table on the host, for inspection only)")
+            self.table_dev = torch.from_numpy(self.table).to(self.device)
+
+    @staticmethod
+    def _plan(bonded, Np: int, name):
+        order, parent_atom, head = [0], {0: 0}, 0
+        while head < len(order):
+            a = order[head]
+            head += 1
+            for b in np.flatnonzero(bonded[a, :Np]):
+                if int(b) not in parent_atom:
+                    parent_atom[int(b)] = a
+                    order.append(int(b))
+        if len(order) != Np:
+            raise ValueError(f"SubstructureSet: pattern {name!r} is not connected ({len(order)} of its {Np} atoms are "
+                             "reached from atom 0)")
+        pos = {a: k for k, a in enumerate(order)}
+        parent = [pos[parent_atom[a]] for a in order]
+        back = [sorted(pos[int(b)] for b in np.flatnonzero(bonded[a, :Np]) if pos[int(b)] < k and pos[int(b)] != parent[k])
+                if k else [] for k, a in enumerate(order)]
+        return order, parent, back
+
+    def __len__(self):
+        return len(self.n_atoms)
+
+    def index(self, which) -> int:
+        """A pattern's column from its index or its name."""
+        if isinstance(which, str):
+            if self.names is None or which not in self.names:
+                raise ValueError(f"SubstructureSet: no pattern named {which!r}")
+            return self.names.index(which)
+        if not isinstance(which, (int, np.integer)) or isinstance(which, bool) or not 0 <= which < len(self):
+            raise ValueError(f"SubstructureSet: pattern {which!r} is not an index in [0, {len(self)}) or a name")
+        return int(which)
+
+    @classmethod
+    def from_molecules(cls, nodes, edges, n_nodes, rules, relax_bonds: bool = False, any_charge: bool = False, *,
+                       names=None, device="rules"):
+        """One pattern per molecule (int8 or fp32 ``nodes`` [P, N, Fn] / ``edges`` [P, N, N, Fe] as they come from
+        anywhere in the library, on the device or the host; ``n_nodes`` [P] or ``None``: the leading rows with a set
+        entry): every atom asks for its type and its charge (``any_charge``: for its type only), every bond for its
+        type (``relax_bonds``: for any bond, the answer to Kekule phases; both options take one bool or one per
+        pattern).  Read back once, here.  A molecule of more
+        than 32 atoms, without atoms, or with a node row that is not one-hot in its type and charge segments raises
+        ``ValueError``."""
+        what = "SubstructureSet.from_molecules"
+        A, Cn, _ = _rules_groups(what, rules)
+        nodes, edges = _sub_array(what, "nodes", nodes, 3), _sub_array(what, "edges", edges, 4)
+        P, N, Fn = nodes.shape
+        if edges.shape[:3] != (P, N, N) or A + Cn > Fn or P < 1:
+            raise ValueError(f"{what}: nodes {nodes.shape} / edges {edges.shape} must be [P, N, Fn] / [P, N, N, Fe] with "
+                             f"P >= 1 and hold the rules' segments {rules.groups}")
+        present = (nodes != 0).any(axis=2)
+        if n_nodes is None:
+            n = np.where(present.all(axis=1), N, np.argmin(present, axis=1))
+        else:
+            n = _sub_array(what, "n_nodes", n_nodes, 1).astype(np.int64)
+            if n.shape != (P,):
+                raise ValueError(f"{what}: n_nodes has shape {n.shape}, expected ({P},)")
+        if n.min() < 1 or n.max() > min(N, L.SUB_MAX_ATOMS):
+            raise ValueError(f"{what}: every molecule needs 1 to {min(N, L.SUB_MAX_ATOMS)} atoms, got "
+                             f"{int(n.min())} to {int(n.max())}")
+        Npm, Fe = int(n.max()), edges.shape[3]
+        inside = np.arange(Npm)[None, :] < n[:, None]
+        tm, cm = (nodes[:, :Npm, :A] != 0) & inside[..., None], (nodes[:, :Npm, A:A + Cn] != 0) & inside[..., None]
+        if ((tm.sum(axis=2) != 1) & inside).any() or ((cm.sum(axis=2) != 1) & inside).any():
+            raise ValueError(f"{what}: a node row below n_nodes is not one-hot in its atom type and formal charge segments")
+        bm = (edges[:, :Npm, :Npm] != 0) & inside[:, :, None, None] & inside[:, None, :, None]
+        try:
+            relax, free = (np.broadcast_to(np.asarray(x, bool), (P,)) for x in (relax_bonds, any_charge))
+        except ValueError:
+            raise ValueError(f"{what}: relax_bonds and any_charge must be a bool or {P} bools, one per pattern") from None
+        bm = np.where(relax[:, None, None, None], np.repeat(bm.any(axis=3, keepdims=True), Fe, axis=3), bm)
+        # an atom is marked by its type row, so that Np is n even for atoms that ask for nothing else
+        return cls(tm, cm & ~free[:, None, None], bm, names=names, device=rules.device if device == "rules" else device)
+
+    @classmethod
+    def from_smiles(cls, strings, rules, max_atoms: int = 32, relax_bonds: bool = False, any_charge: bool = False, *,
+                    aromatic: str = "error", names=None):
+        """One pattern per SMILES string, through ``read_smiles`` (there is no other parser, and NO SMARTS: a string is a
+        molecule; ``aromatic="kekulize"`` reads aromatic input into ONE Kekule phase — use ``relax_bonds`` with it).
+        Hydrogens, stated or implied, ask for nothing.  A string with a reader error bit raises ``ValueError``."""
+        what = "SubstructureSet.from_smiles"
+        strings = list(strings)
+        if not 1 <= max_atoms <= L.SUB_MAX_ATOMS:
+            raise ValueError(f"{what}: max_atoms must be in [1, {L.SUB_MAX_ATOMS}], got {max_atoms!r}")
+        nodes, edges, n, status, _ = read_smiles(strings, rules, max_atoms, aromatic=aromatic).host()
+        for s, bits in zip(strings, status):
+            if bits & L.SMR_READ_ERROR:
+                raise ValueError(f"{what}: {s!r} cannot be read: {describe_read_status(int(bits))}")
+        return cls.from_molecules(nodes, edges, n, rules, relax_bonds, any_charge,
+                                  names=strings if names is None else names)
+
+
+class SubstructureMatches(_ResultBuffer):
+    """What ``substructure`` wrote, on the device, all int32: ``status`` [G], ``match`` / ``n_anchors`` / ``n_limited``
+    [G, P], ``anchors`` [G, P, 4] (atom j: bit ``j & 31`` of word ``j >> 5``), ``first`` [G, P, Np_max]; ``host()`` ->
+    ``{name: numpy array}``.  ``patterns`` is the set that was searched for (``None`` axis names with ``pattern_index``)."""
+
+    def __init__(self, buf: torch.Tensor, G: int, P: int, Npm: int, patterns=None):
+        super().__init__(buf, G, P, Npm)
+        self.P, self.patterns = P, patterns
+
+    @staticmethod
+    @functools.lru_cache(maxsize=64)
+    def layout(G: int, P: int, Npm: int) -> dict:
+        return _pack(("status", "int32", (G,)), ("match", "int32", (G, P)), ("n_anchors", "int32", (G, P)),
+                     ("n_limited", "int32", (G, P)), ("anchors", "int32", (G, P, 4)), ("first", "int32", (G, P, Npm)))
+
+    @staticmethod
+    def _host_result(a):
+        return a
+
+
+def substructure(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Optional[torch.Tensor], rules: ValenceRules,
+                 patterns: SubstructureSet, *, pattern_index: Optional[torch.Tensor] = None,
+                 max_steps: int = 4096) -> SubstructureMatches:
+    """Which molecule contains which pattern, for all G molecules and P patterns in one launch
+    (``gi_mol_substructure``), with no RDKit and no read-back; inputs as ``validity``.
+
+    **THIS IS NOT SMARTS AND NOT RDKit's MATCHER.**  A pattern (``SubstructureSet``) has per atom a set of types, a set
+    of charges, an exact degree and a least hydrogen count, and per bond a set of bond types: **no ring or recursive
+    predicates, and no aromaticity is perceived** — a Kekule pattern of a fused ring system matches only the molecule's
+    stored Kekule phase; ``relax_bonds=True`` is the answer for scaffolds.  A match is a monomorphism, as in
+    ``HasSubstructMatch``: the molecule may have more bonds than the pattern.
+
+    The search runs per (molecule, pattern, anchor), the anchor being the image of pattern atom 0, depth first along
+    the pattern's plan with candidates in ascending atom index (include/graphinvent_amd.h has the rule,
+    tests/substructure_model.py is the specification, matched integer for integer).  An anchor that has taken
+    ``max_steps`` steps (1 to 2**20) and needs another is given up: it counts as no match and in ``n_limited``, and the
+    molecule gets ``SUB_STEP_LIMIT``.  The 863 DRD2 fixture molecules against 18 usual groups and scaffolds never pass
+    112 steps.
+
+    Result (``SubstructureMatches``, views of one device buffer, ``.host()`` is one copy): ``match`` [G, P] 0 / 1;
+    ``n_anchors`` [G, P] the atoms that are the image of pattern atom 0 in some match (the functional-group count when
+    atom 0 is the group's centre); ``anchors`` [G, P, 4] the same as a 128-bit mask; ``first`` [G, P, Np_max] the images
+    of the pattern's atoms, in the pattern's own atom order, found from the lowest matching anchor (-1 where none and
+    past Np); ``n_limited`` [G, P]; ``status`` [G] (``SUBSTRUCTURE_STATUS_MESSAGES``): a malformed, empty or self-loop
+    molecule matches nothing.  With ``pattern_index`` (int32 [G], on the device) molecule g is searched for pattern
+    ``pattern_index[g]`` only and the P axis has length 1 (is the seed still in its product); an index outside [0, P)
+    gives no match and ``SUB_PATTERN_INDEX``.  G = 0 is answered without a launch."""
+    what = "substructure"
+    _rules_groups(what, rules)
+    if not isinstance(patterns, SubstructureSet):
+        raise TypeError(f"{what}: patterns must be a SubstructureSet, got {type(patterns).__name__}")
+    if (not isinstance(max_steps, (int, np.integer)) or isinstance(max_steps, bool)
+            or not 1 <= max_steps <= L.SUB_MAX_STEPS):
+        raise ValueError(f"{what}: max_steps must be an integer in [1, {L.SUB_MAX_STEPS}], got {max_steps!r}")
+    G, N, Fn, Fe, dtype, n_nodes, nn_bytes, _ = _check_inputs(what, nodes, edges, n_nodes, None, False)
+    dev = nodes.device
+    A, Cn, H, order2 = _check_rules(what, rules, Fn, Fe, dev)
+    if patterns.dims != (A, Cn, Fe):
+        raise ValueError(f"{what}: the patterns were built for (types, charges, bond types) = {patterns.dims}, the "
+                         f"molecules and rules have {(A, Cn, Fe)}")
+    if patterns.table_dev is None:
+        raise RuntimeError(f"{what}: the patterns were built with device=None and hold no device table (no CPU fallback)")
+    if patterns.table_dev.device != dev:
+        raise ValueError(f"{what}: the molecules are on {dev}, the patterns on {patterns.table_dev.device}")
+    if pattern_index is not None:
+        if not isinstance(pattern_index, torch.Tensor) or not pattern_index.is_cuda or pattern_index.device != dev:
+            raise RuntimeError(f"{what}: pattern_index must be a CUDA tensor on {dev} (no CPU fallback)")
+        if (tuple(pattern_index.shape) != (G,) or pattern_index.dtype != torch.int32
+                or not pattern_index.is_contiguous()):
+            raise ValueError(f"{what}: pattern_index must be a contiguous int32 tensor of shape ({G},), got "
+                             f"{pattern_index.dtype} {tuple(pattern_index.shape)}")
+    P = 1 if pattern_index is not None else len(patterns)
+    res = SubstructureMatches.empty(dev, G, P, patterns.Np_max, patterns=None if pattern_index is not None else patterns)
+    if G > 0:
+        out = res._ptrs()
+        with torch.cuda.device(dev):
+            L.check(L.load().gi_mol_substructure(
+                G, N, Fn, Fe, nodes.data_ptr(), edges.data_ptr(), dtype,
+                None if n_nodes is None else n_nodes.data_ptr(), nn_bytes, A, Cn, H, rules.allowed_mask.data_ptr(),
+                order2.data_ptr(), patterns.table.ctypes.data, patterns.table_dev.data_ptr(), patterns.table.size,
+                None if pattern_index is None else pattern_index.data_ptr(), int(max_steps), out["match"],
+                out["n_anchors"], out["anchors"], out["first"], out["n_limited"], out["status"],
+                torch.cuda.current_stream(dev).cuda_stream), "gi_mol_substructure")
+    return res
+
+
+def _column_runs(cols):
+    """Sorted distinct columns as (start, stop) runs: a slice each, no index tensor to copy to the device."""
+    runs = []
+    for c in sorted(set(cols)):
+        if runs and runs[-1][1] == c:
+            runs[-1][1] = c + 1
+        else:
+            runs.append([c, c + 1])
+    return runs
+
+
+def substructure_score(result: SubstructureMatches, *, require=(), forbid=()) -> torch.Tensor:
+    """A contribution for ``compute_score``: fp32 [G], 1 where every ``require`` pattern matches and no ``forbid``
+    pattern does, else 0 (pattern indices, or names of a named set).  Plain torch on ``result.match``'s device, no
+    read-back.  A molecule that matches nothing (malformed, empty) passes a forbid-only list: mask it with ``validity``,
+    as ``compute_score`` does."""
+    what = "substructure_score"
+    if not isinstance(result, SubstructureMatches):
+        raise TypeError(f"{what}: result must be substructure's result, got {type(result).__name__}")
+    if result.patterns is None:
+        raise ValueError(f"{what}: a result made with pattern_index has one column; use result.match[:, 0]")
+    req, forb = ([result.patterns.index(w) for w in which] for which in (require, forbid))
+    m = result.match
+    ok = torch.ones(result.G, dtype=torch.bool, device=m.device)
+    for a, b in _column_runs(req):
+        ok = ok & (m[:, a:b] != 0).all(dim=1)
+    for a, b in _column_runs(forb):
+        ok = ok & (m[:, a:b] == 0).all(dim=1)
+    return ok.to(torch.float32)

@@ -173,6 +173,8 @@ SMR_ERROR = (SMR_MULTI_BOND | SMR_EMPTY | SMR_SELF_LOOP | SMR_AROMATIC | SMR_TOO
 SMR_KEKULE, SMR_KEKULIZED = 1 << 26, 1 << 27            # GI_SMR_* of gi_smiles_read_arom with aromatic = 1 only
 SMR_READ_ERROR = SMR_ERROR | SMR_KEKULE                 # GI_SMR_ERROR: SMR_ERROR and the one error bit kekulising adds
 MASK_STRUCTURAL, MASK_MAX_COMBOS = 1 << 20, 4096        # GI_MASK_* of gi_action_mask
+SUB_MAX_ATOMS, SUB_MAX_PATTERNS, SUB_MAX_STEPS = 32, 65536, 1 << 20      # GI_SUB_* of gi_mol_substructure
+SUB_STEP_LIMIT, SUB_PATTERN_INDEX = 1 << 21, 1 << 22
 
 
 class RouteDims(C.Structure):
@@ -324,6 +326,8 @@ SIGNATURES = {
     "gi_action_mask": (ci, [ci, ci, ci, ci, vp, vp, ci, vp, ci, ci, C.POINTER(ci), ci, ci, ci, vp, vp, vp, ci, ci,
                             vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp]),
     "gi_action_mask_stats": (ci, [ci, vp, vp, vp, vp, vp]),
+    "gi_mol_substructure": (ci, [ci, ci, ci, ci, vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp, cll, vp, ci,
+                                 vp, vp, vp, vp, vp, vp, vp]),
 }
 FUSE_GATES_V4, FUSE_DH_SCATTER, FUSE_TIER2_DSELU, FUSE_SLOTS = 1, 2, 4, 8  # GI_FUSE_*
 GLUE_READOUT_FWD, GLUE_READOUT_BWD, GLUE_LOSS_MEAN, GLUE_GRU_AGG = 1, 2, 4, 8  # GI_GLUE_*

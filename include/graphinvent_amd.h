@@ -1529,6 +1529,62 @@ int gi_action_mask(int B, int N, int Fn, int Fe, const void* nodes, const void* 
 int gi_action_mask_stats(int B, const float* removed, const int* grow_state, int* acc_counts, float* acc_mass,
                          void* stream);
 
+/* ---- substructure search (gi_substructure.hip) ------------------------------------------------------------------
+ * Which of G molecules (inputs as gi_mol_valence: fp32 or int8, any alignment, n_nodes given or NULL: derived) contain
+ * which of P PATTERNS, in one launch with no read-back: the host's one HasSubstructMatch per molecule and pattern.
+ * THIS IS NOT SMARTS AND NOT RDKit'S MATCHER: no ring or recursive predicates, NO AROMATICITY PERCEPTION (a Kekule pattern
+ * of a ring system matches the molecule's stored Kekule phase only; ask for "any bond type" on the ring bonds instead).
+ *
+ * A pattern is a connected labelled graph of 1 <= Np <= GI_SUB_MAX_ATOMS atoms.  Per atom: a set of atom types and a set
+ * of formal charges (bit masks over the type / charge segment), `degree` (the exact number of bonded partners, -1: any)
+ * and `min_h` (at least this many hydrogens by the fill of gi_mol_valence, which is 0 for an atom over its valence; -1:
+ * any).  Per bond: a non-empty set of bond types (an Fe-bit mask).  A MATCH is an injective map of the pattern's atoms
+ * to atoms < n under which every atom predicate holds and every pattern bond lands on a bond whose type is in its mask
+ * (a monomorphism: the molecule may have further bonds).  A molecule with a bit of the labelled read (GI_MOL_ONEHOT,
+ * _BOND_PAST_N, _VALUE, _MULTI_BOND, _ASYMMETRIC, _NODE_PAST_N, empty = 128, self-loop = 256) matches nothing.
+ *
+ * The PLAN of a pattern is part of the contract (the step counts depend on it): its atoms in breadth-first order from atom
+ * 0, neighbours in ascending index; position k > 0 has a parent position (where it was discovered from) and its other
+ * bonds to earlier positions, the back bonds, in ascending position.
+ * The SEARCH runs per (molecule, pattern, anchor); the anchor is the atom tried as the image of position 0 (placing it
+ * is not a step).  Depth first: at position k the candidates are
+ *   compat[k] & (OR over the parent bond's mask of the adjacency rows of the parent's image) & ~used
+ * in ascending atom index (after a backtrack: those above the image just abandoned).  Taking a candidate is one STEP;
+ * its back bonds are then checked and a candidate that fails them is abandoned.  The search stops at the first full
+ * assignment.  An anchor about to take a step after max_steps steps is given up: no match, counted in n_limited.
+ * 1 <= max_steps <= GI_SUB_MAX_STEPS.
+ *
+ * The patterns travel as ONE int32 table, once on the host (patterns_host, checked on every call: header against the
+ * dims, Np in range, the plan a permutation, parents earlier than their children, back bonds earlier and not the parent,
+ * masks non-empty and inside their segment) and once on the device (patterns, 16-byte aligned, read by the kernel):
+ *   [0, 8)        P, Np_max, n_types, n_charges, Fe, TW = ceil(n_types / 32), CW = ceil(n_charges / 32), B (a multiple of 4)
+ *   record p      at 8 + p S, S = 4 + Np_max R + B, R = 8 + 4 ceil((TW + CW) / 4):  Np, 0, 0, 0, the rows, the back bonds
+ *   row k         at 4 + k R of the record: parent position, parent bond mask, first back bond, number of back bonds,
+ *                 pattern atom, degree, min_h, 0, TW words of type bits, CW words of charge bits ("any" = all bits set)
+ *   back bond     at 4 + Np_max R + i of the record: position | mask << 8
+ * Outputs, with Pout = P, or 1 with pattern_index [G] int32 (molecule g against pattern pattern_index[g] only; an index
+ * outside [0, P) matches nothing and sets GI_SUB_PATTERN_INDEX):
+ *   match [G, Pout] 0 / 1;  n_anchors [G, Pout] the atoms that are the image of pattern atom 0 in some match (the
+ *   functional-group count when atom 0 is the group's centre);  anchors [G, Pout, 4] the same as a 128-bit mask;
+ *   first [G, Pout, Np_max] the images of the pattern's atoms, in the pattern's own atom order, of the assignment found
+ *   from the LOWEST matching anchor (-1 where none and past Np);  n_limited [G, Pout];  status [G] = the labelled-read
+ *   bits, GI_SUB_STEP_LIMIT if any of its pairs had a limited anchor, GI_SUB_PATTERN_INDEX.
+ * Limits: N <= GI_MAX_NODES, Fe <= GI_MAX_GROUPS (GI_EINVAL), Fn <= GI_ANALYZE_MAX_FN, Np_max <= GI_SUB_MAX_ATOMS, P <=
+ * GI_SUB_MAX_PATTERNS, max_steps <= GI_SUB_MAX_STEPS (GI_ELIMIT).  G = 0 returns 0 and touches nothing.  Integers only,
+ * no global atomics, no scratch, no memset; every loop is bounded by N, Np, Fe, P or max_steps.
+ * tests/substructure_model.py is the Python specification. */
+#define GI_SUB_MAX_ATOMS 32
+#define GI_SUB_MAX_PATTERNS 65536
+#define GI_SUB_MAX_STEPS (1 << 20)
+#define GI_SUB_STEP_LIMIT (1 << 21)     /* an anchor of this molecule was given up at max_steps */
+#define GI_SUB_PATTERN_INDEX (1 << 22)  /* pattern_index[g] is outside [0, P) */
+int gi_mol_substructure(int G, int N, int Fn, int Fe, const void* nodes, const void* edges, int dtype,
+                        const void* n_nodes, int n_nodes_bytes, int n_types, int n_charges, int n_imp_h,
+                        const unsigned short* allowed, const signed char* order2, const int* patterns_host,
+                        const int* patterns, long long pattern_words, const int* pattern_index, int max_steps,
+                        int* match, int* n_anchors, int* anchors, int* first, int* n_limited, int* status,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
