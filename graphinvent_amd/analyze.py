@@ -44,6 +44,11 @@ reference's RDKit preprocessing on the writer's subset: no stereo, atoms in stri
 ``aromatic="kekulize"`` (``gi_smiles_read_arom``) and then kekulised by the library's own rule, not RDKit's, see
 ``read_smiles``.
 
+``resonance`` / ``kekulize`` / ``canonical_compound`` give ONE IDENTITY PER COMPOUND (``gi_mol_resonance``,
+``gi_mol_kekulize``): which bonds change order between the Kekule structures of a molecule, the molecule with those
+bonds in a channel of their own (the normal form ``canonical`` / ``unique`` / ``SeenSet`` then compare) and back to one
+canonical Kekule structure — a definition without chemistry tables, NOT aromaticity perception, see ``resonance``.
+
 Counts are summed as integers on the device and converted once (the exact integer as fp32, then one fp32 division):
 bit for bit the reference's values while every count is below 2**24.  Beyond that the reference's own fp32
 accumulation (``hist[i] += 1``) stops being exact, e.g. it stays at 16777216 for ever; the counts here stay exact
@@ -1912,3 +1917,147 @@ def substructure_score(result: SubstructureMatches, *, require=(), forbid=()) ->
     for a, b in _column_runs(forb):
         ok = ok & (m[:, a:b] == 0).all(dim=1)
     return ok.to(torch.float32)
+
+
+# ---- the resonance normal form: one identity per compound --------------------------------------------------------------
+#: status bits of ``resonance`` / ``kekulize`` / ``canonical_compound`` beyond the malformed bits
+RESONANCE_STATUS_MESSAGES = {
+    **{bit: VALIDITY_STATUS_MESSAGES[bit] for bit in (L.MOL_ONEHOT, L.MOL_BOND_PAST_N, L.MOL_VALUE, L.MOL_MULTI_BOND,
+                                                      L.MOL_ASYMMETRIC, L.MOL_NODE_PAST_N)},
+    L.RES_EMPTY: "the molecule has no atoms: nothing is delocalised",
+    L.RES_SELF_LOOP: "an atom is bonded to itself: nothing is delocalised, the edges are copied",
+    L.RES_AROMATIC: "a stored bond of order 1.5 is present: left as it is, its atoms take no part (informational)",
+    L.RES_BOND_ORDER: "kekulize: there are delocalised bonds and the rules lack a bond type of order 1 or of order 2",
+    L.RES_NO_KEKULE: "kekulize: the delocalised bonds have no perfect matching (no Kekule structure)",
+}
+#: the bits after which ``kekulize`` writes all-zero edges
+NO_KEKULE_BITS = MALFORMED_BITS | L.RES_EMPTY | L.RES_SELF_LOOP | L.RES_BOND_ORDER | L.RES_NO_KEKULE
+
+
+def describe_resonance_status(bits: int) -> str:
+    return "; ".join(msg for bit, msg in RESONANCE_STATUS_MESSAGES.items() if bits & bit) or "well-formed"
+
+
+class ResonanceForms(_ResultBuffer):
+    """What ``resonance`` wrote, on the device: ``status`` / ``n_delocalized`` (bonds) / ``n_atoms`` / ``n_systems``
+    (connected components of the delocalised bonds) [G] int32 and ``delocalized`` [G, N, 4] int32 (128-bit rows: bit
+    ``j & 31`` of word ``j >> 5`` of row i = bond i-j is delocalised, the layout of ``substructure``'s ``anchors``) as
+    views of one buffer (``host()`` -> ``{name: numpy array}`` of the five); and ``.edges`` [G, N, N, Fe + 1] int8, the
+    normal form, when asked for (``None`` otherwise; not part of ``host()``)."""
+
+    def __init__(self, buf: torch.Tensor, G: int, N: int, edges=None):
+        super().__init__(buf, G, N)
+        self.N, self.edges = N, edges
+
+    @staticmethod
+    @functools.lru_cache(maxsize=64)
+    def layout(G: int, N: int) -> dict:
+        return _pack(("status", "int32", (G,)), ("n_delocalized", "int32", (G,)), ("n_atoms", "int32", (G,)),
+                     ("n_systems", "int32", (G,)), ("delocalized", "int32", (G, N, 4)))
+
+    @staticmethod
+    def _host_result(a):
+        return a
+
+
+def _check_normal_form_width(what: str, edges, extra: int):
+    """``Fe + 1 > GI_MAX_GROUPS`` is refused before anything else looks at the tensors (and before any launch)."""
+    if isinstance(edges, torch.Tensor) and edges.dim() == 4 and edges.shape[3] + extra > L.GI_MAX_GROUPS:
+        raise ValueError(f"{what}: the normal form has one channel more than the Fe = {edges.shape[3] + extra - 1} bond "
+                         f"types, which exceeds the limit of {L.GI_MAX_GROUPS} channels")
+
+
+def resonance(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Optional[torch.Tensor], rules: ValenceRules, *,
+              want_edges: bool = True) -> ResonanceForms:
+    """Which bonds change order between the Kekule structures of each molecule, and the molecules in RESONANCE NORMAL
+    FORM, in one launch (``gi_mol_resonance``) with no read-back; inputs as ``validity``.
+
+    **THIS IS NOT AROMATICITY PERCEPTION, and not RDKit's.**  No Hueckel count, no chemistry table, no moving charges,
+    no tautomers: cyclobutadiene, cyclooctatetraene and pentalene are delocalised; pyrrole, furan, quinone and the
+    five-ring of indole are not, because they have ONE Kekule structure and identity needs nothing there.  The rule
+    (include/graphinvent_amd.h at ``gi_mol_resonance``; tests/resonance_model.py is the specification): among the atoms
+    with exactly one double bond, no triple or 1.5 bond, and a double-bond partner of the same kind, a single or double
+    bond is DELOCALISED iff it lies on a cycle of alternating single and double bonds — iff the molecule has a Kekule
+    structure in which that bond has the other order.  Consequences: all Kekule structures of one compound have the
+    same normal form, byte for byte, and equal normal forms mean Kekule structures of one compound; no acyclic bond is
+    delocalised; every atom's bond-order sum is unchanged.  A stored 1.5 bond is left alone (``RES_AROMATIC``).
+
+    ``.edges`` [G, N, N, Fe + 1] int8 is the normal form: a delocalised bond has channel ``Fe`` set and no other, every
+    other bond is as stored (``Fe + 1 > GI_MAX_GROUPS`` raises ``ValueError``; ``want_edges=False`` writes none).
+    IDENTITY PER COMPOUND is composition, the entry points of ``canonical`` are unchanged::
+
+        r = resonance(nodes, edges, n_nodes, rules)
+        uniq, rep, n_classes = unique(nodes, r.edges, n_nodes, mask=valid)      # likewise fraction_unique, canonical
+        new = seen.add(nodes, r.edges, n_nodes, mask=valid)                     # a SeenSet of normal forms
+
+    (``r.edges`` is int8 whatever the input's dtype; fp32 node states go with it as ``nodes.to(torch.int8)``.)
+
+    ``status`` (``RESONANCE_STATUS_MESSAGES``): the malformed bits, ``RES_EMPTY``, ``RES_SELF_LOOP`` (any of them:
+    nothing is delocalised and the edges are copied, so ``canonical`` says about the normal form what it says about
+    the input) and ``RES_AROMATIC``.  ``delocalized`` is the mask a phase-independent substructure search would take;
+    feeding it to ``substructure`` is not done here."""
+    what = "resonance"
+    _rules_groups(what, rules)
+    if want_edges:
+        _check_normal_form_width(what, edges, 1)
+    G, N, Fn, Fe, dtype, n_nodes, nn_bytes, _ = _check_inputs(what, nodes, edges, n_nodes, None, False)
+    dev = nodes.device
+    A, Cn, H, order2 = _check_rules(what, rules, Fn, Fe, dev)
+    out_e = torch.empty((G, N, N, Fe + 1), dtype=torch.int8, device=dev) if want_edges else None
+    res = ResonanceForms.empty(dev, G, N, edges=out_e)
+    if G > 0:
+        out = res._ptrs()
+        with torch.cuda.device(dev):
+            L.check(L.load().gi_mol_resonance(
+                G, N, Fn, Fe, nodes.data_ptr(), edges.data_ptr(), dtype,
+                None if n_nodes is None else n_nodes.data_ptr(), nn_bytes, A, Cn, H, order2.data_ptr(), out["status"],
+                out["n_delocalized"], out["n_atoms"], out["n_systems"], out["delocalized"],
+                None if out_e is None else out_e.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+                "gi_mol_resonance")
+    return res
+
+
+def kekulize(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Optional[torch.Tensor], rules: ValenceRules):
+    """The inverse of ``resonance``: molecules in normal form (``edges`` [G, N, N, Fe + 1], fp32 or int8, the rules
+    holding ``Fe`` bond orders) -> ``(edges [G, N, N, Fe] int8, status [G] int32)``, one launch (``gi_mol_kekulize``),
+    no read-back.  Every atom on a channel-``Fe`` bond gets exactly one double bond among those bonds: a perfect
+    matching found as the SMILES reader's kekuliser finds it (greedy in ascending index, then augmenting paths with
+    blossom contraction, neighbours ascending), the other channel-``Fe`` bonds become single.  THE CHOICE IS A FUNCTION
+    OF THE INDEXED GRAPH, not a chemical preference: on canonical molecules it is a canonical Kekule structure
+    (``canonical_compound``).  ``status``: ``RES_NO_KEKULE`` (no perfect matching), ``RES_BOND_ORDER`` (no single or
+    no double type in the rules), the malformed bits, ``RES_EMPTY``, ``RES_SELF_LOOP`` — after any of them
+    (``NO_KEKULE_BITS``) the molecule's edges are all zero — and ``RES_AROMATIC``."""
+    what = "kekulize"
+    _rules_groups(what, rules)
+    _check_normal_form_width(what, edges, 0)
+    G, N, Fn, Fi, dtype, n_nodes, nn_bytes, _ = _check_inputs(what, nodes, edges, n_nodes, None, False)
+    if Fi < 2:
+        raise ValueError(f"{what}: edges must hold Fe + 1 >= 2 channels (the bond types and the delocalised channel)")
+    dev = nodes.device
+    A, Cn, H, order2 = _check_rules(what, rules, Fn, Fi - 1, dev)
+    out_e = torch.empty((G, N, N, Fi - 1), dtype=torch.int8, device=dev)
+    status = torch.empty(G, dtype=torch.int32, device=dev)
+    if G > 0:
+        with torch.cuda.device(dev):
+            L.check(L.load().gi_mol_kekulize(
+                G, N, Fn, Fi - 1, nodes.data_ptr(), edges.data_ptr(), dtype,
+                None if n_nodes is None else n_nodes.data_ptr(), nn_bytes, A, Cn, H, order2.data_ptr(),
+                status.data_ptr(), out_e.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "gi_mol_kekulize")
+    return out_e, status
+
+
+def canonical_compound(nodes: torch.Tensor, edges: torch.Tensor, n_nodes: Optional[torch.Tensor], rules: ValenceRules):
+    """One representative per COMPOUND: ``resonance`` -> ``canonical(..., want_molecules=True)`` on the normal form ->
+    ``kekulize`` of the canonical molecules; three launches, no read-back.  -> ``(nodes [G, N, Fn] int8, edges
+    [G, N, N, Fe] int8, key [G, 2] int64, status [G] int32)``: the canonical nodes, the canonical Kekule structure (a
+    molecule every other entry point takes: ``smiles`` of it writes ONE string per compound, whatever the node order
+    and the stored phase of the input), ``canonical``'s key of the normal form, and ``resonance``'s status with
+    ``canonical``'s bits and ``kekulize``'s ``RES_NO_KEKULE`` / ``RES_BOND_ORDER`` added.  A molecule with a malformed
+    bit has zero nodes and edges, as in ``canonical``; ``canonical``'s completeness caveat applies unchanged."""
+    r = resonance(nodes, edges, n_nodes, rules)
+    if nodes.dtype != torch.int8:                            # the normal form is int8: 0, 1, and 2 for any other entry
+        nodes = nodes.ne(0).to(torch.int8) + (nodes.ne(0) & nodes.ne(1)).to(torch.int8)
+    can = canonical(nodes, r.edges, n_nodes, want_molecules=True)
+    k_edges, k_status = kekulize(can.nodes, can.edges, n_nodes, rules)
+    status = r.status | can.status | (k_status & (L.RES_NO_KEKULE | L.RES_BOND_ORDER))
+    return can.nodes, k_edges, can.key, status

@@ -175,6 +175,8 @@ SMR_READ_ERROR = SMR_ERROR | SMR_KEKULE                 # GI_SMR_ERROR: SMR_ERRO
 MASK_STRUCTURAL, MASK_MAX_COMBOS = 1 << 20, 4096        # GI_MASK_* of gi_action_mask
 SUB_MAX_ATOMS, SUB_MAX_PATTERNS, SUB_MAX_STEPS = 32, 65536, 1 << 20      # GI_SUB_* of gi_mol_substructure
 SUB_STEP_LIMIT, SUB_PATTERN_INDEX = 1 << 21, 1 << 22
+RES_EMPTY, RES_SELF_LOOP, RES_AROMATIC = 128, 256, 2048  # GI_RES_* of gi_mol_resonance / gi_mol_kekulize
+RES_BOND_ORDER, RES_NO_KEKULE = 1 << 22, 1 << 26        # gi_mol_kekulize only
 
 
 class RouteDims(C.Structure):
@@ -328,6 +330,8 @@ SIGNATURES = {
     "gi_action_mask_stats": (ci, [ci, vp, vp, vp, vp, vp]),
     "gi_mol_substructure": (ci, [ci, ci, ci, ci, vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp, cll, vp, ci,
                                  vp, vp, vp, vp, vp, vp, vp]),
+    "gi_mol_resonance": (ci, [ci, ci, ci, ci, vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "gi_mol_kekulize": (ci, [ci, ci, ci, ci, vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp]),
 }
 FUSE_GATES_V4, FUSE_DH_SCATTER, FUSE_TIER2_DSELU, FUSE_SLOTS = 1, 2, 4, 8  # GI_FUSE_*
 GLUE_READOUT_FWD, GLUE_READOUT_BWD, GLUE_LOSS_MEAN, GLUE_GRU_AGG = 1, 2, 4, 8  # GI_GLUE_*

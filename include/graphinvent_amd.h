@@ -1585,6 +1585,65 @@ int gi_mol_substructure(int G, int N, int Fn, int Fe, const void* nodes, const v
                         int* match, int* n_anchors, int* anchors, int* first, int* n_limited, int* status,
                         void* stream);
 
+/* ---- the resonance normal form: one identity per compound (csrc/gi_resonance.hip) ----
+ * gi_mol_canon compares labelled graphs, so two Kekule structures of one compound are two molecules.  gi_mol_resonance
+ * says which bonds change order between the Kekule structures of a molecule and writes the molecule with those bonds
+ * moved to a channel of their own; on that NORMAL FORM gi_mol_canon / gi_mol_unique / gi_mol_seen_add see one compound.
+ * THIS IS NOT AROMATICITY PERCEPTION (and not RDKit's): no Hueckel count, no chemistry table, no moving charges, no
+ * tautomers.  Cyclobutadiene, cyclooctatetraene and pentalene are delocalised; pyrrole, furan, quinone and the five-ring
+ * of indole are not: they have ONE Kekule structure, so identity needs nothing there.
+ *
+ * The rule, for a well-formed molecule (the labelled read of gi_mol_valence: any GI_MOL_* bit, GI_RES_EMPTY or
+ * GI_RES_SELF_LOOP and nothing is delocalised), orders from order2 [Fe] (twice the bond order):
+ *   d(i) = the number of order-2 bonds at atom i;  t(i) = the number of bonds of order 3 or 1.5 at atom i;
+ *   V' = the atoms with d = 1 and t = 0 whose double-bond partner also has d = 1 and t = 0;
+ *   G' = (V', the bonds of order 1 or 2 between two members of V'); the double bonds inside V' are a perfect matching
+ *        M of G';
+ *   a bond e = (a, b) of G' is DELOCALISED iff   order 2: G' - e (the edge removed) has a perfect matching;
+ *                                                order 1: G' - a - b (both atoms removed) has a perfect matching;
+ *   equivalently iff e lies on an M-alternating cycle.  No other bond is delocalised.
+ *   Normal form: nodes unchanged; edges_out [G, N, N, Fe + 1] int8: a delocalised bond has channel Fe set and no other,
+ *   every other set entry is as stored (1; 2 throughout a molecule with GI_MOL_VALUE, so that gi_mol_canon reports on
+ *   the normal form what it reports on the stored molecule).
+ * What follows, and tests/test_resonance_cpu.py checks:
+ *   PHASE INVARIANCE  V' and G' do not depend on the stored phase and the verdict is a property of G': all Kekule
+ *     structures of one compound (same atoms, charges and hydrogens, the double bonds another perfect matching of G')
+ *     have the same normal form, byte for byte.  CONVERSE: equal normal forms mean the two stored structures are
+ *     perfect matchings of one G'.
+ *   ONLY RING BONDS  no acyclic bond is delocalised (butadiene has none).
+ *   VALENCE-NEUTRAL  every atom's bond-order sum is unchanged by the normal form and by gi_mol_kekulize.
+ *   A stored bond of order 1.5 is left as it is, keeps its atoms out of V' and raises GI_RES_AROMATIC (informational).
+ * The verdict is definitional; HOW it is found is free.  Here: with M in hand, G' - e has a perfect matching iff one
+ * augmenting path joins a and b, G' - a - b iff one joins the partners of a and b (breadth-first search with blossom
+ * contraction, csrc/gi_res_search.h, 64 searches of a molecule at once); a path found closes an alternating cycle, all
+ * of whose bonds are marked at once.
+ * Outputs: status [G] (the labelled-read bits, GI_RES_AROMATIC), n_delocalized [G] (bonds), n_atoms [G] (atoms on
+ * one), n_systems [G] (connected components of the delocalised bonds), delocalized [G, N, 4] (128-bit rows: bit j & 31
+ * of word j >> 5 of row i = bond i-j is delocalised; the layout of gi_mol_substructure's anchors), edges_out as above or
+ * NULL (then nothing is written and Fe may be GI_MAX_GROUPS; with edges_out, Fe + 1 > GI_MAX_GROUPS is GI_ELIMIT).
+ *
+ * gi_mol_kekulize is the inverse: edges [G, N, N, Fe + 1] (fp32 or int8), order2 [Fe].  An atom NEEDS a double bond
+ * when it carries a channel-Fe bond; the candidate graph is the channel-Fe bonds; a perfect matching is looked for as
+ * in gi_smiles_read_arom (greedy in ascending index, then one search per free atom, neighbours ascending; ONE lane).
+ * Matched bonds get the first type of order 2, every other channel-Fe bond the first type of order 1; edges_out
+ * [G, N, N, Fe] int8.  No perfect matching: GI_RES_NO_KEKULE; channel-Fe bonds and no type of order 1 or none of order
+ * 2: GI_RES_BOND_ORDER; either, or an unsound molecule: all-zero edges.  The choice is a function of the indexed graph:
+ * applied to canonical molecules (gi_mol_canon of the normal form) it is a canonical Kekule structure.
+ * Both: G = 0 returns 0 and touches nothing.  Integers only, no global atomics, no scratch, no memset; every loop is
+ * bounded by N or by the number of G' bonds.  tests/resonance_model.py is the Python specification. */
+#define GI_RES_EMPTY 128                /* = GI_VAL_EMPTY */
+#define GI_RES_SELF_LOOP 256            /* = GI_VAL_SELF_LOOP */
+#define GI_RES_AROMATIC 2048            /* = GI_VAL_AROMATIC: a stored bond of order 1.5 (informational) */
+#define GI_RES_BOND_ORDER (1 << 22)     /* gi_mol_kekulize: the rules lack a type of order 1 or of order 2 */
+#define GI_RES_NO_KEKULE (1 << 26)      /* gi_mol_kekulize: the channel-Fe bonds have no perfect matching */
+int gi_mol_resonance(int G, int N, int Fn, int Fe, const void* nodes, const void* edges, int dtype,
+                     const void* n_nodes, int n_nodes_bytes, int n_types, int n_charges, int n_imp_h,
+                     const signed char* order2, int* status, int* n_delocalized, int* n_atoms, int* n_systems,
+                     int* delocalized, signed char* edges_out, void* stream);
+int gi_mol_kekulize(int G, int N, int Fn, int Fe, const void* nodes, const void* edges, int dtype,
+                    const void* n_nodes, int n_nodes_bytes, int n_types, int n_charges, int n_imp_h,
+                    const signed char* order2, int* status, signed char* edges_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
